@@ -8,13 +8,16 @@ through the C-ABI (limo_ba_batch_reset + limo_ba_batch_solve).  Inputs are resid
 value = windows solved per second over all ranks.  The windows of a batch stream through the library's slots
 (kba_kernels.hip:k_sched), so the batch is several times the number of windows in flight.
 
-  python bench.py --gpus N --steps K --warmup W [--batch B] [--no-extras] [--no-cpu-baseline] [--no-pmc]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline] [--no-pmc]]
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the batch's `config`).
+--dump-outputs DIR writes what the last timed step computed (bench.py:dump_outputs) as DIR/<name>.npy; the inputs depend on the
+arguments only, so two builds can be compared output for output.
 N > 1: one rank per GPU (launched by the driver with torch.distributed.run, or by this script itself when it is
 started as a plain `python bench.py --gpus N`); windows are independent, so ranks take disjoint batches with NO
 data-path collective ("replicas only" for this configuration) - weak scaling.  The landmark-sharded solve
 of ONE large window (configs[3], one RCCL all-gather of a 42 KB block per LM iteration) is timed in the `c4` entry when N >= 2.
 
-Besides the headline the JSON line carries (rank 0): `roofline` (k_lin_lm, the Jacobian evaluation: `achieved` on the FUSED unit of
+With --full, besides the headline the JSON line carries (rank 0): `roofline` (k_lin_lm, the Jacobian evaluation: `achieved` on the FUSED unit of
 SURVEY 8d - never above the peak -, `traffic` measured IN this run by rocprofv3 counter passes in a child process when rocprofv3 is
 on PATH (scripts/pmc_collect.py; --no-pmc skips them), `frac` = traffic / kernel time / 8 TB/s, `limited_by`), `roofline_schur` (MFMA),
 `roofline_evaluate` (the MATERIALISED Jacobian kernel of SURVEY 8d), `parity` (the oracle on windows of this very batch against the GPU
@@ -76,6 +79,17 @@ UNFUSED_PMC_FILE = os.path.join(ROOT, "profiles", "r02_pmc_kernels_unfused_pipel
 UNFUSED_BYTES_PER_OBS = 226.1  # k_linearize 101.3 + k_lm_accum 92.6 + k_lm_damp 32.2 B per observation (that file), before they became one pass
 
 
+def _host_cpus():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS when the job sets it (os.cpu_count() is the
+    whole host's)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "0")) or n)
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def _make_window(args):
     from limo_amd import synth
 
@@ -86,7 +100,7 @@ def _make_window(args):
 def generate_windows(seeds, n_kf, n_lm):
     """Synthetic windows, generated by a pool of host processes (10 ms each in numpy; forked before any GPU state exists)."""
     jobs = [(s, n_kf, n_lm) for s in seeds]
-    n_proc = min(32, os.cpu_count() or 1, max(1, len(jobs) // 16))
+    n_proc = min(32, _host_cpus(), max(1, len(jobs) // 16))
     if n_proc <= 1:
         return [_make_window(j) for j in jobs]
     import multiprocessing as mp
@@ -138,6 +152,12 @@ def main():
     ap.add_argument("--distinct", type=int, default=int(os.environ.get("LIMO_BENCH_DISTINCT", "4096")),
                     help="distinct windows generated per rank (0 = every window of the batch is different); the batch repeats them, "
                          "every copy is an independent solve on the device")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the rooflines (one more step with one slot group, rocprofv3 counter passes), the C4 "
+                         "solve, the single-window / batch-size / end-to-end / depth entries and the CPU baseline with parity; the --no-* "
+                         "options below trim what --full adds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, < 64 MB; rank 0's batch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline + rooflines only (no parity / single-window / end-to-end / depth / C4 entries)")
     ap.add_argument("--cpu-solves", type=int, default=20)
@@ -156,6 +176,8 @@ def main():
     selftest = args.selftest_dist
     if selftest:
         args.batch, args.n_lm, args.no_cpu_baseline, args.no_extras = min(args.batch, 4), min(args.n_lm, 60), True, True
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline, args.no_extras = True, True
 
     # ---- synthetic input first (host processes; no GPU state yet): `distinct` different windows per rank, tiled to the
     # batch size (each copy is an independent solve), distinct seeds per rank
@@ -224,38 +246,24 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     reps = batch.download()  # batch.windows now hold the GPU results
-    # Per-kernel times for the rooflines: one more step with ONE slot group - with several groups the kernels of
-    # different groups overlap on the device and event timing of a single kernel means nothing.
-    if not selftest:
-        os.environ["KBA_GROUPS"] = "1"
-        batch.kernel_stats(reset=True)
-        step()
-        torch.cuda.synchronize()
-        del os.environ["KBA_GROUPS"]
-    stats = batch.kernel_stats(reset=False)
-    prof_steps = 1 if not selftest else args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, reps, distinct)
+    if args.full:
+        # Per-kernel times for the rooflines: one more step with ONE slot group - with several groups the kernels of
+        # different groups overlap on the device and event timing of a single kernel means nothing.
+        if not selftest:
+            os.environ["KBA_GROUPS"] = "1"
+            batch.kernel_stats(reset=True)
+            step()
+            torch.cuda.synchronize()
+            del os.environ["KBA_GROUPS"]
+        stats = batch.kernel_stats(reset=False)
+        prof_steps = 1 if not selftest else args.steps
 
     out = None
     if rank == 0:
         total_windows = args.batch * world * args.steps
         value = total_windows / elapsed
-        # ---- roofline of the Jacobian evaluation (k_lin_lm): what one launch linearises, from the reports of this very run
-        lin_obs = sum(r["num_linearizations"] * w.n_obs for r, w in zip(reps, windows)) * prof_steps
-        lin_lms = sum(r["num_linearizations"] * w.n_lm for r, w in zip(reps, windows)) * prof_steps
-        # (round 6: the kernel also moves the landmarks of an accepted step from the candidate buffer into place - the former k_accept
-        # pass -: 24 B written per landmark and accepted step; every accepted step is followed by exactly one linearisation)
-        acc_lms = sum(r["successful_steps"] * w.n_lm for r, w in zip(reps, windows)) * prof_steps
-        alg_bytes = FUSED_BYTES_PER_OBS * lin_obs + FUSED_BYTES_PER_LANDMARK * lin_lms + ACCEPT_MOVE_BYTES_PER_LANDMARK * acc_lms
-        launches = max(1, stats["linearize_launches"])
-        lin_ms = stats["linearize_ms"]
-        lin_s = max(1e-12, lin_ms * 1e-3)
-        achieved = alg_bytes / lin_s / 1e9
-        # ---- second dominant kernel: the Schur complement (f64 MFMA).  Algorithmic flops of one window iteration =
-        # n_c^2 * 3N (SYRK of the 3N x n_c landmark-eliminated block; n_c free camera slots, N landmarks left)
-        nf = [10 * (w.n_kf - 1) for w in windows]  # first keyframe Pose-fixed, every other keyframe 6 + 3 + 1 slots
-        schur_flops = sum(r["iterations_total"] * (n * n * 3.0 * (w.n_lm - r["n_trimmed_landmarks"])) for r, n, w in zip(reps, nf, windows)) * prof_steps
-        schur_ms = stats["schur_ms"]
-        schur_tf = schur_flops / (schur_ms * 1e-3) / 1e12 if schur_ms > 0 else 0.0
         out = {
             "metric": "keyframe-BA window solves/sec (5 KF, ~2k landmarks)",
             "value": value,
@@ -284,54 +292,74 @@ def main():
                 "accept_ratio": float(sum(r["successful_steps"] for r in reps)) / max(1, sum(r["iterations_total"] for r in reps)),
                 "linearisations_per_iteration": float(sum(r["num_linearizations"] for r in reps)) / max(1, sum(r["iterations_total"] for r in reps)),
             },
-            "roofline": {
-                "kernel": "k_lin_lm (Jacobian evaluation + landmark blocks + damping, landmark-major; SURVEY 8d's fused normal-equation path)",
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS,
-                "frac_definition": "achieved / peak: algorithmic bytes / kernel time / 8 TB/s (the fraction on the bytes the counters saw: traffic_frac)",
-                "traffic": None,
-                "traffic_source": None,
-                "launches": stats["linearize_launches"],
-                "avg_launch_ms": lin_ms / launches,
-                "algorithmic_bytes_per_launch": alg_bytes / launches,
-                "algorithmic_unit": "SURVEY 8d fused path: 52 B read per observation + 72 B (V, g) written per landmark, + the 16 B per observation of factored "
-                                    "Jacobian planes this design stores in place of W (144 B per pair), + 24 B per landmark and ACCEPTED step (the landmark moved into place by the "
-                                    "relinearisation since round 6); x the observations / landmarks this run linearised",
-                "fp64": {"achieved": FP64_FLOPS_PER_LINEARISED_OBS * lin_obs / lin_s / 1e12, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": FP64_FLOPS_PER_LINEARISED_OBS * lin_obs / lin_s / 1e12 / F64_MFMA_PEAK_TFLOPS,
-                         "algorithmic_flops_per_observation": FP64_FLOPS_PER_LINEARISED_OBS,
-                         "what": "algorithmic fp64 flops of the fused linearisation (~300 multiply-adds per (landmark, view) pair) / kernel time / the fp64 vector = matrix peak"},
-                "linearised_observations_per_launch": lin_obs / launches,
-                "measured_in": "one extra step with a single slot group (kernels of different groups overlap in the timed steps); HIP events on the kernel's stream",
-                "materialised_kernel": "the SURVEY 8d MATERIALISED Jacobian pass (212 B / observation + 84 B / depth observation) is k_evaluate: see roofline_evaluate",
-                "kernel_share_of_device_time": lin_ms / stats["total_ms"] if stats["total_ms"] > 0 else None,
-                "_lin_obs": lin_obs, "_lin_s": lin_s,
-            },
-            "roofline_schur": {
-                "kernel": "k_schur_lean (plain + ground-plane blocks)",
-                "bound": "mfma",
-                "achieved": schur_tf,
-                "peak": F64_MFMA_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": schur_tf / F64_MFMA_PEAK_TFLOPS,
-                "traffic": None,
-                "launches": stats["schur_launches"],
-                "avg_launch_ms": schur_ms / max(1, stats["schur_launches"]),
-                "algorithmic_flops_per_launch": schur_flops / max(1, stats["schur_launches"]),
-                "kernel_share_of_device_time": schur_ms / stats["total_ms"] if stats["total_ms"] > 0 else None,
-            },
         }
+        if args.full:
+            # ---- roofline of the Jacobian evaluation (k_lin_lm): what one launch linearises, from the reports of this very run
+            lin_obs = sum(r["num_linearizations"] * w.n_obs for r, w in zip(reps, windows)) * prof_steps
+            lin_lms = sum(r["num_linearizations"] * w.n_lm for r, w in zip(reps, windows)) * prof_steps
+            # (round 6: the kernel also moves the landmarks of an accepted step from the candidate buffer into place - the former k_accept
+            # pass -: 24 B written per landmark and accepted step; every accepted step is followed by exactly one linearisation)
+            acc_lms = sum(r["successful_steps"] * w.n_lm for r, w in zip(reps, windows)) * prof_steps
+            alg_bytes = FUSED_BYTES_PER_OBS * lin_obs + FUSED_BYTES_PER_LANDMARK * lin_lms + ACCEPT_MOVE_BYTES_PER_LANDMARK * acc_lms
+            launches = max(1, stats["linearize_launches"])
+            lin_ms = stats["linearize_ms"]
+            lin_s = max(1e-12, lin_ms * 1e-3)
+            achieved = alg_bytes / lin_s / 1e9
+            # ---- second dominant kernel: the Schur complement (f64 MFMA).  Algorithmic flops of one window iteration =
+            # n_c^2 * 3N (SYRK of the 3N x n_c landmark-eliminated block; n_c free camera slots, N landmarks left)
+            nf = [10 * (w.n_kf - 1) for w in windows]  # first keyframe Pose-fixed, every other keyframe 6 + 3 + 1 slots
+            schur_flops = sum(r["iterations_total"] * (n * n * 3.0 * (w.n_lm - r["n_trimmed_landmarks"])) for r, n, w in zip(reps, nf, windows)) * prof_steps
+            schur_ms = stats["schur_ms"]
+            schur_tf = schur_flops / (schur_ms * 1e-3) / 1e12 if schur_ms > 0 else 0.0
+            out.update({
+                "roofline": {
+                    "kernel": "k_lin_lm (Jacobian evaluation + landmark blocks + damping, landmark-major; SURVEY 8d's fused normal-equation path)",
+                    "bound": "hbm",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBPS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBPS,
+                    "frac_definition": "achieved / peak: algorithmic bytes / kernel time / 8 TB/s (the fraction on the bytes the counters saw: traffic_frac)",
+                    "traffic": None,
+                    "traffic_source": None,
+                    "launches": stats["linearize_launches"],
+                    "avg_launch_ms": lin_ms / launches,
+                    "algorithmic_bytes_per_launch": alg_bytes / launches,
+                    "algorithmic_unit": "SURVEY 8d fused path: 52 B read per observation + 72 B (V, g) written per landmark, + the 16 B per observation of factored "
+                                        "Jacobian planes this design stores in place of W (144 B per pair), + 24 B per landmark and ACCEPTED step (the landmark moved into place by the "
+                                        "relinearisation since round 6); x the observations / landmarks this run linearised",
+                    "fp64": {"achieved": FP64_FLOPS_PER_LINEARISED_OBS * lin_obs / lin_s / 1e12, "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": FP64_FLOPS_PER_LINEARISED_OBS * lin_obs / lin_s / 1e12 / F64_MFMA_PEAK_TFLOPS,
+                             "algorithmic_flops_per_observation": FP64_FLOPS_PER_LINEARISED_OBS,
+                             "what": "algorithmic fp64 flops of the fused linearisation (~300 multiply-adds per (landmark, view) pair) / kernel time / the fp64 vector = matrix peak"},
+                    "linearised_observations_per_launch": lin_obs / launches,
+                    "measured_in": "one extra step with a single slot group (kernels of different groups overlap in the timed steps); HIP events on the kernel's stream",
+                    "materialised_kernel": "the SURVEY 8d MATERIALISED Jacobian pass (212 B / observation + 84 B / depth observation) is k_evaluate: see roofline_evaluate",
+                    "kernel_share_of_device_time": lin_ms / stats["total_ms"] if stats["total_ms"] > 0 else None,
+                    "_lin_obs": lin_obs, "_lin_s": lin_s,
+                },
+                "roofline_schur": {
+                    "kernel": "k_schur_lean (plain + ground-plane blocks)",
+                    "bound": "mfma",
+                    "achieved": schur_tf,
+                    "peak": F64_MFMA_PEAK_TFLOPS,
+                    "unit": "TFLOP/s",
+                    "frac": schur_tf / F64_MFMA_PEAK_TFLOPS,
+                    "traffic": None,
+                    "launches": stats["schur_launches"],
+                    "avg_launch_ms": schur_ms / max(1, stats["schur_launches"]),
+                    "algorithmic_flops_per_launch": schur_flops / max(1, stats["schur_launches"]),
+                    "kernel_share_of_device_time": schur_ms / stats["total_ms"] if stats["total_ms"] > 0 else None,
+                },
+            })
     batch.close()
 
     # ---- HBM traffic of k_lin_lm, MEASURED in this run when rocprofv3 is there: two counter passes (FETCH_SIZE, WRITE_SIZE - they
     # do not share a pass) + one SQ pass over full 1024-window rounds of the same kernels (scripts/pmc_collect.py), in a child
     # process after the batch has released its memory; else the stored, sha-bound profile; else nothing.
-    if rank == 0 and not selftest:
+    if rank == 0 and args.full and not selftest:
         fill_traffic(out["roofline"], out["roofline_schur"], measure=not args.no_pmc and world == 1, timeout=args.pmc_timeout)
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["roofline"].pop("_lin_obs"), out["roofline"].pop("_lin_s")
 
     # ---- C4: landmark-sharded solve of one large window (every rank takes part when N >= 2)
@@ -382,6 +410,51 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LANDMARK_BYTES = 32 << 20  # landmark positions of a seeded sample of the distinct windows (all of them: ~200 MB at the defaults)
+REPORT_KEYS = ("termination", "num_solves", "iterations_total", "iterations_final", "successful_steps", "n_depth_blocks", "n_repr_blocks",
+               "n_gp_blocks", "n_trimmed_landmarks", "num_linearizations", "initial_cost", "final_cost")  # (time_sec: host clock, not a result)
+
+
+def dump_outputs(path, batch, reps, distinct):
+    """--dump-outputs: what limo_ba_batch_download hands the caller after the last timed step, as float64 .npy files.
+    Copies of a window share its host buffers (identical solves), so the parameters are stored once per distinct window:
+      report_<field>       [batch]            every field of limo_ba_report but the host timer
+      kf_pose              [distinct, K, 7]   keyframe poses;  kf_plane_dir [distinct, K, 3], kf_plane_dist [distinct, K]
+      lm_sample_windows    [S]                the distinct windows of the landmark sample (seeded, ~32 MB of positions)
+      lm_sample_offsets    [S + 1]            their rows in lm_pos_sample
+      lm_pos_sample        [rows, 3]          landmark positions of those windows
+      lm_trimmed_sample    [rows]             1 where the trimming rounds removed the landmark (limo_ba_batch_trimmed)"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    ws = batch.windows[:distinct]
+    out = {"report_" + k: np.array([r[k] for r in reps], np.float64) for k in REPORT_KEYS if reps and k in reps[0]}  # (the stub has fewer)
+    for name in ("kf_pose", "kf_plane_dir", "kf_plane_dist"):
+        out[name] = np.stack([getattr(w, name) for w in ws]).astype(np.float64)
+    order, budget, pick = np.random.default_rng(20261016).permutation(len(ws)), DUMP_LANDMARK_BYTES, []
+    for i in order:
+        budget -= ws[i].lm_pos.nbytes
+        if budget < 0:
+            break
+        pick.append(int(i))
+    pick.sort()
+    out["lm_sample_windows"] = np.array(pick, np.float64)
+    out["lm_sample_offsets"] = np.concatenate([[0], np.cumsum([ws[i].n_lm for i in pick])]).astype(np.float64)
+    out["lm_pos_sample"] = np.concatenate([ws[i].lm_pos for i in pick] or [np.zeros((0, 3))]).astype(np.float64)
+    if hasattr(batch, "trimmed"):  # (not the --selftest-dist stub)
+        flags = []
+        for i in pick:  # window i of the batch is the first copy of distinct window i
+            f = np.zeros(ws[i].n_lm, np.float64)
+            f[batch.trimmed(i)] = 1.0
+            flags.append(f)
+        out["lm_trimmed_sample"] = np.concatenate(flags or [np.zeros(0)])
+    total = sum(a.nbytes for a in out.values())
+    if total > 64 << 20:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (limit 64 MB)" % (total / 1e6))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------- extras

@@ -1,7 +1,7 @@
 # A/B of two library builds alternating on one box: scripts/gpu_ab_libs.sh TAG1:LIB1 TAG2:LIB2   (LIB empty = the product build)
 for rep in 1 2; do for cfg in "$@"; do
   tag=${cfg%%:*}; lib=${cfg#*:}
-  env ${lib:+LIMO_HIP_LIB=$PWD/$lib} python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > /tmp/b_$tag.json 2>/tmp/b_$tag.err || tail -3 /tmp/b_$tag.err
+  env ${lib:+LIMO_HIP_LIB=$PWD/$lib} python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-pmc > /tmp/b_$tag.json 2>/tmp/b_$tag.err || tail -3 /tmp/b_$tag.err
   python - <<PY
 import json
 d=json.load(open("/tmp/b_$tag.json"))

@@ -1,6 +1,6 @@
 # A/B of the fused launch train (KBA_UNFUSED_TRAIN=1: the round-5 sequence of launches), alternating on one box
 for v in 1 0 1 0; do
-  KBA_NO_SCHUR_PAIR=$v python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > /tmp/b_$v.json 2>/tmp/b_$v.err || tail -3 /tmp/b_$v.err
+  KBA_NO_SCHUR_PAIR=$v python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-pmc > /tmp/b_$v.json 2>/tmp/b_$v.err || tail -3 /tmp/b_$v.err
   python - <<PY
 import json
 d=json.load(open("/tmp/b_$v.json"))

@@ -2,7 +2,7 @@
 # Closing run of round 4 on the final sources: the bench line (in-run counter passes), then the drive with the depth thread and without.
 OUT=gpurun_out/r04f
 mkdir -p $OUT
-( time python bench.py > $OUT/bench.json 2> $OUT/bench.err ) 2>&1 | grep real; tail -2 $OUT/bench.err; head -c 400 $OUT/bench.json; echo
+( time python bench.py --full > $OUT/bench.json 2> $OUT/bench.err ) 2>&1 | grep real; tail -2 $OUT/bench.err; head -c 400 $OUT/bench.json; echo
 app=$(python -c "import sys; sys.path.insert(0,'tests'); import emu_ffi; print(emu_ffi.build_stream_app(gpu=True))")
 for mode in thread none thread; do
   echo "== limo_stream --depth-ahead $mode"

@@ -7,9 +7,10 @@ mkdir -p gpurun_out profiles
 cp gpurun_out/r02_pmc_kernels.json profiles/r02_pmc_kernels.json
 ( time LIMO_FUZZ_SCALE=1 python -m pytest tests -m gpu -x -q ) > gpurun_out/pytest_gpu.log 2>&1; grep -E "passed|failed|real" gpurun_out/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py > gpurun_out/r02_bench.json 2> gpurun_out/r02_bench.err; tail -2 gpurun_out/r02_bench.err; head -c 1500 gpurun_out/r02_bench.json; echo
+OUT=${OUT:-results}; mkdir -p $OUT  # the bench line and its kernel table
+python bench.py --full > $OUT/r02_bench.json 2> $OUT/r02_bench.err; tail -2 $OUT/r02_bench.err; head -c 1500 $OUT/r02_bench.json; echo
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_bench -o bench -- python bench.py --no-extras --no-cpu-baseline > gpurun_out/prof_bench.log 2>&1
-grep '^{' gpurun_out/prof_bench.log > gpurun_out/r02_bench_under_rocprof.json
-python scripts/prof_summary.py gpurun_out/prof_bench/bench_results.db > gpurun_out/r02_rocprof_kernel_stats_bench.txt; head -22 gpurun_out/r02_rocprof_kernel_stats_bench.txt
+rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o bench -- python bench.py --full --no-extras --no-cpu-baseline > $OUT/prof_bench.log 2>&1
+grep '^{' $OUT/prof_bench.log > $OUT/r02_bench_under_rocprof.json
+python scripts/prof_summary.py $OUT/prof_bench/bench_results.db > $OUT/r02_rocprof_kernel_stats_bench.txt; head -22 $OUT/r02_rocprof_kernel_stats_bench.txt
 ./scripts/gpu_single_prof.sh > gpurun_out/r02_rocprof_kernel_stats_single_window.txt 2>&1; head -3 gpurun_out/r02_rocprof_kernel_stats_single_window.txt

@@ -6,9 +6,9 @@
 # Counter passes carry --kernel-trace only (no other trace domains).   usage: scripts/gpu_round_r04.sh [SKIP_DRIVE=1]
 OUT=gpurun_out/r04
 mkdir -p $OUT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err; head -c 300 $OUT/bench.json; echo
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -2 $OUT/bench.err; head -c 300 $OUT/bench.json; echo
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-KBA_GROUPS=1 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_bench1 -o bench -- python bench.py --no-extras --no-cpu-baseline --no-pmc > $OUT/prof_bench1.log 2>&1
+KBA_GROUPS=1 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_bench1 -o bench -- python bench.py --full --no-extras --no-cpu-baseline --no-pmc > $OUT/prof_bench1.log 2>&1
 python scripts/prof_summary.py $OUT/prof_bench1/bench_results.db > $OUT/rocprof_kernel_stats_bench_one_group.txt; head -22 $OUT/rocprof_kernel_stats_bench_one_group.txt
 rm -rf $OUT/prof_bench1
 timeout 600 python scripts/pmc_collect.py --passes all --out $OUT/pmc_kernels.json --timeout 500 | tee $OUT/pmc_summary.txt

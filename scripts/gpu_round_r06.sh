@@ -19,12 +19,12 @@ if [ -n "$TESTS" ]; then
   ( time timeout 1800 python -m pytest tests -m gpu -x -q -s ${PYTEST_ARGS:-} ) > $OUT/pytest_gpu.log 2>&1; grep -E "passed|failed|error|Error|assert|^real|^fuzz seed|ulp|chol3" $OUT/pytest_gpu.log | tail -24
 fi
 if [ -z "$NO_BENCH" ]; then
-  ( time python bench.py $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err ) 2>&1 | grep real; tail -2 $OUT/bench.err; head -c 400 $OUT/bench.json; echo
+  ( time python bench.py --full $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err ) 2>&1 | grep real; tail -2 $OUT/bench.err; head -c 400 $OUT/bench.json; echo
 fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 table() {  # table NAME [LIB]
   rm -rf $OUT/prof_$1
-  env KBA_GROUPS=1 ${2:+LIMO_HIP_LIB=$2} timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$1 -o bench -- python bench.py ${TABLE_ARGS:---steps 5 --warmup 2} --no-extras --no-cpu-baseline --no-pmc > $OUT/prof_$1.log 2>&1
+  env KBA_GROUPS=1 ${2:+LIMO_HIP_LIB=$2} timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$1 -o bench -- python bench.py ${TABLE_ARGS:---steps 5 --warmup 2} --full --no-extras --no-cpu-baseline --no-pmc > $OUT/prof_$1.log 2>&1
   python scripts/prof_summary.py $OUT/prof_$1/bench_results.db > $OUT/rocprof_kernel_stats_bench_one_group$3.txt
   rm -rf $OUT/prof_$1
 }
