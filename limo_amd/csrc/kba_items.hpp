@@ -11,9 +11,6 @@
 #include "kba_lm.hpp"
 #include "kba_math.hpp"
 
-#ifndef KBA_SLAB_ENTRIES
-#define KBA_SLAB_ENTRIES 4
-#endif
 #ifndef KBA_SYNC
 #define KBA_SYNC() ((void)0)
 #endif
@@ -1283,7 +1280,6 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     }
     KBA_SYNC();
     KBA_TICK(1);
-    if (c.pad == 41) return;  // (41-44: profiling aids, early exits after the phases)
     // (2) ground-plane rows: F^T F on the 10x10 block of their keyframe: one lane per (keyframe, entry) adds the staged
     //     rows of ITS keyframe in row order.
     if (bv.gp_red) {
@@ -1361,7 +1357,6 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         KBA_SYNC();
     }
     KBA_TICK(2);
-    if (c.pad == 42) return;
     // (3) regulariser rows: one lane evaluates one row into scratch and spreads it over the columns of its (at most
     //     two, neighbouring) keyframes ...
     const int nrows = reg_row_count(wd);
@@ -1404,7 +1399,6 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     }
     KBA_SYNC();
     KBA_TICK(3);
-    if (c.pad == 45) return;
     // ... then every entry of the block tridiagonal of H (diagonal blocks, then the blocks (k, k+1) and their mirror
     //     images) is owned by one lane, which adds the rows' products in row order: no serial pass over the rows,
     //     same sum per entry for any lane count.
@@ -1432,7 +1426,6 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     }
     KBA_SYNC();
     KBA_TICK(4);
-    if (c.pad == 43) return;
     // (4) mask constant / absent slots
     const uint8_t* cm = bv.cmask + (int64_t)wd.cam0;
     for (int i = tid; i < nc * nc; i += nt) {
@@ -1448,7 +1441,6 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
             bv.scale_c[wd.cam0 + i] = (cm[i] && c.jacobi_scaling) ? 1.0 / (1.0 + sqrt(H[i * nc + i])) : 1.0;
     }
     KBA_TICK(5);
-    if (c.pad == 44) return;
     // (5) reductions
     double cost = 0.0, failf = 0.0, gmax = 0.0, xn2 = 0.0, reg_free = 0.0, reg_fixed = 0.0;
     for (int i = tid; i < wd.n_lblk * wd.n_view; i += nt) cost += bv.lv_part[wd.lvpart_off + (int64_t)i * kLinPartial];
@@ -1544,7 +1536,7 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     // in the (q mod 4) order and the sums keep their bits (a skipped term is an exact zero).  Round 5: this sum is what bounds
     // k_cam_solve in a batch (137 KB of slab entries per window and iteration at C2; 86 KB with the skip).
     const int q_gp = c.schur_nslab > 0 ? 0 : (schur_plain_slabs(wd, c.schur_span) & ~3);
-    constexpr int kE = KBA_SLAB_ENTRIES;  // entries a lane sums at once
+    constexpr int kE = 4;  // entries a lane sums at once
     for (int i0 = tid; i0 < n_need; i0 += kE * nt) {
         double s[kE], acc[kE][4];
         int64_t off[kE];
@@ -1597,7 +1589,6 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     }
     KBA_SYNC();
     KBA_TICK(9);
-    if (c.pad == 1) return;
     // ---- right-looking Cholesky of the upper triangle fused with the forward substitution (rhs = extra column):
     //      A = U^T U, y = U^-T rhs.  One barrier per pivot; the rows are divided by sqrt(d_k) in one pass at the end.
     //      Eigen LLT<Upper> semantics: failure when a pivot is <= 0.
@@ -1745,7 +1736,6 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     }
     KBA_SYNC();
     KBA_TICK(10);
-    if (c.pad == 2) return;
     // ---- backward substitution U x = y (y = column nf), column oriented
 #if defined(__HIP_DEVICE_COMPILE__)
     if (nt >= 64 && nf <= 64) {
@@ -1779,7 +1769,6 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     }
     KBA_SYNC();
     KBA_TICK(11);
-    if (c.pad == 3) return;
     for (int a = tid; a < nc; a += nt) {
         const int ca = cs[a];
         const double yv = ca >= 0 ? y[ca] : 0.0;

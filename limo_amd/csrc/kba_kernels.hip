@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kSchedThreads) void k_sched_scan(BatchView bv, int 
     }
 }
 
-__global__ __launch_bounds__(256) void k_sched_fill(BatchView bv, SolveConsts c, int view_consts_here) {
+__global__ __launch_bounds__(256) void k_sched_fill(BatchView bv, SolveConsts c) {
     const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= bv.n_slots) return;
     const int32_t* off = bv.slot_cnt + (int64_t)s * (SL_COUNT + 1);
@@ -349,24 +349,15 @@ __global__ __launch_bounds__(256) void k_sched_fill(BatchView bv, SolveConsts c,
     if (lane == 0) L(SL_WIN)[0] = w;
     // the per-view constants of a window that is linearised this round (the former k_view_consts launch: the wave is here anyway)
     const WinState& st = bv.st[w];
-    if (view_consts_here && st.active && st.need_lin && lane < wd.n_view) view_consts_item(bv, wd.view0 + lane);
+    if (st.active && st.need_lin && lane < wd.n_view) view_consts_item(bv, wd.view0 + lane);
 }
 
 // ------------------------------------------------------------------------------------------ observations
-// per-view constants of the current poses (kba_items.hpp:view_consts_item), one lane per view
-// (streaming solve: one 64-lane workgroup per listed window, lanes over its <= kMaxViews views)
+// per-view constants of the current poses (kba_items.hpp:view_consts_item), one lane per view (lock-step solve; the streaming
+// solve forms them in k_sched_fill)
 __global__ void k_view_consts(BatchView bv) {
-    int v;
-    if (bv.counted) {
-        const int32_t* wl = bv.sched_lists + bv.sched_off[SL_WIN] + 1;
-        if ((int)blockIdx.x >= wl[-1]) return;
-        const WinDesc& wd = bv.win[wl[blockIdx.x]];
-        if ((int)threadIdx.x >= wd.n_view) return;
-        v = wd.view0 + threadIdx.x;
-    } else {
-        v = blockIdx.x * blockDim.x + threadIdx.x;
-        if (v >= bv.TV) return;
-    }
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= bv.TV) return;
     const WinState& st = bv.st[bv.view_win[v]];
     if (!st.active || !st.need_lin) return;
     view_consts_item(bv, v);
@@ -377,7 +368,7 @@ __global__ void k_view_consts(BatchView bv) {
 // (kba_items.hpp:lin_lm_lane has the plain statements).  Lane = landmark, loop over the window's views:
 //   * the view's 37 constants (kba_items.hpp:view_consts_item) are wave-uniform: the workgroup copies its window's constants
 //     into LDS once and reads them from there (VLDS, the default since round 5); the other variant reads view_lin through the
-//     constant address space (written by k_view_consts, the launch before: scalar loads although plane stores precede them);
+//     constant address space (written by k_sched_fill or k_view_consts, the launch before: scalar loads although plane stores precede them);
 //   * the observation of the pair (slot table -> index s -> u, v, d: 12 B) is fetched one view ahead, the slot two ahead;
 //   * branch-free: a landmark that does not see the view (or is out of the problem) runs the same arithmetic on a valid
 //     dummy observation, contributes zeros and stores into the dump area behind the planes;
@@ -387,29 +378,18 @@ __global__ void k_view_consts(BatchView bv) {
 // 79 B per observation under counters (round 5); the separate view-major linearise + landmark-major accumulate pair of round 1
 // moved 101 + 93.
 typedef const double __attribute__((address_space(4))) cdouble;
-constexpr int kLinAccl = 13;  // doubles per lane that the ACCL variants of k_lin_lm park in LDS: V 6 | g 3 | Jacobi scale 3 | ground-plane row
+constexpr int kLinAccl = 13;  // doubles per lane that lin_lm_block parks in LDS: V 6 | g 3 | Jacobi scale 3 | ground-plane row
 // (the body of k_lin_lm for landmark workgroup b; k_solve_wg runs it for the workgroups of its window one after the other)
-// KVIEW: the view constants are read through the constant address space (scalar loads) - only valid when they were
-// written by an EARLIER launch (k_view_consts); k_solve_wg writes them in the same launch and reads them as plain memory.
-template <bool KVIEW>
-struct ViewPtr {
-    typedef cdouble* type;
-};
-template <>
-struct ViewPtr<false> {
-    typedef const double* type;
-};
-// ACCL: the landmark block's nine running sums (V 6 | g 3) live in LDS ([9][kBlock] doubles in front of the view slices, one
-// column per lane: conflict-free) instead of registers - read, three rows added, written back once per view.  18 registers
-// less across the view loop: what the 128-register build (four waves per SIMD) spilled; the sums and their order are the same.
-// VLDS: the window's view constants are copied into LDS once per workgroup ([view][kLinVlds], behind the ACCL region) and read from
+// The landmark block's nine running sums (V 6 | g 3) live in LDS ([9][kBlock] doubles in front of the view slices, one column
+// per lane: conflict-free) instead of registers - read, three rows added, written back once per view.  18 registers less across
+// the view loop: what the 128-register build (four waves per SIMD) spilled; the sums and their order are the same.
+// VLDS: the window's view constants are copied into LDS once per workgroup ([view][kLinVlds], behind the sums) and read from
 // there (ds_read, broadcast) instead of through scalar loads: LDS reads return in order and are waited for one by one, scalar loads
-// return out of order - every use of one waits for ALL of them (s_waitcnt lgkmcnt(0)), ten times per pair.
-#ifndef KBA_COOP_VLDS
-#define KBA_COOP_VLDS 1  // the one-launch kernels (k_solve_wg, k_solve_coop) linearise through LDS as well (0: A/B builds)
-#endif
+// return out of order - every use of one waits for ALL of them (s_waitcnt lgkmcnt(0)), ten times per pair.  The one-launch kernels
+// (k_solve_wg, k_solve_coop) write the constants in the same launch and always take the LDS copy; !VLDS reads them through the
+// constant address space, which is only valid when an EARLIER launch wrote them (k_sched_fill, k_view_consts).
 constexpr int kLinVlds = 38;  // doubles of a view's constants the linearisation reads (view_consts_item: 37)
-template <bool KVIEW, bool ACCL = false, bool VLDS = false>
+template <bool VLDS>
 __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveConsts& c, int b) {
     const int w = bv.lblk_win[b];
     const WinState& st = bv.st[w];
@@ -442,11 +422,11 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     lin_lm_tail_fetch(bv, w, gl, tail);
     const int32_t* slot = bv.lm_slot + gl;
     double* out = bv.lv_part + wd.lvpart_off + (int64_t)(b - wd.lblk0) * n_view * kLinPartial;
-    extern __shared__ __attribute__((aligned(16))) double lin_lds[];  // ACCL: [kLinAccl][kBlock] sums, tail inputs | VLDS: [view][kLinVlds] | [view][wave][kLinPartial]
-    double* const vlds = lin_lds + (ACCL ? kLinAccl * kBlock : 0);
+    extern __shared__ __attribute__((aligned(16))) double lin_lds[];  // [kLinAccl][kBlock] sums, tail inputs | VLDS: [view][kLinVlds] | [view][wave][kLinPartial]
+    double* const vlds = lin_lds + kLinAccl * kBlock;
     double* const lv_lds = vlds + (VLDS ? n_view * kLinVlds : 0);
     double* const accl = lin_lds + threadIdx.x;
-    typedef typename std::conditional<VLDS, const double*, typename ViewPtr<KVIEW>::type>::type VT;
+    typedef typename std::conditional<VLDS, const double*, cdouble*>::type VT;
     constexpr int kVStride = VLDS ? kLinVlds : kViewLin;
     VT vc;
     if constexpr (VLDS) {
@@ -458,35 +438,24 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         vc = (VT)(bv.view_lin + (int64_t)kViewLin * wd.view0);
     }
     const int64_t dump = bv.SO - kObsBlock + threadIdx.x;
-    LmAcc acc;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) acc.V[i] = 0.0;
+    for (int i = 0; i < 9; ++i) accl[i * kBlock] = 0.0;
+    // the tail's per-landmark inputs wait in LDS as well (fetched up here, in front of the loop's stores: LmTailIn)
 #pragma unroll
-    for (int i = 0; i < 3; ++i) acc.g[i] = 0.0;
-    if constexpr (ACCL) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) accl[i * kBlock] = 0.0;
-        // the tail's per-landmark inputs wait in LDS as well (fetched up here, in front of the loop's stores: LmTailIn)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) accl[(9 + i) * kBlock] = tail.sc[i];
-        accl[12 * kBlock] = __hiloint2double(tail.gg, 0);
-    }
+    for (int i = 0; i < 3; ++i) accl[(9 + i) * kBlock] = tail.sc[i];
+    accl[12 * kBlock] = __hiloint2double(tail.gg, 0);
     // (a lane only ever touches its own column of the sums: no barrier between these accesses)
     auto accum = [&](auto vl, const double* r3, const double* c4) {
-        if constexpr (ACCL) {
-            LmAcc a;
+        LmAcc a;
 #pragma unroll
-            for (int i = 0; i < 6; ++i) a.V[i] = accl[i * kBlock];
+        for (int i = 0; i < 6; ++i) a.V[i] = accl[i * kBlock];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) a.g[i] = accl[(6 + i) * kBlock];
-            lin_lm_accum(vl, r3, c4, a);
+        for (int i = 0; i < 3; ++i) a.g[i] = accl[(6 + i) * kBlock];
+        lin_lm_accum(vl, r3, c4, a);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) accl[i * kBlock] = a.V[i];
+        for (int i = 0; i < 6; ++i) accl[i * kBlock] = a.V[i];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) accl[(6 + i) * kBlock] = a.g[i];
-        } else {
-            lin_lm_accum(vl, r3, c4, acc);
-        }
+        for (int i = 0; i < 3; ++i) accl[(6 + i) * kBlock] = a.g[i];
     };
     int fail = 0;
     // pipeline: slot of view j + 2, measurement of view j + 1 in flight while view j computes
@@ -579,15 +548,14 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
             if (rs14_idx >= 0) lv_lds[(j * kLinWaves + wave) * kLinPartial + 14 + rs14_idx] = tot;
         }
     }
-    if constexpr (ACCL) {
+    LmAcc acc;
 #pragma unroll
-        for (int i = 0; i < 6; ++i) acc.V[i] = accl[i * kBlock];
+    for (int i = 0; i < 6; ++i) acc.V[i] = accl[i * kBlock];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) acc.g[i] = accl[(6 + i) * kBlock];
+    for (int i = 0; i < 3; ++i) acc.g[i] = accl[(6 + i) * kBlock];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) tail.sc[i] = accl[(9 + i) * kBlock];
-        tail.gg = __double2hiint(accl[12 * kBlock]);
-    }
+    for (int i = 0; i < 3; ++i) tail.sc[i] = accl[(9 + i) * kBlock];
+    tail.gg = __double2hiint(accl[12 * kBlock]);
     double part[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // the landmark's ground-plane row (B3) is linearised by its own lane right here, before lin_lm_finish adds it to the
     // landmark block (a separate k_gp launch per linearisation did this before: one launch per iteration less)
@@ -613,24 +581,18 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         bv.lblk_linfail[b] = any_fail ? 1.0 : 0.0;
     }
 }
-// k_lin_lm<WAVES, VLDS>: <4, true> is the default (128 registers: view constants, landmark sums and tail inputs in LDS, 33 KB per
-// workgroup at five views); <3, true> the same at three waves per SIMD (KBA_LIN_WAVES=3); <., false> reads the view constants through
-// scalar loads (windows with so many views that the LDS copy would cost occupancy; <3, false> keeps the sums in registers).  Same
-// statements, same order, same bits in all of them.
-template <int WAVES, bool VLDS>
-#ifdef KBA_NOATTR_LIN
-__global__ __launch_bounds__(kBlock) void k_lin_lm(
-#else
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_lin_lm(
-#endif
-    BatchView bv, SolveConsts c, const int32_t* wl) {
+// k_lin_lm<VLDS>: four waves per SIMD (128 registers: landmark sums and tail inputs in LDS, and with VLDS the view constants: 33 KB
+// per workgroup at five views); <false> reads the view constants through scalar loads (windows with so many views that the LDS
+// copy would cost occupancy).  Same statements, same order, same bits in both.
+template <bool VLDS>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_lin_lm(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int b = wl_at(bv, wl, blockIdx.x);
     if (b < 0) return;
-    lin_lm_block<true, WAVES >= 4 || VLDS, VLDS>(bv, c, b);
+    lin_lm_block<VLDS>(bv, c, b);
 }
-// accl: the launch keeps its landmark sums in LDS (k_lin_lm<4, .>, k_lin_lm<., true>); vlds: ... and a copy of the view constants
-__host__ __device__ inline int lin_lm_lds_bytes(int n_view_max, bool accl = false, bool vlds = false) {
-    return (n_view_max * (kLinWaves * kLinPartial + (vlds ? kLinVlds : 0)) + (accl || vlds ? kLinAccl * kBlock : 0)) * (int)sizeof(double);
+// vlds: the launch keeps a copy of the view constants in LDS as well
+__host__ __device__ inline int lin_lm_lds_bytes(int n_view_max, bool vlds) {
+    return (n_view_max * (kLinWaves * kLinPartial + (vlds ? kLinVlds : 0)) + kLinAccl * kBlock) * (int)sizeof(double);
 }
 
 // ------------------------------------------------------------------------------------------ landmarks
@@ -1196,12 +1158,9 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         }
     }
 }
+// (without the occupancy attribute the two variants of a round take 180 / 276 registers: +16 % / +46 %, profiles/r05_experiment_schur_ablations.txt)
 template <int TM, bool GP, int WAVES>
-#ifdef KBA_NOATTR_SCHUR
-__global__ __launch_bounds__(64) void k_schur_lean(
-#else
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_schur_lean(
-#endif
     BatchView bv, const int32_t* wl, int span, int span_gp) {
     const int sb = wl_at(bv, wl, blockIdx.x);
     if (sb < 0) return;
@@ -1227,20 +1186,8 @@ __global__ __launch_bounds__(64) void k_schur_lean_pair(BatchView bv, const int3
 }
 
 // ------------------------------------------------------------------------------------------ camera system
-// (three waves per SIMD = three windows per CU: 168 registers; the ground-plane Gram tile of round 5 took the allocation to 172)
-#ifndef KBA_CAM_ASM_WAVES
-#define KBA_CAM_ASM_WAVES 3  // (0: no attribute - 172 registers, two waves per SIMD)
-#endif
-#ifndef KBA_CAM_SOLVE_WAVES
-#define KBA_CAM_SOLVE_WAVES 0  // 0: no occupancy attribute on k_cam_solve (128 registers).  With amdgpu_waves_per_eu(3, 3) - or (4, 4) - the
-                               // compiler's schedule is 27 % slower (287 vs 226 us per round, profiles/r05_experiment_cam_solve_occupancy.txt)
-#endif
-#if KBA_CAM_ASM_WAVES > 0
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KBA_CAM_ASM_WAVES, KBA_CAM_ASM_WAVES))) void k_cam_assemble(
-#else
-__global__ __launch_bounds__(kBlock) void k_cam_assemble(
-#endif
-    BatchView bv, SolveConsts c, const int32_t* wl) {
+// (three waves per SIMD = three windows per CU; without the attribute 172 registers, two waves; four spill: profiles/r06_experiment_launch_train.txt)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_cam_assemble(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int w = wl_at(bv, wl, blockIdx.x);
     if (w < 0) return;
     WinState& st = bv.st[w];
@@ -1281,12 +1228,8 @@ __global__ __launch_bounds__(kBlock) void k_cam_assemble(
     }
 }
 
-#if KBA_CAM_SOLVE_WAVES > 0
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KBA_CAM_SOLVE_WAVES, KBA_CAM_SOLVE_WAVES))) void k_cam_solve(
-#else
-__global__ __launch_bounds__(kBlock) void k_cam_solve(
-#endif
-    BatchView bv, SolveConsts c, const int32_t* wl) {
+// (no occupancy attribute: with one the compiler's schedule is 27 % slower, profiles/r05_experiment_cam_solve_occupancy.txt)
+__global__ __launch_bounds__(kBlock) void k_cam_solve(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int w = wl_at(bv, wl, blockIdx.x);
     if (w < 0) return;
     if (!bv.st[w].active) return;
@@ -1316,8 +1259,8 @@ __global__ __launch_bounds__(64) void k_step_decide(BatchView bv, SolveConsts c,
     __syncthreads();
     if (threadIdx.x == 0) lm_decide_step(bv.st[w], bv.red[w], c);
     if (!bv.counted) return;
-    // streaming solve: the accepted keyframe parameters move here, per window (k_accept works per landmark workgroup and
-    // a window WITHOUT landmark workgroups - every landmark filtered out, regularisers only - would never get them)
+    // streaming solve: the accepted keyframe parameters move here, per window (a pass per landmark workgroup would never reach
+    // a window WITHOUT landmark workgroups - every landmark filtered out, regularisers only)
     __syncthreads();
     const WinDesc& wd = bv.win[w];
     if (bv.st[w].accept && (int)threadIdx.x < wd.n_kf) {
@@ -1328,20 +1271,9 @@ __global__ __launch_bounds__(64) void k_step_decide(BatchView bv, SolveConsts c,
     }
 }
 
-// candidate -> current for accepted windows (keyframe part: first TK threads, landmark part: the rest)
-// (streaming solve: one workgroup per listed landmark workgroup; the keyframes moved in k_step_decide)
+// candidate -> current for accepted windows (keyframe part: first TK threads, landmark part: the rest; lock-step solve - the
+// streaming solve moves the keyframes in k_step_decide and the landmarks in its relinearisation, lin_lm_block)
 __global__ void k_accept(BatchView bv) {
-    if (bv.counted) {
-        const int32_t* wl = bv.sched_lists + bv.sched_off[SL_LBLK] + 1;
-        if ((int)blockIdx.x >= wl[-1]) return;
-        const int b = wl[blockIdx.x], w = bv.lblk_win[b];
-        if (!bv.st[w].accept) return;
-        if ((int)threadIdx.x < bv.lblk_n[b]) {
-            const int64_t l = bv.lblk_lm0[b] + threadIdx.x;
-            for (int q = 0; q < 3; ++q) bv.lm[3 * l + q] = bv.lm_c[3 * l + q];
-        }
-        return;
-    }
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < bv.TK) {
         if (!bv.st[bv.kf_win[i]].accept) return;
@@ -1589,7 +1521,7 @@ __global__ __launch_bounds__(kBlock) void k_trim_select(BatchView bv, SolveConst
 // few microseconds of work and six barriers.  Same arithmetic, same summation orders as the launches it replaces:
 // the results are bit-identical (tests/test_gpu_parity.py compares the two paths).
 //   * the view constants are written and read in the same launch: the workgroup copies them into LDS with plain loads
-//     (lin_lm_block<false, true, true>), not through the scalar cache;
+//     (lin_lm_block<true>), not through the scalar cache;
 //   * the step reduction of k_step_decide is a 64-lane sum: reduce_step(.., n_work = 64) forms exactly that one;
 //   * cap_ticks > 0: wall-clock cap of each solve in ticks of the 100 MHz constant clock (Solver::Options::
 //     max_solver_time_in_seconds as run_schedule applies it: checked once per iteration after the linearisation).
@@ -1641,7 +1573,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c
                 __syncthreads();
                 KBA_WTICK(1);
                 for (int b = lb0; b < lb1; ++b) {
-                    lin_lm_block<false, KBA_COOP_VLDS != 0, KBA_COOP_VLDS != 0>(bv, c, b);  // (view constants, sums and tail inputs in LDS: lin_lm_lds_bytes(., true, true))
+                    lin_lm_block<true>(bv, c, b);  // (view constants, sums and tail inputs in LDS: lin_lm_lds_bytes(., true))
                     __syncthreads();
                 }
                 KBA_WTICK(2);
@@ -1911,7 +1843,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
                 const bool scale_first = st.compute_scale != 0 || G == 1;
                 // ---- k_lin_lm
                 for (int b = lb0 + g; b < lb1; b += G) {
-                    lin_lm_block<false, KBA_COOP_VLDS != 0, KBA_COOP_VLDS != 0>(bv, c, b);  // (view constants, sums and tail inputs in LDS: lin_lm_lds_bytes(., true, true))
+                    lin_lm_block<true>(bv, c, b);  // (view constants, sums and tail inputs in LDS: lin_lm_lds_bytes(., true))
                     __syncthreads();
                 }
                 KBA_CTICK(0);
@@ -2117,25 +2049,12 @@ __global__ void k_lm_owned(BatchView bv, double* out, int rank, int n_shards, in
 //   * everything LOADED is consumed before the first store is issued (one counter for loads and stores on gfx950: a load waited
 //     for behind a store waits for the store's acknowledge);
 //   * the cost leaves the kernel as ONE double per wave (chunk_cost, fixed summation order), the validity flags as bytes.
-#ifndef KBA_EVAL_NT
-#define KBA_EVAL_NT 0  // 1: non-temporal stores for the planes (A/B builds)
-#endif
-__device__ __forceinline__ void store_plane(double* p, double v) {
-#if KBA_EVAL_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
 // per-view constants of EVERY view of the batch at the current poses (evaluate-only batches have no LM state to ask)
 __global__ void k_view_consts_all(BatchView bv) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v < bv.TV) view_consts_item(bv, v);
 }
 __host__ __device__ inline int evaluate_grid(int n_echunk) { return 8 * ((n_echunk + 8 * (kBlock / 64) - 1) / (8 * (kBlock / 64))); }
-#ifndef KBA_EVAL_STAGE
-#define KBA_EVAL_STAGE 1  // 1: the depth rows of a workgroup leave through LDS as whole 128-byte lines; 0: every lane stores its own (A/B builds)
-#endif
 __global__ __launch_bounds__(kBlock) void k_evaluate(BatchView bv, SolveConsts c, int apply_loss, double* chunk_cost, uint8_t* obs_valid) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // workgroup -> run of four chunks: XCD x (= blockIdx % 8, observed placement) takes the x-th eighth of the chunks
@@ -2143,16 +2062,12 @@ __global__ __launch_bounds__(kBlock) void k_evaluate(BatchView bv, SolveConsts c
     const int wg = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     const int ci = __builtin_amdgcn_readfirstlane(wg * (kBlock / 64) + wave);  // (wave-uniform: scalar loads below)
     const bool have = ci < bv.n_echunk;
-#if KBA_EVAL_STAGE
     // The depth rows of the workgroup's (up to) 256 observations have consecutive ranks [R0, R1) - the chunks are consecutive and
     // ranks follow the packed order - so they are collected in LDS and written as whole lines: a lane per plane entry, 64 consecutive
     // entries per wave from a multiple of 16 on.  (Each lane storing its own row at its rank: a run of ~29 x 8 B at any alignment per
     // instruction = three partial-line writes, 1.65x the requests per byte; profiles/r06_experiment_evaluate_store_path.txt.)
     __shared__ double stage[10][kBlock];
     __shared__ int wave_end[kBlock / 64];
-#else
-    if (!have) return;
-#endif
     const EvalChunk ch = bv.echunk[have ? ci : 0];
     cdouble* vl = (cdouble*)(bv.view_lin + (int64_t)kViewLin * ch.view);
     const int64_t o = (int64_t)ch.base + lane;
@@ -2173,14 +2088,13 @@ __global__ __launch_bounds__(kBlock) void k_evaluate(BatchView bv, SolveConsts c
     eval_obs_rows(vl, p, h, Jp, Jl);
     if (in) {
 #pragma unroll
-        for (int k = 0; k < 2; ++k) store_plane(bv.obs_r + k * SO + o, h.r[k]);
+        for (int k = 0; k < 2; ++k) bv.obs_r[k * SO + o] = h.r[k];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) store_plane(bv.obs_Jp + k * SO + o, Jp[k]);
+        for (int k = 0; k < 12; ++k) bv.obs_Jp[k * SO + o] = Jp[k];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) store_plane(bv.obs_Jl + k * SO + o, Jl[k]);
+        for (int k = 0; k < 6; ++k) bv.obs_Jl[k * SO + o] = Jl[k];
         obs_valid[o] = h.ok ? 1 : 0;
     }
-#if KBA_EVAL_STAGE
     const int R0 = bv.echunk[min(wg * (kBlock / 64), bv.n_echunk - 1)].dep0;  // first rank of the workgroup (its first chunk exists whenever one does)
     if (dep) {
         const int lr = rank - R0;  // < kBlock: at most one depth row per observation of the workgroup
@@ -2196,22 +2110,13 @@ __global__ __launch_bounds__(kBlock) void k_evaluate(BatchView bv, SolveConsts c
     for (int e = (R0 & ~15) + (int)threadIdx.x; e < R1; e += kBlock) {
         if (e < R0) continue;
         const int lr = e - R0;
-        store_plane(bv.obs_r + 2 * SO + e, stage[0][lr]);
+        bv.obs_r[2 * SO + e] = stage[0][lr];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) store_plane(bv.obs_Jp + 12 * SO + k * SD + e, stage[1 + k][lr]);
+        for (int k = 0; k < 6; ++k) bv.obs_Jp[12 * SO + k * SD + e] = stage[1 + k][lr];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) store_plane(bv.obs_Jl + 6 * SO + k * SD + e, stage[7 + k][lr]);
+        for (int k = 0; k < 3; ++k) bv.obs_Jl[6 * SO + k * SD + e] = stage[7 + k][lr];
     }
     if (!have) return;
-#else
-    if (dep) {
-        store_plane(bv.obs_r + 2 * SO + rank, h.r[2]);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) store_plane(bv.obs_Jp + 12 * SO + k * SD + rank, Jp[12 + k]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) store_plane(bv.obs_Jl + 6 * SO + k * SD + rank, Jl[6 + k]);
-    }
-#endif
     const double ws = wave_sum(in ? h.cost : 0.0);  // lanes in a fixed order: deterministic
     if (lane == 0) chunk_cost[ci] = ws;
 }

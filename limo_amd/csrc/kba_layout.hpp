@@ -29,7 +29,7 @@ constexpr int kObsPerLane = 4;    // observations per lane of the view-major ker
                                   // accumulated in registers over them before the one workgroup reduction
 constexpr int kObsBlock = kBlock * kObsPerLane;  // observations per linearize / cost workgroup
 constexpr int kSchurLm = 16;      // landmarks per Schur LDS tile (48 rows = 12 MFMA k-steps)
-constexpr int kSchurLmPerBlock = 64;   // landmarks per Schur block; a wave takes SolveConsts::schur_span (1, 2 or 4)
+constexpr int kSchurLmPerBlock = 64;   // landmarks per Schur block; a wave takes SolveConsts::schur_span (2; 1 when landmark-sharded)
                                        // consecutive blocks of a window and writes one partial slab
 constexpr int kMaxRegRows = 1 + (kMaxKf - 1) * 5 + 3 * kMaxKf;  // scale + per pair (3+1+1) + global normal 3/kf
 
@@ -139,7 +139,7 @@ struct SolveConsts {  // subset of limo_ba_options the kernels need
     int32_t max_invalid, jacobi_scaling;
     double depth_quantile, reprojection_quantile;
     int32_t min_groups, pad;
-    int32_t schur_span;   // plain Schur blocks per wave in this iteration (kba_items.hpp:schur_slab_of)
+    int32_t schur_span;   // plain Schur blocks per wave (kba_items.hpp:schur_slab_of)
     int32_t schur_span_gp;  // ground-plane Schur blocks per wave
     int32_t num_trim_rounds, trim_iters, max_iters;  // the schedule, for the device-side scheduler
     int32_t schur_nslab;  // > 0: k_cam_solve sums this many slabs from S_red instead of the window's partial slabs

@@ -206,7 +206,6 @@ SolveConsts make_consts(const limo_ba_options& o) {
     c.num_trim_rounds = o.num_trim_rounds;
     c.trim_iters = o.trim_solver_iterations;
     c.max_iters = o.max_num_iterations;
-    if (const char* e = std::getenv("KBA_DEBUG_STAGE")) c.pad = std::atoi(e);  // profiling aid only
     return c;
 }
 
@@ -239,8 +238,7 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
             for (int w = 0; w < n; ++w) f(w);
             return;
         }
-        static const bool use_pool = !(std::getenv("KBA_PACK_POOL") && std::atoi(std::getenv("KBA_PACK_POOL")) == 0);
-        if (use_pool && pack_pool().run(nt, n, std::function<void(int)>(f))) return;
+        if (pack_pool().run(nt, n, std::function<void(int)>(f))) return;
         std::atomic<int> next{0};
         std::vector<std::thread> pool;
         for (unsigned t = 0; t < nt; ++t)

@@ -96,16 +96,12 @@ struct limo_ctx {
         }
         return false;
     }
-    size_t pooled_large_cap() const {  // KBA_POOL_LARGE_MB: cap of the idle large blocks of a context (default 16 GB; 0 keeps none)
-        static const size_t cap = std::getenv("KBA_POOL_LARGE_MB") ? (size_t)std::strtoull(std::getenv("KBA_POOL_LARGE_MB"), nullptr, 10) << 20 : kPoolLargeBytes;
-        return cap;
-    }
     void pool_free(void* p, size_t bytes) {
         const size_t c = size_class(bytes);
         auto& v = pool[c];
         static const bool no_reuse = std::getenv("KBA_NO_POOL") != nullptr;
         const bool large = bytes > kPoolMaxBlock;
-        if (!no_reuse && (large ? (v.empty() && pooled_large + c <= pooled_large_cap()) : (int)v.size() < kPoolPerClass)) {
+        if (!no_reuse && (large ? (v.empty() && pooled_large + c <= kPoolLargeBytes) : (int)v.size() < kPoolPerClass)) {
             v.push_back(p);
             if (large) pooled_large += c;
         } else {

@@ -9,7 +9,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -67,11 +66,10 @@ struct limo_ba_batch : Executor {
     // active set has halved, so late LM iterations only launch the workgroups that have work
     int32_t *d_wl_blk = nullptr, *d_wl_lblk = nullptr, *d_wl_sblk = nullptr, *d_wl_win = nullptr, *d_flags = nullptr;
     int32_t* d_wl_sblk_part = nullptr;                          // Schur worklist of a re-batched active set
-    struct FullSblk {  // Schur worklist of every window for one (span, span_gp), built on first use
+    struct FullSblk {  // Schur worklist of every window, built on first use
         int32_t* d = nullptr;
         int n = 0, n_plain = 0, n_fgp = 0;
-    };
-    std::map<std::pair<int, int>, FullSblk> wl_sblk_full;
+    } wl_sblk_full;
     // Schur worklists are ordered [plain groups of fast windows | ground-plane groups of fast windows | generic windows]
     int n_wl_sblk_plain = 0, n_wl_sblk_fgp = 0;
     const void* schur_fn_plain = nullptr;
@@ -423,18 +421,10 @@ struct limo_ba_batch : Executor {
     // which its Schur complement is summed, is then the same alone and inside any batch - single-window and batched
     // solves give the same bits.  (Measured at 1024 C2 windows: span 2 is as fast as 4, span 1 costs 2 %.)
     // The spans also decide which slabs of S_part are "plain" (written in part only, kba_kernels.hip:schur_lean_group) - a slab must keep
-    // its class for the life of the batch, so the A/B environment variables are read ONCE per batch, at its first solve.
-    int span_env = 0, span_gp_env = 0;  // 0: not read yet
-    void set_span(int) {
-        if (span_env == 0) {
-            span_env = 2;
-            span_gp_env = 1;
-            if (const char* e = std::getenv("KBA_SPAN_GP")) span_gp_env = std::max(1, std::atoi(e));
-            if (const char* e = std::getenv("KBA_SPAN")) span_env = std::max(1, std::atoi(e));  // A/B timing aids
-        }
-        c.schur_span = span_env;
-        c.schur_span_gp = span_gp_env;
-        if (shard_P > 1) c.schur_span = c.schur_span_gp = 1;  // Schur blocks are cut at shard boundaries
+    // its class for the life of the batch.
+    void set_span() {
+        c.schur_span = shard_P > 1 ? 1 : 2;  // (Schur blocks are cut at shard boundaries)
+        c.schur_span_gp = 1;
         c.schur_nslab = shard_P > 1 ? shard_P : 0;
         c.schur_packed = shard_P > 1 ? 1 : 0;
     }
@@ -542,8 +532,8 @@ struct limo_ba_batch : Executor {
         n_wl_lblk = P.n_lblk;
         n_wl_win = P.n_win;
         listed = P.n_win;
-        set_span(P.n_win);
-        FullSblk& fl = wl_sblk_full[{c.schur_span, c.schur_span_gp}];
+        set_span();
+        FullSblk& fl = wl_sblk_full;
         if (!fl.d) {
             std::vector<int32_t> v;
             build_sblk_list(nullptr, c.schur_span, c.schur_span_gp, -1, v, fl.n_plain, fl.n_fgp);
@@ -582,7 +572,7 @@ struct limo_ba_batch : Executor {
             for (int i = 0; i < d.n_blk; ++i) wb.push_back(d.blk0 + i);
             for (int i = 0; i < d.n_lblk; ++i) wlb.push_back(d.lblk0 + i);
         }
-        set_span((int)ww.size());
+        set_span();
         build_sblk_list(&ww, c.schur_span, c.schur_span_gp, -1, wsb, n_wl_sblk_plain, n_wl_sblk_fgp);
         auto up = [&](int32_t* dst, const std::vector<int32_t>& v) {
             if (!v.empty()) note(hipMemcpyAsync(dst, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, s), "upload worklist");
@@ -626,27 +616,22 @@ struct limo_ba_batch : Executor {
         listed = n_wl_win;
     }
 
-    // k_lin_lm<4, true> (the default since round 6): four waves per SIMD, the window's view constants, the landmark block's running sums and
-    // the tail's inputs in LDS (kba_kernels.hip:lin_lm_block VLDS / ACCL) - scalar loads of the view constants return out of order, so
-    // every use of one waited for all of them (round 5: 550 -> 513 us per round of 4096 slots through LDS).  With the camera-side sums in
-    // their raw form (kba_items.hpp:lin_cam_half0: the 3 x 6 pose Jacobian is never formed) the kernel needs 129 registers instead of 149,
-    // so the fourth wave costs nothing else: 505 -> 495 us per round, bench line +0.7 % (KBA_LIN_WAVES=3, read once, takes <3, true>).
+    // k_lin_lm<true> (the default since round 6): four waves per SIMD, the window's view constants, the landmark block's running sums and
+    // the tail's inputs in LDS (kba_kernels.hip:lin_lm_block) - scalar loads of the view constants return out of order, so every use of
+    // one waited for all of them (round 5: 550 -> 513 us per round of 4096 slots through LDS).  With the camera-side sums in their raw
+    // form (kba_items.hpp:lin_cam_half0: the 3 x 6 pose Jacobian is never formed) the kernel needs 129 registers instead of 149, so the
+    // fourth wave costs nothing else: 505 -> 495 us per round, bench line +0.7 % against three waves.
     // Batches whose windows have so many views that the copy would cost occupancy (> 48 KB of LDS per workgroup: more than ~16 views)
-    // and KBA_LIN_VLDS=0 (read once) take <., false>: scalar loads, sums in registers - same bits in all variants.
-    // KBA_LIN_LDS_PAD=<bytes>: extra dynamic LDS per workgroup (occupancy experiments).
-    int lin_lds_set[3] = {0, 0, 0};
+    // and KBA_LIN_VLDS=0 (read once; the tests) take <false>: scalar loads - same bits in both variants.
+    int lin_lds_set = 0;  // dynamic LDS k_lin_lm<false> was allowed beyond the default 48 KB (k_lin_lm<true> never needs more)
     void launch_lin_lm(int grid, hipStream_t s, const BatchView& v, const int32_t* wl) {
-        static const int lw = std::getenv("KBA_LIN_WAVES") ? std::atoi(std::getenv("KBA_LIN_WAVES")) : 4;
         static const int want_vlds = std::getenv("KBA_LIN_VLDS") ? std::atoi(std::getenv("KBA_LIN_VLDS")) : 1;
-        static const int pad = std::getenv("KBA_LIN_LDS_PAD") ? std::atoi(std::getenv("KBA_LIN_LDS_PAD")) : 0;
-        const bool four = lw >= 4;
-        const bool vlds = want_vlds != 0 && lin_lm_lds_bytes(P.Vmax, true, true) <= 48 * 1024;
-        const int which = four ? 2 : vlds ? 1 : 0;
-        const void* fn = four ? (vlds ? (const void*)k_lin_lm<4, true> : (const void*)k_lin_lm<4, false>) : vlds ? (const void*)k_lin_lm<3, true> : (const void*)k_lin_lm<3, false>;
-        const int lds = lin_lm_lds_bytes(P.Vmax, four, vlds) + pad;
-        if (lds > 48 * 1024 && lin_lds_set[which] < lds) {  // (beyond the default dynamic-LDS limit: many views, or the padding)
+        const bool vlds = want_vlds != 0 && lin_lm_lds_bytes(P.Vmax, true) <= 48 * 1024;
+        const void* fn = vlds ? (const void*)k_lin_lm<true> : (const void*)k_lin_lm<false>;
+        const int lds = lin_lm_lds_bytes(P.Vmax, vlds);
+        if (lds > 48 * 1024 && lin_lds_set < lds) {  // (beyond the default dynamic-LDS limit: many views)
             note(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute(k_lin_lm)");
-            lin_lds_set[which] = lds;
+            lin_lds_set = lds;
         }
         const BatchView* vp = &v;
         const SolveConsts* cp = &c;
@@ -868,10 +853,6 @@ struct limo_ba_batch : Executor {
     };
     std::vector<StreamGroup> groups;
     int stream_groups_built = 0;
-    // The launch train of a round (round 6): the per-view constants inside k_sched_fill, accepted landmarks + re-damping in ONE launch
-    // (k_after_step) - 12 launches per round instead of 14.  KBA_UNFUSED_TRAIN=1 (read per solve) keeps k_view_consts, k_lm_damp and
-    // k_accept as launches of their own: the same device functions, the same bits (tests/test_gpu_reproducible.py).
-    bool fused_train = true;
     hipEvent_t start_ev = nullptr;
 
     void stream_teardown() {
@@ -887,11 +868,7 @@ struct limo_ba_batch : Executor {
         start_ev = nullptr;
     }
 
-    int stream_slots() const {
-        int n = std::min((int)P.n_win, std::max(1024, std::min(kSchedMaxSlots, (int)P.n_win / 4)));
-        if (const char* e = std::getenv("KBA_SLOTS")) n = std::max(1, std::min({std::atoi(e), (int)P.n_win, kSchedMaxSlots}));
-        return n;
-    }
+    int stream_slots() const { return std::min((int)P.n_win, std::max(1024, std::min(kSchedMaxSlots, (int)P.n_win / 4))); }
     int stream_setup(int n_groups) {
         if (stream_groups_built == n_groups) return LIMO_OK;
         (void)hipStreamSynchronize(ctx->stream);
@@ -899,7 +876,7 @@ struct limo_ba_batch : Executor {
         // windows in flight: a quarter of the batch (so that the ramp-down at the end of the batch is a small part of the
         // solve), at least 1024 (a round of fewer windows is bound by the latency of its window-level kernels)
         n_slots = stream_slots();
-        set_span(P.n_win);
+        set_span();
         int mx[SL_COUNT] = {0};
         for (const WinDesc& d : P.win) {
             const int plg = (d.n_sblk_plain + c.schur_span - 1) / c.schur_span, gpg = (d.n_sblk - d.n_sblk_plain + c.schur_span_gp - 1) / c.schur_span_gp;
@@ -958,7 +935,8 @@ struct limo_ba_batch : Executor {
     }
 
     // One round of one group = scheduler + (side stream) trimming of the windows whose trimming solve just ended + one LM
-    // iteration of every window in the group's slots.
+    // iteration of every window in the group's slots.  The launch train (round 6): the per-view constants inside k_sched_fill,
+    // accepted landmarks + re-damping in ONE launch (k_after_step) - 12 launches per round instead of 14.
     // in_flight_max: an upper bound on the windows this group can have in its slots in this round (the batch's unfinished windows as
     // of the pinned done-counter the host read last).  The list-driven kernels are launched over bound x (entries per window)
     // workgroups instead of the lists' capacities: while the batch drains, a round of 200 windows in 2048 slots no longer
@@ -974,7 +952,7 @@ struct limo_ba_batch : Executor {
         if (round > 0) note(hipStreamWaitEvent(s, g.trim_ev, 0), "wait trim");  // last round's trimming re-armed its windows
         hipLaunchKernelGGL(k_sched_advance, dim3(cdiv(g.n_slots, 256)), dim3(256), 0, s, sv, c);
         hipLaunchKernelGGL(k_sched_scan, dim3(1), dim3(kSchedThreads), 0, s, sv, round);
-        hipLaunchKernelGGL(k_sched_fill, dim3(cdiv(g.n_slots, 4)), dim3(256), 0, s, sv, c, fused_train ? 1 : 0);
+        hipLaunchKernelGGL(k_sched_fill, dim3(cdiv(g.n_slots, 4)), dim3(256), 0, s, sv, c);
         LAUNCH_CHECK("scheduler kernels");
         // ---- trimming of the windows whose trimming solve just ended, on the side stream: k_trim_select is a
         //      latency-bound sort (one workgroup per window, ~0.3 ms) - the other windows iterate meanwhile, the
@@ -986,8 +964,7 @@ struct limo_ba_batch : Executor {
         hipLaunchKernelGGL(k_trim_select, dim3(cap[SL_TWIN]), dim3(kBlock), trim_bytes, g.trim_stream, sv, c);
         LAUNCH_CHECK("trim kernels");
         note(hipEventRecord(g.trim_ev, g.trim_stream), "record trim");
-        // ---- linearisation of the windows that need it (their per-view constants: k_sched_fill above, or the launch of its own)
-        if (!fused_train) hipLaunchKernelGGL(k_view_consts, dim3(cap[SL_WIN]), dim3(64), 0, s, sv);
+        // ---- linearisation of the windows that need it (their per-view constants: k_sched_fill above)
         {
             EventPair* ep = time_kernels ? timed(LIMO_KERNEL_LINEARIZE, s) : nullptr;
             if (cap[SL_LBLK]) launch_lin_lm(cap[SL_LBLK], s, sv, L(SL_LBLK));
@@ -996,13 +973,11 @@ struct limo_ba_batch : Executor {
         hipLaunchKernelGGL(k_cam_assemble, dim3(cap[SL_WIN]), dim3(kBlock), asm_bytes, s, sv, c, L(SL_WIN));
         LAUNCH_CHECK("linearisation kernels");
         // ---- trust-region step of the windows that iterate
-        if (!fused_train && cap[SL_LBLK]) hipLaunchKernelGGL(k_lm_damp, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
         {
             EventPair* ep = time_kernels ? timed(LIMO_KERNEL_SCHUR, s) : nullptr;
             int span = c.schur_span, span_gp = c.schur_span_gp;
             // few windows in flight (the batch drains): both fast-class lists in one launch (kba_kernels.hip:k_schur_lean_pair)
-            static const int pair_bound = std::getenv("KBA_SCHUR_PAIR_BOUND") ? std::atoi(std::getenv("KBA_SCHUR_PAIR_BOUND")) : kSchurPairBound;
-            const bool pair = schur_pair_ok && bound <= pair_bound && cap[SL_SPLAIN] && cap[SL_SFGP];
+            const bool pair = schur_pair_ok && bound <= kSchurPairBound && cap[SL_SPLAIN] && cap[SL_SFGP];
             if (pair) {
                 const int32_t *wlp = L(SL_SPLAIN), *wlg = L(SL_SFGP);
                 int n_plain_cap = cap[SL_SPLAIN];
@@ -1030,12 +1005,8 @@ struct limo_ba_batch : Executor {
         hipLaunchKernelGGL(k_cam_solve, dim3(cap[SL_WIN]), dim3(kBlock), solve_bytes, s, sv, c, L(SL_WIN));
         if (cap[SL_LBLK]) hipLaunchKernelGGL(k_backsub, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
         hipLaunchKernelGGL(k_step_decide, dim3(cap[SL_WIN]), dim3(64), 0, s, sv, c, L(SL_WIN));
-        if (cap[SL_LBLK]) {
-            if (fused_train)  // accepted landmarks / re-damping in one launch (kba_kernels.hip:k_after_step)
-                hipLaunchKernelGGL(k_after_step, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
-            else
-                hipLaunchKernelGGL(k_accept, dim3(cap[SL_LBLK]), dim3(256), 0, s, sv);
-        }
+        if (cap[SL_LBLK])  // accepted landmarks / re-damping in one launch (kba_kernels.hip:k_after_step)
+            hipLaunchKernelGGL(k_after_step, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
         LAUNCH_CHECK("step kernels");
         note(hipEventRecord(g.round_ev[round & 3], s), "record round");
     }
@@ -1052,10 +1023,10 @@ struct limo_ba_batch : Executor {
             if (d.n_lblk > kWgMaxLblk) return false;
         return wg_lds_bytes() <= kCamLdsCapBytes;
     }
-    int wg_lds_bytes() const { return std::max(std::max(asm_bytes, solve_bytes), std::max(trim_bytes, lin_lm_lds_bytes(P.Vmax, true, true))); }
+    int wg_lds_bytes() const { return std::max(std::max(asm_bytes, solve_bytes), std::max(trim_bytes, lin_lm_lds_bytes(P.Vmax, true))); }
     void solve_wg() {
         const int lds = wg_lds_bytes();
-        set_span(P.n_win);
+        set_span();
         note(hipFuncSetAttribute((const void*)k_solve_wg, hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute(k_solve_wg)");
         const long long cap_ticks = opts.max_solver_time_sec > 0.0 ? std::max(1ll, (long long)(opts.max_solver_time_sec * 1e8)) : 0ll;
         hipLaunchKernelGGL(k_solve_wg, dim3(P.n_win), dim3(kBlock), lds, ctx->stream, bv, c, cap_ticks, d_plane_rep, d_plane_dep);
@@ -1075,13 +1046,13 @@ struct limo_ba_batch : Executor {
     int coop_G = 0, coop_xcd = 1;
     int coop_lds_bytes() const {
         const int wave = (std::max(plain_lds_bytes, leangp_lds_bytes) + 15) / 16 * 16;
-        return std::max(std::max(std::max(asm_bytes, solve_bytes), std::max(trim_bytes, lin_lm_lds_bytes(P.Vmax, true, true))), (kBlock / 64) * wave);
+        return std::max(std::max(std::max(asm_bytes, solve_bytes), std::max(trim_bytes, lin_lm_lds_bytes(P.Vmax, true))), (kBlock / 64) * wave);
     }
     bool coop_solve_applies() {
         if (shard_P != 1 || P.evaluate_only || P.n_win < 1) return false;
         if (const char* e = std::getenv("KBA_NO_COOP_SOLVE"))
             if (std::atoi(e) != 0) return false;
-        set_span(P.n_win);
+        set_span();
         int G = 1;
         for (const WinDesc& d : P.win) {
             if (!d.schur_fast || d.cam_scr_off >= 0 || d.nf_pad * d.nf_pad > kCoopRedStride) return false;
@@ -1090,15 +1061,13 @@ struct limo_ba_batch : Executor {
             G = std::max(G, std::max((int)d.n_lblk, tasks ? 1 + (tasks + kBlock / 64 - 1) / (kBlock / 64) : 1));
         }
         G = std::min(G, 32);
-        if (const char* e = std::getenv("KBA_COOP_G")) G = std::max(1, std::min(64, std::atoi(e)));  // (timing aid)
         // one workgroup per CU, all resident: a batch of up to kCoopMaxWin windows shares the chip with fewer workgroups per
         // window (64 windows: 4 each) - still far ahead of ten launches per iteration over 64 slots
         if (P.n_win > kCoopMaxWg || coop_lds_bytes() > kCamLdsCapBytes) return false;
         // the workgroups of a window on one XCD (k_solve_coop): the grid is 8 G ceil(n_win / 8), of which n_win G blocks work
-        coop_xcd = 1;
-        if (const char* e = std::getenv("KBA_COOP_XCD")) coop_xcd = std::atoi(e) != 0;  // (read per call: A/B timing)
+        // (a batch too large for that grid takes the plain mapping)
         const int per8 = ((int)P.n_win + 7) / 8;
-        if (coop_xcd && 8 * per8 > kCoopMaxWg) coop_xcd = 0;
+        coop_xcd = 8 * per8 > kCoopMaxWg ? 0 : 1;
         G = std::max(1, std::min(G, coop_xcd ? kCoopMaxWg / (8 * per8) : kCoopMaxWg / (int)P.n_win));
         coop_G = G;
         return true;
@@ -1134,23 +1103,18 @@ struct limo_ba_batch : Executor {
         cp.plane_dep = d_plane_dep;
         cp.red = d_coop_red;
         void* args[] = {(void*)&bv, (void*)&c, (void*)&cp};
-        // A PLAIN launch by default, with the co-residency of the grid checked here against the occupancy the runtime reports
-        // (the workgroups of other kernels on the device all finish, so every workgroup of this grid gets its CU; a barrier that
-        // waits too long is recovered, coop_sync).  hipLaunchCooperativeKernel gives the same guarantee from the runtime, but
-        // after the first such launch of a process every LATER solve that uses several streams ran 30-50 % slower (a 2048-window
-        // batch 91 -> 118-137 ms, scripts/gpu_groups_sequence.py; with plain launches 91 ms) - KBA_COOP_PLAIN_LAUNCH=0 takes that API.
-        static const bool plain_launch = !(std::getenv("KBA_COOP_PLAIN_LAUNCH") && std::atoi(std::getenv("KBA_COOP_PLAIN_LAUNCH")) == 0);
-        if (plain_launch) {
-            int per_cu = 0, n_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_solve_coop, kBlock, (size_t)lds) != hipSuccess ||
-                hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || per_cu * n_cu < coop_grid) {
-                (void)hipGetLastError();
-                return false;  // (not all workgroups resident at once: the launch sequence)
-            }
+        // A PLAIN launch, with the co-residency of the grid checked here against the occupancy the runtime reports (the workgroups
+        // of other kernels on the device all finish, so every workgroup of this grid gets its CU; a barrier that waits too long is
+        // recovered, coop_sync).  hipLaunchCooperativeKernel gives the same guarantee from the runtime, but after the first such launch
+        // of a process every LATER solve that uses several streams ran 30-50 % slower (a 2048-window batch 91 -> 118-137 ms,
+        // profiles/r04_experiment_coop_api_vs_plain_launch.txt).
+        int per_cu = 0, n_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_solve_coop, kBlock, (size_t)lds) != hipSuccess ||
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || per_cu * n_cu < coop_grid) {
+            (void)hipGetLastError();
+            return false;  // (not all workgroups resident at once: the launch sequence)
         }
-        const hipError_t e = plain_launch ? hipLaunchKernel((const void*)k_solve_coop, dim3(coop_grid), dim3(kBlock), args, lds, ctx->stream)
-                                          : hipLaunchCooperativeKernel((const void*)k_solve_coop, dim3(coop_grid), dim3(kBlock), args, lds, ctx->stream);
-        if (e != hipSuccess) {
+        if (hipLaunchKernel((const void*)k_solve_coop, dim3(coop_grid), dim3(kBlock), args, lds, ctx->stream) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
@@ -1168,11 +1132,10 @@ struct limo_ba_batch : Executor {
         int n_groups = stream_slots() >= 4096 ? 3 : P.n_win >= 512 ? 2 : 1;
         if (const char* e = std::getenv("KBA_GROUPS")) n_groups = std::max(1, std::min(4, std::atoi(e)));
         if (stream_setup(n_groups) != LIMO_OK) return LIMO_ERR_RUNTIME;
-        set_span(P.n_win);
+        set_span();
         hipStream_t s0 = ctx->stream;
         groups[0].stream = s0;
         HIP_TRY(ctx, hipMemsetAsync(d_sched_ctl, 0, sizeof(int32_t) * 8, s0));
-        fused_train = !(std::getenv("KBA_UNFUSED_TRAIN") && std::atoi(std::getenv("KBA_UNFUSED_TRAIN")) != 0);
         for (StreamGroup& g : groups) {
             HIP_TRY(ctx, hipMemsetAsync(g.d_slot_win, 0xFF, sizeof(int32_t) * std::max(1, g.n_slots), s0));
             for (int i = 0; i < 4; ++i) g.h_done[i] = 0;
@@ -1188,9 +1151,8 @@ struct limo_ba_batch : Executor {
         const auto t_solve0 = std::chrono::steady_clock::now();
         bool finished = false;
         int done_seen = 0;  // windows finished, as last read from the pinned ring (monotone, kLag + 1 rounds old when it is used)
-        static const bool shrink = !(std::getenv("KBA_NO_GRID_SHRINK") && std::atoi(std::getenv("KBA_NO_GRID_SHRINK")) != 0);
         for (int round = 0; !finished; ++round) {
-            const int in_flight_max = shrink ? (int)P.n_win - done_seen : (int)P.n_win;
+            const int in_flight_max = (int)P.n_win - done_seen;
             const auto t_enq0 = std::chrono::steady_clock::now();
             for (StreamGroup& g : groups) enqueue_round(g, round, time_kernels, in_flight_max);
             if (sched_trace) enq_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enq0).count();
@@ -1337,12 +1299,10 @@ static int batch_create_impl(limo_ctx* ctx, int32_t n, const limo_ba_window* win
     b->opts = o;
     b->c = make_consts(o);
     const auto t_c0 = std::chrono::steady_clock::now();
-    // Large batches pack into the context's pinned arena when no other live batch holds it (limo_ctx.hpp:pack_arena; KBA_NO_PACK_ARENA=1
-    // keeps the heap).  The first large batch of a context only measures what it would have needed; the arena is made right behind its
-    // packing, for the next one.
-    static const bool arena_off = std::getenv("KBA_NO_PACK_ARENA") && std::atoi(std::getenv("KBA_NO_PACK_ARENA")) != 0;
+    // Large batches pack into the context's pinned arena when no other live batch holds it (limo_ctx.hpp:pack_arena).  The first large
+    // batch of a context only measures what it would have needed; the arena is made right behind its packing, for the next one.
     PackArena lend;
-    const bool lending = !arena_off && n >= 128 && !ctx->pack_arena_busy && hipSetDevice(ctx->device) == hipSuccess;
+    const bool lending = n >= 128 && !ctx->pack_arena_busy && hipSetDevice(ctx->device) == hipSuccess;
     auto arena_resize = [&](size_t wanted) {  // (only while no batch holds the arena)
         const size_t step = size_t(64) << 20;
         const size_t cap = std::min(limo_ctx::kPackArenaMax, (wanted + wanted / 8 + step - 1) / step * step);

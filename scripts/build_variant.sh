@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds a variant of liblimo_hip.so with extra compiler flags into limo_amd/lib/variants/liblimo_hip_<TAG>.so (selected at run time
-# with LIMO_HIP_LIB=...; travels to the GPU box with the snapshot).   usage: scripts/build_variant.sh TAG "-DKBA_CAM_SOLVE_WAVES=4 ..."
+# with LIMO_HIP_LIB=...; travels to the GPU box with the snapshot).   usage: scripts/build_variant.sh TAG "-DKBA_PROFILE_TICKS ..."
 set -e
 cd "$(dirname "$0")/.."
 tag=$1; flags=$2

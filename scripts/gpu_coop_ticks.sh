@@ -15,7 +15,6 @@ PY
 if [ -z "$SKIP_COOP_TICKS" ]; then
 LIMO_HIPCC_EXTRA="-DKBA_COOP_TICKS" python -c "import __graft_entry__ as g; g.build_hip(force=True)" 2>&1 | grep -i error
 timeout 120 python /tmp/one.py 2>&1 | tail -4
-for g in ${GS:-}; do echo "== G=$g"; KBA_COOP_G=$g timeout 120 python /tmp/one.py 2>&1 | tail -4; done
 fi
 LIMO_HIPCC_EXTRA="-DKBA_PROFILE_TICKS" python -c "import __graft_entry__ as g; g.build_hip(force=True)" 2>&1 | grep -i error
 echo "== one launch"; timeout 120 python /tmp/one.py 2>&1 | grep "ticks" | tail -4

@@ -24,4 +24,4 @@ st = b.kernel_stats()
 # every solve launches k_linearize twice here (the second launch finds nothing to linearise and exits at once):
 # time per solve = the full-batch launch (+ ~5 us of the empty one)
 ms = st["linearize_ms"] / N
-print("B=%d obs=%d  k_linearize %.1f us/launch  algorithmic (SURVEY 8d) %.1f MB -> %.0f GB/s (%.2f of 8 TB/s); stored bytes %.1f MB -> %.0f GB/s  [variant %s]" % (B, n_obs, ms * 1e3, alg / 1e6, alg / ms / 1e6, alg / ms / 1e6 / 8000, stored / 1e6, stored / ms / 1e6, os.environ.get("KBA_DEBUG_STAGE", "0")))
+print("B=%d obs=%d  k_linearize %.1f us/launch  algorithmic (SURVEY 8d) %.1f MB -> %.0f GB/s (%.2f of 8 TB/s); stored bytes %.1f MB -> %.0f GB/s" % (B, n_obs, ms * 1e3, alg / 1e6, alg / ms / 1e6, alg / ms / 1e6 / 8000, stored / 1e6, stored / ms / 1e6))

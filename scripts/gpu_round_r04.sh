@@ -13,7 +13,7 @@ python scripts/prof_summary.py $OUT/prof_bench1/bench_results.db > $OUT/rocprof_
 rm -rf $OUT/prof_bench1
 timeout 600 python scripts/pmc_collect.py --passes all --out $OUT/pmc_kernels.json --timeout 500 | tee $OUT/pmc_summary.txt
 ./scripts/gpu_single_ab.sh "single:A=1" | tee $OUT/single_window.txt
-KBA_COOP_PLAIN_LAUNCH=1 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_single -o s -- python /tmp/single.py single > $OUT/prof_single.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_single -o s -- python /tmp/single.py single > $OUT/prof_single.log 2>&1
 python scripts/prof_summary.py $OUT/prof_single/s_results.db > $OUT/rocprof_kernel_stats_single_window.txt; head -6 $OUT/rocprof_kernel_stats_single_window.txt
 rm -rf $OUT/prof_single
 if [ -z "$SKIP_DRIVE" ]; then

@@ -3,7 +3,6 @@
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["KBA_GROUPS"] = "1"
-os.environ["KBA_SLOTS"] = "1024"
 from limo_amd import synth
 
 B = 1024
