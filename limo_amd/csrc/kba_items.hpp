@@ -443,13 +443,13 @@ KBA_HD int lin_lm_lane(const BatchView& bv, const SolveConsts& c, int w, int gl,
         lin_fetch(bv, s, gl, in);
         const double* vl = bv.view_lin + (int64_t)kViewLin * (wd.view0 + j);
         double r3[3], c4[4];
-        if (j < wd.n_view_fixed0) {  // keyframe without a free pose block: cost, residual and planes only
+        if (j < wd.n_view_fixed0) {  // keyframe without a free pose block: cost and residual only (nobody reads its planes)
             if (!lin_obs<false>(vl, c, in, want_cost, r3, c4, cam[j])) fail = 1;
         } else {
             if (!lin_obs<true>(vl, c, in, want_cost, r3, c4, cam[j])) fail = 1;
+            bv.obs_c[s] = c4[0];  // (au, sd: the residual stays in the lane, xn / yn are rebuilt from the landmark: view_xy)
+            bv.obs_c[bv.SO + s] = c4[3];
         }
-        bv.obs_c[s] = c4[0];  // (au, sd: the residual stays in the lane, xn / yn are rebuilt from the landmark: view_xy)
-        bv.obs_c[bv.SO + s] = c4[3];
         lin_lm_accum(vl, r3, c4, acc);
     }
     if (state == 1) {
@@ -714,6 +714,38 @@ KBA_HD void slab_reduce_entry(const BatchView& bv, int w, int n_shards, int i) {
 
 KBA_HD int schur_col(int i, int nfq) {
     return i + (i >= nfq ? 1 : 0);
+}
+
+// Packed partial slabs (SolveConsts::slab_packed; fast-class windows outside the sharded and the one-launch solve): a slab holds
+// exactly the entries of the enumeration above, back to back - nothing the camera solve does not read, and a lane-contiguous
+// read of a slab is a contiguous run of memory.
+//   * ground-plane slab: the enumeration for the nf free slots, stride schur_need_pad(nf);
+//   * plain slab (landmarks without a ground-plane row: zero outside the pose slots and the rhs): the same enumeration for a
+//     system of the nfq pose slots, stride schur_need_pad(nfq);
+//   * plain slab q of a window at q * stride_plain of its S_part region, ground-plane slab j at P * stride_plain + j * stride_gp
+//     (P = schur_plain_slabs).  The region keeps the size of the tile layout (spart_off: one nf_pad^2 tile matrix per Schur
+//     block), which is never smaller.
+// Index of entry (ca, cb) in the enumeration for n slots (ca <= cb <= n, cb == n: the rhs)
+KBA_HD int schur_need_index(int n, int ca, int cb) { return ca * (n + 1) - ca * (ca - 1) / 2 + (cb - ca); }
+KBA_HD int64_t slab_packed_base(int q, int n_plain, int nf, int nfq) {
+    return q < n_plain ? (int64_t)q * schur_need_pad(nfq) : (int64_t)n_plain * schur_need_pad(nfq) + (int64_t)(q - n_plain) * schur_need_pad(nf);
+}
+// Reader: entry (ca, cb) of the enumeration for nf (cb == nf: the rhs) -> index inside a slab of the class, -1: a plain slab
+// has no such entry (it involves a plane slot: an exact zero)
+KBA_HD int slab_packed_read(bool gp, int ca, int cb, int nf, int nfq) {
+    if (gp) return schur_need_index(nf, ca, cb);
+    if (ca >= nfq || (cb >= nfq && cb < nf)) return -1;
+    return schur_need_index(nfq, ca, cb < nf ? cb : nfq);
+}
+// Writer: entry (zr, zc) of the Gram matrix Z^T Z in schur_col space - column nfq is the rhs t, compact slot i sits in column
+// i + (i >= nfq) - -> index inside a slab of the class, -1: nobody reads the entry (lower triangle, |t|^2, padding columns,
+// plane columns of a plain slab).  The rhs of a slot in front of column nfq is entry (slot, nfq), of a slot behind it (nfq, slot).
+KBA_HD int slab_packed_write(bool gp, int zr, int zc, int nf, int nfq) {
+    const int n = gp ? nf : nfq;  // slots of the slab's system: columns [0, n]
+    if (zr > zc || zc > n || (zr == nfq && zc == nfq)) return -1;
+    if (zc == nfq) return schur_need_index(n, zr, n);
+    if (zr == nfq) return schur_need_index(n, zc - 1, n);
+    return schur_need_index(n, zr - (zr > nfq ? 1 : 0), zc - (zc > nfq ? 1 : 0));
 }
 
 // ======================================================================================= back-substitution
@@ -1536,56 +1568,80 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     // in the (q mod 4) order and the sums keep their bits (a skipped term is an exact zero).  Round 5: this sum is what bounds
     // k_cam_solve in a batch (137 KB of slab entries per window and iteration at C2; 86 KB with the skip).
     const int q_gp = c.schur_nslab > 0 ? 0 : (schur_plain_slabs(wd, c.schur_span) & ~3);
+    // Where slab q starts and where an entry sits in it.  Tile layout and the packed slabs of S_red: every slab has the stride
+    // `slab` and holds an entry at the same offset.  Packed partial slabs (SolveConsts::slab_packed, fast-class windows): the
+    // first n_pk slabs - the plain ones - have the stride and the entry offsets of a system of the nfq pose slots, the
+    // ground-plane slabs behind them those of the nf free slots (slab_packed_base / slab_packed_read): consecutive lanes read
+    // consecutive doubles of a slab.  Same slabs, same chains, same order of the sum: only the address of a term changes.
+    const bool pk = c.slab_packed && wd.schur_fast && c.schur_nslab == 0;
+    const int n_pk = pk ? schur_plain_slabs(wd, c.schur_span) : 0;
+    const int64_t stride_pl = pk ? schur_need_pad(nfq) : 0, stride_gp = pk ? schur_need_pad(nf) : slab;
+    // (a skipped term's load: the entry's place in the LAST slab, as seen by a ground-plane slab - inside the window's region
+    // for every mix of classes: with a ground-plane slab last it is that slab's entry; with none, or no slab but plain ones
+    // packed, an index below schur_need_pad(nf) <= nf_pad^2 from the region's start or the last tile slab's)
+    const int64_t skip_base = pk ? (n_slab > n_pk ? slab_packed_base(n_slab - 1, n_pk, nf, nfq) : 0) : (int64_t)(n_slab - 1) * slab;
     constexpr int kE = 4;  // entries a lane sums at once
     for (int i0 = tid; i0 < n_need; i0 += kE * nt) {
-        double s[kE], acc[kE][4];
-        int64_t off[kE];
+        double acc[kE][4];
+        int off[kE], off_pl[kE];  // the entry's offset in a slab (ground-plane slab when packed) | in a packed plain slab, -1: none
         int dst[kE], qs[kE];
         for (int e = 0; e < kE; ++e) {
             const int i = i0 + e * nt;
             dst[e] = -1;
             off[e] = 0;
+            off_pl[e] = -1;
             qs[e] = n_slab;
-            s[e] = 0.0;
             for (int r = 0; r < 4; ++r) acc[e][r] = 0.0;
             if (i >= n_need) continue;
             int ca, cb;
             schur_need_decode(i, nf, ca, cb);
             const int a = fl[ca];
+            double s_e;
             if (cb < nf) {
                 const int b = fl[cb];
                 double v = sc[a] * sc[b] * Hg[a * nc + b];
                 Hs[i] = v;
                 if (ca == cb) v += fmin(fmax(v, c.min_lm_diagonal), c.max_lm_diagonal) / radius;
-                s[e] = v;
+                s_e = v;
             } else {
-                s[e] = sc[a] * bv.gc[wd.cam0 + a];
-                Hs[i] = s[e];
+                s_e = sc[a] * bv.gc[wd.cam0 + a];
+                Hs[i] = s_e;
             }
-            // (packed slabs of a sharded solve hold exactly these entries in this order)
-            off[e] = c.schur_packed ? (int64_t)i : schur_need_offset(ca, cb, nf, nfq, nfp);
+            // (packed slabs - of a sharded solve's S_red, ground-plane slabs of S_part - hold exactly these entries in this order)
+            off[e] = (c.schur_packed || pk) ? i : (int)schur_need_offset(ca, cb, nf, nfq, nfp);
+            if (pk) off_pl[e] = slab_packed_read(false, ca, cb, nf, nfq);
             dst[e] = ca * lda + cb;
+            A[dst[e]] = s_e;  // (waits at its place - this lane's own - while the slabs are summed: eight registers less over the loop)
             qs[e] = (ca >= nfq || (cb >= nfq && cb < nf)) ? q_gp : 0;
         }
         // (branch-free: a skipped term loads the same entry of the LAST slab instead - a line the sum reads anyway - and adds an exact
         // zero; with a branch around the loads the 16 loads of a step were no longer in flight together, and a window with 79 slabs -
         // C4 - took 30 % longer per LM iteration)
+        // (packed: a plain slab in the chains of an entry that involves a plane slot - one of the up to three between q_gp and the
+        // first ground-plane slab - has no such entry: skipped as well, where the tile layout read a zero the Schur wave had stored
+        // or the allocation had left)
         int q = 0;
         for (; q + 4 <= n_slab; q += 4)
             for (int e = 0; e < kE; ++e)
                 for (int r = 0; r < 4; ++r) {
-                    const bool on = q >= qs[e];
-                    const double v = sp[(int64_t)(on ? q + r : n_slab - 1) * slab + off[e]];
+                    const bool plain = q + r < n_pk;  // (uniform)
+                    const int64_t base = plain ? (int64_t)(q + r) * stride_pl : n_pk * stride_pl + (int64_t)(q + r - n_pk) * stride_gp;
+                    const int o = plain ? off_pl[e] : off[e];
+                    const bool on = q >= qs[e] && o >= 0;
+                    const double v = sp[on ? base + o : skip_base + off[e]];
                     acc[e][r] += on ? v : 0.0;
                 }
         for (; q < n_slab; ++q)
             for (int e = 0; e < kE; ++e) {
-                const bool on = q >= qs[e];
-                const double v = sp[(int64_t)(on ? q : n_slab - 1) * slab + off[e]];
+                const bool plain = q < n_pk;
+                const int64_t base = plain ? (int64_t)q * stride_pl : n_pk * stride_pl + (int64_t)(q - n_pk) * stride_gp;
+                const int o = plain ? off_pl[e] : off[e];
+                const bool on = q >= qs[e] && o >= 0;
+                const double v = sp[on ? base + o : skip_base + off[e]];
                 acc[e][0] += on ? v : 0.0;
             }
         for (int e = 0; e < kE; ++e)
-            if (dst[e] >= 0) A[dst[e]] = s[e] - ((acc[e][0] + acc[e][1]) + (acc[e][2] + acc[e][3]));
+            if (dst[e] >= 0) A[dst[e]] = A[dst[e]] - ((acc[e][0] + acc[e][1]) + (acc[e][2] + acc[e][3]));
     }
     KBA_SYNC();
     KBA_TICK(9);

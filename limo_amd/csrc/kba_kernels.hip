@@ -470,7 +470,7 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     }
     const int rs14_idx = rs14_index(lane);
     // ---- the leading views of keyframes WITHOUT a free pose block (WinDesc::n_view_fixed0: the Pose-fixed oldest keyframe of
-    //      a sliding window): same pipeline, same planes, same landmark-block terms, but no pose Jacobian, no U / g, and only the
+    //      a sliding window): same pipeline, same landmark-block terms, but no planes stored, no pose Jacobian, no U / g, and only the
     //      cost leaves the wave (the slice's other 27 entries are zeros).  A loop of its own: the general loop below stays one
     //      straight-line body (a uniform branch inside it cost more than the skipped third of the arithmetic gave back).
     const int j_cam0 = wd.n_view_fixed0;
@@ -495,11 +495,7 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         LinLane l;
         double r3[3], c4[4];
         if (!lin_obs<false>(vl, c, in, want_cost, r3, c4, l)) fail = 1;
-        {
-            const int64_t o = have ? s : dump;
-            bv.obs_c[o] = c4[0];
-            bv.obs_c[bv.SO + o] = c4[3];
-        }
+        // (no planes stored: the Schur fills load them for keyframes with a free pose block only, k_backsub starts behind these views)
         accum(vl, r3, c4);
         const double tot = wave_sum_all(l.e[0]);
         if (lane < kLinPartial) lv_lds[(j * kLinWaves + wave) * kLinPartial + lane] = lane == 0 ? tot : 0.0;
@@ -823,7 +819,7 @@ __device__ __forceinline__ void schur_wave_sync() {
     }
 }
 template <int TM, bool GP, bool COOP>
-__device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, int span, int span_gp, double* smem) {
+__device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, int span, int span_gp, int slab_packed, double* smem) {
     const int w = bv.sblk_win[sb];
     // (COOP: k_solve_coop only gets here for a window that iterates - and workgroup 0 may be writing the window's LM state at
     // this very moment (lm_decide_lin runs beside the Schur phase), so the state is not read here)
@@ -1080,13 +1076,50 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         }
         schur_wave_sync<COOP>();
     }
-    // ---- the slab of this group: tiles (tr <= tc) of the nfp x nfp matrix.  A ground-plane group writes all of them (zeros
-    //      outside its columns included).  A plain group only writes the tiles that hold its pose columns and the rhs (rows and
-    //      columns <= nfq): the readers of the slabs - cam_solve, slab_reduce_entry, k_solve_coop's slab sum - never look at a
-    //      plain slab outside them (round 5: 6 KB instead of 12 KB per plain slab at C2), and a slab keeps its class for the
-    //      life of the batch (schur_slab_of: plain groups first, fixed spans).
-    double* out = bv.S_part + wd.spart_off + (int64_t)schur_slab_of(wd, sb, span, span_gp) * ((int64_t)nfp * nfp);
+    // ---- the slab of this group.
+    //      Packed (SolveConsts::slab_packed, never COOP): exactly the entries the camera solve reads - upper triangle of the
+    //      slab's slots + rhs in cam_solve's enumeration (kba_items.hpp:slab_packed_write), a plain slab for the nfq pose slots
+    //      only - as predicated stores of the accumulators, unchanged, straight to their packed places; the 16 lanes of a tile
+    //      row land in one contiguous run.  2.6 KB per plain and 6.9 KB per ground-plane slab at four free keyframes.
+    //      Tile layout (k_solve_coop, whose slab sum indexes it, and the landmark-sharded solve: slab_reduce_entry): tiles
+    //      (tr <= tc) of the nfp x nfp matrix.  A ground-plane group writes all of them (zeros outside its columns included).
+    //      A plain group only writes the tiles that hold its pose columns and the rhs (rows and columns <= nfq): the readers
+    //      never look at a plain slab outside them (6 KB instead of 12 KB per plain slab at C2).
+    //      Either way a slab keeps its class and its place for the life of the batch (schur_slab_of: plain groups first,
+    //      fixed spans).
+    const bool packed = !COOP && slab_packed != 0;
+    const int q_slab = schur_slab_of(wd, sb, span, span_gp);
+    double* out = bv.S_part + wd.spart_off +
+                  (packed ? slab_packed_base(q_slab, schur_plain_slabs(wd, span), wd.nf, nfq) : (int64_t)q_slab * ((int64_t)nfp * nfp));
     const int T = nfp / 16;
+    if (two_tile && packed) {
+        // the two products and the rhs sums go from the registers to their packed places (no staging matrix: nothing has to be
+        // zero-filled, and no entry is written twice - the second product leaves the block {0..7} x {16..23} to the first)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = kq + 4 * r;
+            {   // first product: entry (row, 8 + li)
+                const int col = 8 + li;
+                if (row <= col && col < nfq) out[slab_packed_write(false, row, col, wd.nf, nfq)] = acc[0][r];
+            }
+            {   // second product: entry (m(row), m(li))
+                const int a = row < 8 ? row : row + 8, b = mq;
+                if (a <= b && b < nfq && !(a < 8 && b >= 16)) out[slab_packed_write(false, a, b, wd.nf, nfq)] = acc[1][r];
+            }
+        }
+        if (have) {  // rhs: sum of this keyframe's six slot values over the 16 landmark lanes
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                double v = yt[a];
+                v += __shfl_xor(v, 1, 64);
+                v += __shfl_xor(v, 2, 64);
+                v += __shfl_xor(v, 4, 64);
+                v += __shfl_xor(v, 8, 64);
+                if (li == 0) out[slab_packed_write(false, zcs[kq * 12] + a, nfq, wd.nf, nfq)] = v;
+            }
+        }
+        return;
+    }
     if (two_tile) {
         // the two products and the rhs sums meet in a 32 x 32 staging matrix in LDS (the Z tile is free now), from where
         // the slab is written in the layout of the three-tile path (upper tiles, zeros outside the Gram)
@@ -1131,7 +1164,12 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = kq + 4 * r, col = li;
-            out[row * nfp + col] = (row < ncol && col < ncol) ? acc[0][r] : 0.0;
+            if (packed) {
+                const int k = slab_packed_write(false, row, col, wd.nf, nfq);
+                if (k >= 0) out[k] = acc[0][r];
+            } else {
+                out[row * nfp + col] = (row < ncol && col < ncol) ? acc[0][r] : 0.0;
+            }
         }
     } else {
         int idx = 0;
@@ -1144,28 +1182,34 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
                     for (int r = 0; r < 4; ++r) {
                         // f64 16x16x4 C/D layout: row = (lane>>4) + 4*reg, col = lane&15
                         const int row = tr * 16 + kq + 4 * r, col = tc * 16 + li;
-                        out[row * nfp + col] = (row < ncol && col < ncol) ? acc[idx][r] : 0.0;
+                        if (packed) {
+                            const int k = slab_packed_write(GP, row, col, wd.nf, nfq);
+                            if (k >= 0) out[k] = acc[idx][r];
+                        } else {
+                            out[row * nfp + col] = (row < ncol && col < ncol) ? acc[idx][r] : 0.0;
+                        }
                     }
                 }
                 ++idx;
             }
         if constexpr (GP) {
-            for (int tc = TM; tc < T; ++tc)
-                for (int tr = 0; tr <= tc; ++tr) {
+            if (!packed)
+                for (int tc = TM; tc < T; ++tc)
+                    for (int tr = 0; tr <= tc; ++tr) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) out[(tr * 16 + kq + 4 * r) * nfp + tc * 16 + li] = 0.0;
-                }
+                        for (int r = 0; r < 4; ++r) out[(tr * 16 + kq + 4 * r) * nfp + tc * 16 + li] = 0.0;
+                    }
         }
     }
 }
 // (without the occupancy attribute the two variants of a round take 180 / 276 registers: +16 % / +46 %, profiles/r05_experiment_schur_ablations.txt)
 template <int TM, bool GP, int WAVES>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_schur_lean(
-    BatchView bv, const int32_t* wl, int span, int span_gp) {
+    BatchView bv, const int32_t* wl, int span, int span_gp, int slab_packed) {
     const int sb = wl_at(bv, wl, blockIdx.x);
     if (sb < 0) return;
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    schur_lean_group<TM, GP, false>(bv, sb, span, span_gp, smem);
+    schur_lean_group<TM, GP, false>(bv, sb, span, span_gp, slab_packed, smem);
 }
 
 // The plain and the ground-plane groups of a round in ONE launch (workgroups [0, n_plain_cap) take the plain list, the others the
@@ -1174,14 +1218,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 // (218: two waves per SIMD), so it is only used while the batch drains (limo_hip.hip: kSchurPairBound); same device functions, same
 // slabs, same bits.
 template <int TMP, int TMG>
-__global__ __launch_bounds__(64) void k_schur_lean_pair(BatchView bv, const int32_t* wl_plain, int n_plain_cap, const int32_t* wl_gp, int span, int span_gp) {
+__global__ __launch_bounds__(64) void k_schur_lean_pair(BatchView bv, const int32_t* wl_plain, int n_plain_cap, const int32_t* wl_gp, int span, int span_gp, int slab_packed) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if ((int)blockIdx.x < n_plain_cap) {
         const int sb = wl_at(bv, wl_plain, blockIdx.x);
-        if (sb >= 0) schur_lean_group<TMP, false, false>(bv, sb, span, span_gp, smem);
+        if (sb >= 0) schur_lean_group<TMP, false, false>(bv, sb, span, span_gp, slab_packed, smem);
     } else {
         const int sb = wl_at(bv, wl_gp, blockIdx.x - n_plain_cap);
-        if (sb >= 0) schur_lean_group<TMG, true, false>(bv, sb, span, span_gp, smem);
+        if (sb >= 0) schur_lean_group<TMG, true, false>(bv, sb, span, span_gp, slab_packed, smem);
     }
 }
 
@@ -1776,17 +1820,17 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
             if (t < n_pg) {
                 const int sb = wd.sblk0 + t * c.schur_span;
                 if (a.vp == 1)
-                    schur_lean_group<1, false, true>(bv, sb, c.schur_span, c.schur_span_gp, mine);
+                    schur_lean_group<1, false, true>(bv, sb, c.schur_span, c.schur_span_gp, 0, mine);
                 else
-                    schur_lean_group<2, false, true>(bv, sb, c.schur_span, c.schur_span_gp, mine);
+                    schur_lean_group<2, false, true>(bv, sb, c.schur_span, c.schur_span_gp, 0, mine);
             } else {
                 const int sb = wd.sblk0 + wd.n_sblk_plain + (t - n_pg) * c.schur_span_gp;
                 if (a.vg == 1)
-                    schur_lean_group<1, true, true>(bv, sb, c.schur_span, c.schur_span_gp, mine);
+                    schur_lean_group<1, true, true>(bv, sb, c.schur_span, c.schur_span_gp, 0, mine);
                 else if (a.vg == 2)
-                    schur_lean_group<2, true, true>(bv, sb, c.schur_span, c.schur_span_gp, mine);
+                    schur_lean_group<2, true, true>(bv, sb, c.schur_span, c.schur_span_gp, 0, mine);
                 else
-                    schur_lean_group<3, true, true>(bv, sb, c.schur_span, c.schur_span_gp, mine);
+                    schur_lean_group<3, true, true>(bv, sb, c.schur_span, c.schur_span_gp, 0, mine);
             }
             schur_wave_sync<true>();  // the wave's LDS region is reused by its next group
         }

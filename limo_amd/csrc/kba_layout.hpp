@@ -146,6 +146,11 @@ struct SolveConsts {  // subset of limo_ba_options the kernels need
     int32_t schur_packed; // 1 (landmark-sharded solve): a slab of S_red holds ONLY the entries the camera solve reads - upper triangle
                           // of the free slots + rhs, in the order cam_solve enumerates them (kba_items.hpp:schur_need_offset), stride
                           // schur_need_pad(nf) - what a shard puts on the wire per LM iteration (33 KB at 90 free slots, not 74 KB)
+    int32_t slab_packed;  // 1 (per launch: the streaming solve and the lock-step launches of an unsharded batch): the partial slabs of
+                          // a fast-class window (WinDesc::schur_fast) in S_part hold only the entries the camera solve reads, back to
+                          // back (kba_items.hpp:slab_packed_write / slab_packed_read), not 16 x 16 tiles of an nf_pad x nf_pad matrix.
+                          // Only together with schur_nslab == 0.  0: tile layout (k_schur_wide windows, the landmark-sharded solve,
+                          // k_solve_coop)
 };
 
 // Raw pointers to every buffer of a batch (device pointers in the library, host pointers in the emulator).

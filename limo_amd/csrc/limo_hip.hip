@@ -395,6 +395,11 @@ struct limo_ba_batch : Executor {
         return LIMO_OK;
     }
 
+    // S_part holds packed slabs (SolveConsts::slab_packed) of an earlier solve of this batch.  The tile layout counts on the zeros of
+    // the allocation in the tiles a plain group never writes (the slab sums read them for the up to three plain slabs behind q_gp),
+    // and packed slabs lie across such tiles: the one-launch solve clears the buffer first (a solve after limo_ba_batch_reset that
+    // follows a warm re-solve - rare, and a fill of a few MB)
+    bool spart_has_packed = false;
     bool pristine = true;  // the device state is the state of create / reset: what a recovered barrier timeout of the one-launch solve restores
     int reset_state() {
         pristine = true;
@@ -427,6 +432,10 @@ struct limo_ba_batch : Executor {
         c.schur_span_gp = 1;
         c.schur_nslab = shard_P > 1 ? shard_P : 0;
         c.schur_packed = shard_P > 1 ? 1 : 0;
+        // the launch sequences of an unsharded batch (lock-step and streaming) keep the partial slabs of fast-class windows packed
+        // (kba_items.hpp:slab_packed_write); a sharded solve reduces tile slabs (slab_reduce_entry), and the one-launch solve, whose
+        // own slab sum indexes the tile layout, gets a copy of the constants without it (solve_coop)
+        c.slab_packed = shard_P > 1 ? 0 : 1;
     }
 
     // ---- sharding helpers
@@ -742,6 +751,7 @@ struct limo_ba_batch : Executor {
 
     void step() override {
         hipStream_t s = ctx->stream;
+        if (c.slab_packed) spart_has_packed = true;
         for (size_t i = 0; i < pv.size(); ++i)
             if (count_lblk(i)) {
                 hipLaunchKernelGGL(k_lm_damp, dim3(count_lblk(i)), dim3(kBlock), 0, s, pv[i], c, list_lblk(i));
@@ -752,16 +762,16 @@ struct limo_ba_batch : Executor {
             for (size_t i = 0; i < pv.size(); ++i) {
                 int n_plain = count_sblk_plain(i), n_fgp = count_sblk_fgp(i);
                 const int n_gen = count_sblk(i) - n_plain - n_fgp;
-                int span = c.schur_span, span_gp = c.schur_span_gp;
+                int span = c.schur_span, span_gp = c.schur_span_gp, packed = c.slab_packed;
                 const int32_t* wlp = list_sblk(i);
                 if (n_plain) {
-                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp};
+                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
                     note(hipLaunchKernel(schur_fn_plain, dim3(n_plain), dim3(64), args, plain_lds_bytes, s), "launch k_schur_lean");
                     LAUNCH_CHECK("k_schur_lean");
                     wlp += n_plain;
                 }
                 if (n_fgp) {
-                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp};
+                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
                     note(hipLaunchKernel(schur_fn_leangp, dim3(n_fgp), dim3(64), args, leangp_lds_bytes, s), "launch k_schur_lean (gp)");
                     LAUNCH_CHECK("k_schur_lean (gp)");
                     wlp += n_fgp;
@@ -975,24 +985,24 @@ struct limo_ba_batch : Executor {
         // ---- trust-region step of the windows that iterate
         {
             EventPair* ep = time_kernels ? timed(LIMO_KERNEL_SCHUR, s) : nullptr;
-            int span = c.schur_span, span_gp = c.schur_span_gp;
+            int span = c.schur_span, span_gp = c.schur_span_gp, packed = c.slab_packed;
             // few windows in flight (the batch drains): both fast-class lists in one launch (kba_kernels.hip:k_schur_lean_pair)
             const bool pair = schur_pair_ok && bound <= kSchurPairBound && cap[SL_SPLAIN] && cap[SL_SFGP];
             if (pair) {
                 const int32_t *wlp = L(SL_SPLAIN), *wlg = L(SL_SFGP);
                 int n_plain_cap = cap[SL_SPLAIN];
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&n_plain_cap, (void*)&wlg, (void*)&span, (void*)&span_gp};
+                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&n_plain_cap, (void*)&wlg, (void*)&span, (void*)&span_gp, (void*)&packed};
                 note(hipLaunchKernel((const void*)k_schur_lean_pair<2, 3>, dim3(cap[SL_SPLAIN] + cap[SL_SFGP]), dim3(64), args, std::max(plain_lds_bytes, leangp_lds_bytes), s),
                      "launch k_schur_lean_pair");
             }
             if (!pair && cap[SL_SPLAIN]) {
                 const int32_t* wlp = L(SL_SPLAIN);
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp};
+                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
                 note(hipLaunchKernel(schur_fn_plain, dim3(cap[SL_SPLAIN]), dim3(64), args, plain_lds_bytes, s), "launch k_schur_lean");
             }
             if (!pair && cap[SL_SFGP]) {
                 const int32_t* wlp = L(SL_SFGP);
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp};
+                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
                 note(hipLaunchKernel(schur_fn_leangp, dim3(cap[SL_SFGP]), dim3(64), args, leangp_lds_bytes, s), "launch k_schur_lean (gp)");
             }
             if (cap[SL_SGEN]) {
@@ -1082,6 +1092,10 @@ struct limo_ba_batch : Executor {
             return false;
         }
         note(hipMemsetAsync(d_coop_bar, 0, sizeof(int32_t) * 8 * P.n_win, ctx->stream), "memset barrier words");
+        if (spart_has_packed) {
+            note(hipMemsetAsync(bv.S_part, 0, sizeof(double) * (size_t)std::max<int64_t>(1, P.spart_total), ctx->stream), "clear packed Schur slabs");
+            spart_has_packed = false;
+        }
         h_active[8] = 0;
         CoopParams cp;
         cp.G = coop_G;
@@ -1102,7 +1116,9 @@ struct limo_ba_batch : Executor {
         cp.plane_rep = d_plane_rep;
         cp.plane_dep = d_plane_dep;
         cp.red = d_coop_red;
-        void* args[] = {(void*)&bv, (void*)&c, (void*)&cp};
+        SolveConsts cc = c;
+        cc.slab_packed = 0;  // (tile layout: the slab sum of k_solve_coop indexes it)
+        void* args[] = {(void*)&bv, (void*)&cc, (void*)&cp};
         // A PLAIN launch, with the co-residency of the grid checked here against the occupancy the runtime reports (the workgroups
         // of other kernels on the device all finish, so every workgroup of this grid gets its CU; a barrier that waits too long is
         // recovered, coop_sync).  hipLaunchCooperativeKernel gives the same guarantee from the runtime, but after the first such launch
@@ -1133,6 +1149,7 @@ struct limo_ba_batch : Executor {
         if (const char* e = std::getenv("KBA_GROUPS")) n_groups = std::max(1, std::min(4, std::atoi(e)));
         if (stream_setup(n_groups) != LIMO_OK) return LIMO_ERR_RUNTIME;
         set_span();
+        if (c.slab_packed) spart_has_packed = true;
         hipStream_t s0 = ctx->stream;
         groups[0].stream = s0;
         HIP_TRY(ctx, hipMemsetAsync(d_sched_ctl, 0, sizeof(int32_t) * 8, s0));
