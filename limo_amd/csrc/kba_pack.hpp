@@ -34,6 +34,14 @@ void pack_arena_lend(PackArena* a);              // this thread's pack_windows c
 void pack_arena_register(const void* base, size_t cap, bool add);  // the ranges pack_arena_owns knows (process-wide)
 bool pack_arena_owns(const void* p);
 void* pack_arena_take(size_t bytes);             // nullptr: no arena lent / no room
+// Lends *a (nothing when null) for the life of the guard: the loan ends however the scope is left, so that the thread's arena
+// pointer never outlives the PackArena it aims at.
+struct PackArenaLend {
+    explicit PackArenaLend(PackArena* a) { pack_arena_lend(a); }
+    ~PackArenaLend() { pack_arena_lend(nullptr); }
+    PackArenaLend(const PackArenaLend&) = delete;
+    PackArenaLend& operator=(const PackArenaLend&) = delete;
+};
 
 template <typename T>
 struct default_init_allocator : std::allocator<T> {

@@ -3,12 +3,36 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "kba_pack.hpp"
+
+// Grow-only pinned host buffer: ensure() keeps what it has when that holds `bytes`, else it frees it and allocates
+// max(bytes, min_bytes), at most max_bytes.  A failed allocation leaves the buffer empty.
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes, size_t min_bytes = 0, size_t max_bytes = ~size_t(0)) {
+        if (cap >= bytes) return hipSuccess;
+        release();
+        const size_t want = std::min(max_bytes, std::max(bytes, min_bytes));
+        const hipError_t e = hipHostMalloc(&p, want);
+        if (e == hipSuccess)
+            cap = want;
+        else
+            p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
 
 struct limo_ctx {
     int device = 0;
@@ -24,8 +48,7 @@ struct limo_ctx {
     // fabric run the landmark-sharded solve with world > 1
     void (*xfn)(const double* send, double* recv, long long count, int kind, void* user) = nullptr;
     void* xuser = nullptr;
-    double* xhost = nullptr;  // pinned staging: [1 + world][count]
-    size_t xhost_cap = 0;
+    PinnedBuf xhost;  // pinned staging: [1 + world][count] doubles
     bool has_transport() const { return comm != nullptr || xfn != nullptr; }
     long long exchange_stats[3] = {0, 0, 0};  // last landmark-sharded solve: exchange steps, bytes per rank, LM iterations
     long long coop_fallbacks = 0;           // one-launch solves whose barrier timed out and that were redone as a launch sequence
@@ -38,18 +61,15 @@ struct limo_ctx {
     static constexpr int kPoolPerClass = 4;
     static constexpr size_t kPoolMaxBlock = 32u << 20;  // larger blocks (big batches) go straight to hipMalloc / hipFree
     std::map<size_t, std::vector<void*>> pool, host_pool;  // device blocks / pinned host blocks
-    void* staging = nullptr;                // pinned host staging buffer of small uploads
-    size_t staging_cap = 0;
+    PinnedBuf staging;                      // pinned host staging buffer of small uploads
     // Pinned host arena the big arrays of ONE batch's packing are carved from (kba_pack.hpp:PackArena): grow-only up to kPackArenaMax,
     // lent to a batch at its creation when no other live batch holds it, recycled when that batch is destroyed.  A batch packed into
     // it touches no fresh pages and uploads by DMA straight from where the pack wrote (1024 C2 windows: create 21 -> ~14 ms).
-    void* pack_arena = nullptr;
-    size_t pack_arena_cap = 0;
+    PinnedBuf pack_arena;
     size_t pack_arena_wanted = 0;           // what the last batch that did not fit would have needed
     bool pack_arena_busy = false;
     static constexpr size_t kPackArenaMax = size_t(1) << 30;
-    void* staging_big = nullptr;            // pinned host buffer the results of a LARGE batch come back through (grow-only, <= kBigStageMax)
-    size_t staging_big_cap = 0;
+    PinnedBuf staging_big;                  // pinned host buffer the results of a LARGE batch come back through (<= kBigStageMax)
     static constexpr size_t kBigStageMax = 512u << 20;
 
     // Larger blocks (the arena of a 1024-window batch is ~1.5 GB) are kept too, in 64 MB classes, one per class and at most
@@ -133,20 +153,10 @@ struct limo_ctx {
             for (void* p : kv.second) (void)hipFree(p);
         pool.clear();
         pooled_large = 0;
-        if (xhost) (void)hipHostFree(xhost);
-        xhost = nullptr;
-        xhost_cap = 0;
-        if (staging) (void)hipHostFree(staging);
-        staging = nullptr;
-        staging_cap = 0;
-        if (staging_big) (void)hipHostFree(staging_big);
-        staging_big = nullptr;
-        staging_big_cap = 0;
-        if (pack_arena) {
-            kba::pack_arena_register(pack_arena, pack_arena_cap, false);
-            (void)hipHostFree(pack_arena);
-        }
-        pack_arena = nullptr;
-        pack_arena_cap = 0;
+        xhost.release();
+        staging.release();
+        staging_big.release();
+        if (pack_arena.p) kba::pack_arena_register(pack_arena.p, pack_arena.cap, false);
+        pack_arena.release();
     }
 };

@@ -10,12 +10,15 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <memory>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "kba_kernels.hip"
 
+#include "kba_batch_plan.hpp"
 #include "kba_buffers.hpp"
 #include "kba_rows.hpp"
 
@@ -62,39 +65,34 @@ struct limo_ba_batch : Executor {
     size_t h_flags_bytes = 0;
     hipEvent_t act_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int it_no = 0;
-    // worklists of the windows that still iterate (nullptr = every workgroup): rebuilt on the host whenever the
-    // active set has halved, so late LM iterations only launch the workgroups that have work
-    int32_t *d_wl_blk = nullptr, *d_wl_lblk = nullptr, *d_wl_sblk = nullptr, *d_wl_win = nullptr, *d_flags = nullptr;
-    int32_t* d_wl_sblk_part = nullptr;                          // Schur worklist of a re-batched active set
-    struct FullSblk {  // Schur worklist of every window, built on first use
-        int32_t* d = nullptr;
-        int n = 0, n_plain = 0, n_fgp = 0;
-    } wl_sblk_full;
+    // The workgroups a producer view pv[i] launches (a null list = every workgroup, in order).  `full` lists every window - of an
+    // unsharded batch without any list but the Schur one, which is built on first use (the one-launch and streaming solves never
+    // need it); of a shard, the workgroups it owns.  `cur` is what the lock-step launches use: `full`, or the lists of the windows
+    // that still iterate - rebuilt on the host whenever the active set has halved, so late LM iterations only launch the workgroups
+    // that have work (rebatch).
     // Schur worklists are ordered [plain groups of fast windows | ground-plane groups of fast windows | generic windows]
-    int n_wl_sblk_plain = 0, n_wl_sblk_fgp = 0;
-    const void* schur_fn_plain = nullptr;
-    int plain_lds_bytes = 0;
-    const void* schur_fn_leangp = nullptr;
-    int leangp_lds_bytes = 0;
-    int schur_vp = 1, schur_vg = 1;  // the same choice as template arguments of the one-launch solve (k_solve_coop)
-    bool schur_pair_ok = false;      // the batch's variants are <2, false> / <3, true>: k_schur_lean_pair<2, 3> exists for them
+    struct WorkLists {
+        const int32_t *blk = nullptr, *lblk = nullptr, *sblk = nullptr, *win = nullptr;
+        int n_blk = 0, n_lblk = 0, n_sblk_plain = 0, n_sblk_fgp = 0, n_sblk = 0, n_win = 0;
+    };
+    struct ViewLists {
+        WorkLists full, cur;
+        int owner = -1;  // shard whose Schur blocks the view lists (-1: all of them)
+    };
+    std::vector<ViewLists> wl;  // [pv.size()]
+    int32_t *d_act_blk = nullptr, *d_act_lblk = nullptr, *d_act_sblk = nullptr, *d_act_win = nullptr;  // device lists of a re-batched active set
+    int32_t* d_flags = nullptr;
+    BatchPlan plan;  // kernel variants and LDS sizes (kba_batch_plan.hpp) ...
+    const void *schur_fn_plain = nullptr, *schur_fn_leangp = nullptr, *schur_fn_gen = nullptr;  // ... and the variants as kernels
+    bool schur_pair_ok = false;      // plan.pair_ok, and KBA_NO_SCHUR_PAIR is not set
     static constexpr int kSchurPairBound = 384;  // windows in flight in a slot group up to which a round launches the pair kernel (192: -0.7 %, 768: -9 % at 1024 windows)
-    std::vector<uint8_t> win_fast;  // per window: k_schur<.., true> applies (<= 4 keyframes with free slots, one view each)
-    int avg_sblk = 0;
     int32_t* h_flags = nullptr;  // pinned
-    std::vector<int32_t> h_wl;
-    bool use_wl = false;
-    int n_wl_blk = 0, n_wl_lblk = 0, n_wl_sblk = 0, n_wl_win = 0, listed = 0;
-    int max_nc = 0, asm_bytes = 0, solve_bytes = 0, trim_bytes = 0;
-    const void* schur_fn_gen = nullptr;  // k_schur_wide<NPW> for the windows outside the fast class (chosen per window: results
-                                         // do not depend on what else is in the batch)
-    int wide_lds_bytes = 0;
     int rc = LIMO_OK;
     // ---- streaming solve (device-side scheduler k_sched): windows move through n_slots slots, a finished window is
     // replaced by the next pending one, so every launch round works on a full set (kba_kernels.hip:k_sched)
     int n_slots = 0;
     int32_t* d_sched_ctl = nullptr;   // [0] cursor over the batch's windows, [1] windows finished (shared by the groups)
-    // ---- landmark sharding.  shard_P == 1: everything below is inert (pv = {bv}).
+    // ---- landmark sharding.  shard_P == 1: everything below is inert (pv = {bv}, local_shards = {0}).
     // Every shard holds the same global layout and owns the observation / landmark / Schur workgroups of its
     // landmarks (rank lists); the per-workgroup partial arrays it produces live in its own "producer view" pv[i] and
     // are summed into the consumer view bv before each window-level kernel: by RCCL all-reduce when the shards are
@@ -111,14 +109,6 @@ struct limo_ba_batch : Executor {
     WinDesc* d_win_orig = nullptr;      // the batch's own window descriptors (bv.win of the consumer view is modified)
     bool first_lin = false, assemble_pending = false;
     int64_t n_exchanges = 0, exchange_bytes = 0;  // all-reduce calls / bytes of this batch so far (limo_ba_batch_exchange_stats)
-    struct RankLists {
-        int32_t *full_blk = nullptr, *full_lblk = nullptr, *full_sblk = nullptr;  // every window listed
-        int32_t *act_blk = nullptr, *act_lblk = nullptr, *act_sblk = nullptr;     // re-batched active set
-        int n_full_blk = 0, n_full_lblk = 0, n_full_sblk = 0, n_full_sblk_plain = 0, n_full_sblk_fgp = 0, n_sblk_plain = 0, n_sblk_fgp = 0;
-        const int32_t *blk = nullptr, *lblk = nullptr, *sblk = nullptr;           // lists in use
-        int n_blk = 0, n_lblk = 0, n_sblk = 0;
-    };
-    std::vector<RankLists> rl;
     double* d_lm_tmp = nullptr;
     // kernel timing (linearize) via HIP events on the batch's stream
     std::vector<EventPair> ev_pool;
@@ -162,34 +152,41 @@ struct limo_ba_batch : Executor {
         return LIMO_OK;
     }
 
-    // Schur worklist over `windows` (all of them when null): first block of every group of `span` blocks of one class,
-    // ordered [plain groups of fast windows | ground-plane groups of fast windows | groups of generic windows];
-    // owner >= 0 keeps the blocks of that shard only.
-    void build_sblk_list(const std::vector<int32_t>* windows, int span, int span_gp, int owner, std::vector<int32_t>& v, int& n_plain, int& n_fgp) const {
-        v.clear();
-        n_plain = n_fgp = 0;
-        const int nw = windows ? (int)windows->size() : P.n_win;
-        for (int cls = 0; cls < 3; ++cls) {
-            for (int q = 0; q < nw; ++q) {
-                const int w = windows ? (*windows)[q] : q;
-                const WinDesc& d = P.win[w];
-                if ((cls < 2) != (win_fast[w] != 0)) continue;
-                auto groups = [&](int i0, int i1, int sp) {
-                    for (int i = i0; i < i1; i += sp)
-                        if (owner < 0 || P.sblk_owner[d.sblk0 + i] == owner) v.push_back(d.sblk0 + i);
-                };
-                if (cls != 1) groups(0, d.n_sblk_plain, span);
-                if (cls != 0) groups(d.n_sblk_plain, d.n_sblk, span_gp);
-            }
-            if (cls == 0) n_plain = (int)v.size();
-            if (cls == 1) n_fgp = (int)v.size() - n_plain;
+    // The kernel of a plan entry: cls 0 / 1 = k_schur_lean<a, false / true, b> (a = TM, b = waves per EU), cls 2 = k_schur_wide<a>.
+    static const void* schur_kernel(int cls, int a, int b) {
+        switch (cls * 100 + a * 10 + b) {
+            case 14: return (const void*)k_schur_lean<1, false, 4>;
+            case 23: return (const void*)k_schur_lean<2, false, 3>;
+            case 113: return (const void*)k_schur_lean<1, true, 3>;
+            case 122: return (const void*)k_schur_lean<2, true, 2>;
+            case 132: return (const void*)k_schur_lean<3, true, 2>;
+            case 210: return (const void*)k_schur_wide<1>;
+            case 230: return (const void*)k_schur_wide<3>;
+            case 260: return (const void*)k_schur_wide<6>;
+            case 320: return (const void*)k_schur_wide<12>;
         }
+        return nullptr;
+    }
+
+    // A worklist as a device block of this batch (a synchronous copy).
+    int upload_list(const std::vector<int32_t>& v, const int32_t** out) {
+        int32_t* d = nullptr;
+        if (dmalloc((void**)&d, sizeof(int32_t) * std::max<size_t>(1, v.size()))) return LIMO_ERR_RUNTIME;
+        if (!v.empty()) HIP_TRY(ctx, hipMemcpy(d, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
+        *out = d;
+        return LIMO_OK;
+    }
+    // The Schur worklist of every window, for producer view i.
+    int build_full_sblk(size_t i) {
+        WorkLists& f = wl[i].full;
+        std::vector<int32_t> v;
+        build_sblk_list(P, nullptr, c.schur_span, c.schur_span_gp, wl[i].owner, v, f.n_sblk_plain, f.n_sblk_fgp);
+        f.n_sblk = (int)v.size();
+        return upload_list(v, &f.sblk);
     }
 
     int upload() {
         std::memset(&bv, 0, sizeof(bv));
-        win_fast.assign(P.n_win, 1);
-        for (int w = 0; w < P.n_win; ++w) win_fast[w] = P.win[w].schur_fast ? 1 : 0;  // decided at pack time (kba_pack.cpp)
         // Every buffer of the batch view lives in ONE device block: [initialised buffers | zero-filled buffers].
         // Small batches (a single window) stage the initialised part in pinned host memory and upload it with one
         // copy; large ones copy buffer by buffer (no second host copy of hundreds of MB).  One memset for the rest.
@@ -231,17 +228,11 @@ struct limo_ba_batch : Executor {
         for (Ent& e : ents) *e.slot = arena + e.off;
         constexpr size_t kStageMax = 16u << 20;
         if (init_total <= kStageMax) {
-            if (ctx->staging_cap < init_total) {
-                if (ctx->staging) (void)hipHostFree(ctx->staging);
-                ctx->staging = nullptr;
-                ctx->staging_cap = 0;
-                HIP_TRY(ctx, hipHostMalloc(&ctx->staging, std::max<size_t>(init_total, 1u << 20)));
-                ctx->staging_cap = std::max<size_t>(init_total, 1u << 20);
-            }
+            HIP_TRY(ctx, ctx->staging.ensure(init_total, 1u << 20));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // an earlier upload may still read the staging buffer
             for (const Ent& e : ents)
-                if (e.init) std::memcpy(static_cast<char*>(ctx->staging) + e.off, e.init, e.bytes);
-            if (init_total) HIP_TRY(ctx, hipMemcpyAsync(arena, ctx->staging, init_total, hipMemcpyHostToDevice, ctx->stream));
+                if (e.init) std::memcpy(static_cast<char*>(ctx->staging.p) + e.off, e.init, e.bytes);
+            if (init_total) HIP_TRY(ctx, hipMemcpyAsync(arena, ctx->staging.p, init_total, hipMemcpyHostToDevice, ctx->stream));
         } else {
             // (a host array that initialises several device buffers - the landmarks: current, candidate and pristine copy - crosses the
             // bus ONCE and is copied on the device for the others: 96 MB of 390 less for 1024 C2 windows, 12.2 -> ~9 ms)
@@ -282,32 +273,10 @@ struct limo_ba_batch : Executor {
                 HIP_TRY(ctx, hipMemcpy(d_wc, wc.data(), sizeof(WinDesc) * wc.size(), hipMemcpyHostToDevice));
                 exchange_bind_consumer(xl, bv, arena_c, trims[0], d_wc);
             }
-            rl.assign(local_shards.size(), RankLists());
             for (size_t i = 0; i < local_shards.size(); ++i) {
                 if (zeros(&blocks[i], xl.b_total)) return LIMO_ERR_RUNTIME;  // the shard's own block ...
                 exchange_bind_producer(xl, pv[i], blocks[i], trims[1 + i]);
                 if (zeros(&pv[i].S_part, xl.spart_count)) return LIMO_ERR_RUNTIME;  // ... and its private Schur slabs
-                const int r = local_shards[i];
-                auto make = [&](const std::vector<int32_t>& owner, int32_t** full, int32_t** act, int* n) -> int {
-                    std::vector<int32_t> v;
-                    for (size_t k = 0; k < owner.size(); ++k)
-                        if (owner[k] == r) v.push_back((int32_t)k);
-                    *n = (int)v.size();
-                    if (dmalloc((void**)full, sizeof(int32_t) * std::max<size_t>(1, v.size()))) return LIMO_ERR_RUNTIME;
-                    if (dmalloc((void**)act, sizeof(int32_t) * std::max<size_t>(1, v.size()))) return LIMO_ERR_RUNTIME;
-                    if (!v.empty()) HIP_TRY(ctx, hipMemcpy(*full, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
-                    return LIMO_OK;
-                };
-                if (make(P.blk_owner, &rl[i].full_blk, &rl[i].act_blk, &rl[i].n_full_blk)) return LIMO_ERR_RUNTIME;
-                if (make(P.lblk_owner, &rl[i].full_lblk, &rl[i].act_lblk, &rl[i].n_full_lblk)) return LIMO_ERR_RUNTIME;
-                {   // Schur blocks (span 1)
-                    std::vector<int32_t> v;
-                    build_sblk_list(nullptr, 1, 1, r, v, rl[i].n_full_sblk_plain, rl[i].n_full_sblk_fgp);
-                    rl[i].n_full_sblk = (int)v.size();
-                    if (dmalloc((void**)&rl[i].full_sblk, sizeof(int32_t) * std::max<size_t>(1, v.size()))) return LIMO_ERR_RUNTIME;
-                    if (dmalloc((void**)&rl[i].act_sblk, sizeof(int32_t) * std::max<size_t>(1, v.size()))) return LIMO_ERR_RUNTIME;
-                    if (!v.empty()) HIP_TRY(ctx, hipMemcpy(rl[i].full_sblk, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
-                }
             }
             if (!shard_virtual && dmalloc((void**)&d_lm_tmp, sizeof(double) * 3 * std::max(1, P.TL))) return LIMO_ERR_RUNTIME;
         }
@@ -318,77 +287,51 @@ struct limo_ba_batch : Executor {
         bv.n_active_host = nullptr;
         h_flags_bytes = sizeof(int32_t) * std::max(1, P.n_win);
         HIP_TRY(ctx, ctx->host_alloc((void**)&h_flags, h_flags_bytes));
-        if (dmalloc((void**)&d_wl_blk, sizeof(int32_t) * std::max(1, P.n_blk))) return LIMO_ERR_RUNTIME;
-        if (dmalloc((void**)&d_wl_lblk, sizeof(int32_t) * std::max(1, P.n_lblk))) return LIMO_ERR_RUNTIME;
-        if (dmalloc((void**)&d_wl_sblk_part, sizeof(int32_t) * std::max(1, P.n_sblk))) return LIMO_ERR_RUNTIME;
-        avg_sblk = P.n_win ? (P.n_sblk + P.n_win - 1) / P.n_win : 0;
-        if (dmalloc((void**)&d_wl_win, sizeof(int32_t) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+        if (dmalloc((void**)&d_act_blk, sizeof(int32_t) * std::max(1, P.n_blk))) return LIMO_ERR_RUNTIME;
+        if (dmalloc((void**)&d_act_lblk, sizeof(int32_t) * std::max(1, P.n_lblk))) return LIMO_ERR_RUNTIME;
+        if (dmalloc((void**)&d_act_sblk, sizeof(int32_t) * std::max(1, P.n_sblk))) return LIMO_ERR_RUNTIME;
+        if (dmalloc((void**)&d_act_win, sizeof(int32_t) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
         if (dmalloc((void**)&d_flags, sizeof(int32_t) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
-        for (const WinDesc& d : P.win) max_nc = std::max(max_nc, (int)d.nc);
-        {
-            bool any_fast = false, any_gen = false;
-            int t_gen = 1, nfp_gen = 16, nc_gen = kCamSlots, nv_gen = 1, max_nfq = 0, max_nf = 0;
-            for (int w = 0; w < P.n_win; ++w) {
-                const WinDesc& d = P.win[w];
-                if (win_fast[w]) {
-                    any_fast = true;
-                    max_nfq = std::max(max_nfq, (int)d.nfq);
-                    max_nf = std::max(max_nf, (int)d.nf);
-                } else if (d.n_sblk > 0) {
-                    any_gen = true;
-                    t_gen = std::max(t_gen, d.nf_pad / 16);
-                    nfp_gen = std::max(nfp_gen, (int)d.nf_pad);
-                    nc_gen = std::max(nc_gen, (int)d.nc);
-                    nv_gen = std::max(nv_gen, (int)d.n_view);
-                }
-            }
-            if (any_fast) {
-                schur_vp = (max_nfq + 16) / 16 <= 1 ? 1 : 2;
-                schur_vg = std::min(3, (max_nf + 16) / 16);
-                schur_fn_plain = (max_nfq + 16) / 16 <= 1 ? (const void*)k_schur_lean<1, false, 4> : (const void*)k_schur_lean<2, false, 3>;
-                plain_lds_bytes = schur_lean_lds_bytes(max_nfq + 1);
-                HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_plain, hipFuncAttributeMaxDynamicSharedMemorySize, plain_lds_bytes));
-                const int tg = (max_nf + 16) / 16;
-                schur_fn_leangp = tg <= 1 ? (const void*)k_schur_lean<1, true, 3> : tg == 2 ? (const void*)k_schur_lean<2, true, 2> : (const void*)k_schur_lean<3, true, 2>;
-                leangp_lds_bytes = schur_lean_lds_bytes(max_nf + 1);
-                HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_leangp, hipFuncAttributeMaxDynamicSharedMemorySize, leangp_lds_bytes));
-                schur_pair_ok = schur_vp == 2 && schur_vg == 3 && !(std::getenv("KBA_NO_SCHUR_PAIR") && std::atoi(std::getenv("KBA_NO_SCHUR_PAIR")) != 0);
-                if (schur_pair_ok)
-                    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_schur_lean_pair<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(plain_lds_bytes, leangp_lds_bytes)));
-            }
-            if (any_gen) {
-                const int tiles = t_gen * (t_gen + 1) / 2, npw = (tiles + kWideWaves - 1) / kWideWaves;
-                schur_fn_gen = npw <= 1 ? (const void*)k_schur_wide<1> : npw <= 3 ? (const void*)k_schur_wide<3>
-                             : npw <= 6 ? (const void*)k_schur_wide<6> : (const void*)k_schur_wide<12>;
-                if (npw > 12) {
-                    ctx->err = "window with too many free camera slots for k_schur_wide";
-                    return LIMO_ERR_INVALID;
-                }
-                wide_lds_bytes = schur_wide_lds_bytes(nfp_gen, nc_gen, nv_gen);
-                HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_gen, hipFuncAttributeMaxDynamicSharedMemorySize, wide_lds_bytes));
-            }
+        // full lists: a shard's are its own workgroups (Schur blocks: span 1), built here; an unsharded batch needs none but the
+        // Schur list, which waits for its first lock-step solve (full_lists)
+        wl.assign(pv.size(), ViewLists());
+        for (size_t i = 0; i < wl.size(); ++i) {
+            WorkLists& f = wl[i].full;
+            f.n_blk = P.n_blk;
+            f.n_lblk = P.n_lblk;
+            f.n_win = P.n_win;
+            if (shard_P == 1) continue;
+            const int r = wl[i].owner = local_shards[i];
+            auto owned = [&](const std::vector<int32_t>& owner, const int32_t** list, int* n) -> int {
+                std::vector<int32_t> v;
+                for (size_t k = 0; k < owner.size(); ++k)
+                    if (owner[k] == r) v.push_back((int32_t)k);
+                *n = (int)v.size();
+                return upload_list(v, list);
+            };
+            if (owned(P.blk_owner, &f.blk, &f.n_blk) || owned(P.lblk_owner, &f.lblk, &f.n_lblk) || build_full_sblk(i)) return LIMO_ERR_RUNTIME;
         }
-        {   // LDS of the window-level kernels: the largest window that still works in LDS (the others: cam_scr_off)
-            int nc_lds = kCamSlots, nf_lds = 1, nv_lds = 1;
-            for (const WinDesc& d : P.win)
-                if (d.cam_scr_off < 0) {
-                    nc_lds = std::max(nc_lds, (int)d.nc);
-                    nf_lds = std::max(nf_lds, (int)d.nf);
-                    nv_lds = std::max(nv_lds, (int)d.n_view);
-                }
-            asm_bytes = cam_assemble_scratch(nc_lds, kBlock, nv_lds) * (int)sizeof(double);
-            solve_bytes = cam_solve_scratch(nc_lds, kBlock, nf_lds) * (int)sizeof(double);  // the compact system: nf <= nc free slots
+        plan = plan_batch(P, {schur_lean_lds_bytes, schur_wide_lds_bytes, lin_lm_lds_bytes(P.Vmax, true), kWideWaves, kTrimMaxSort});
+        if (plan.wide_npw < 0) {
+            ctx->err = "window with too many free camera slots for k_schur_wide";
+            return LIMO_ERR_INVALID;
         }
-        int max_lm = 1;
-        for (const WinDesc& d : P.win) max_lm = std::max(max_lm, (int)d.n_lm);
-        {
-            int np2 = 1;
-            while (np2 < max_lm) np2 <<= 1;
-            trim_bytes = np2 <= kTrimMaxSort ? np2 * 12 + max_lm + 16 : 16;
+        if (plan.any_fast) {
+            schur_fn_plain = schur_kernel(0, plan.plain_tm, plan.plain_wpe);
+            HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_plain, hipFuncAttributeMaxDynamicSharedMemorySize, plan.plain_lds));
+            schur_fn_leangp = schur_kernel(1, plan.gp_tm, plan.gp_wpe);
+            HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_leangp, hipFuncAttributeMaxDynamicSharedMemorySize, plan.leangp_lds));
+            schur_pair_ok = plan.pair_ok && !(std::getenv("KBA_NO_SCHUR_PAIR") && std::atoi(std::getenv("KBA_NO_SCHUR_PAIR")) != 0);
+            if (schur_pair_ok)
+                HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_schur_lean_pair<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(plan.plain_lds, plan.leangp_lds)));
         }
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, asm_bytes));
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_solve, hipFuncAttributeMaxDynamicSharedMemorySize, solve_bytes));
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_trim_select, hipFuncAttributeMaxDynamicSharedMemorySize, trim_bytes));
+        if (plan.any_gen) {
+            schur_fn_gen = schur_kernel(2, plan.wide_npw, 0);
+            HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_gen, hipFuncAttributeMaxDynamicSharedMemorySize, plan.wide_lds));
+        }
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, plan.asm_bytes));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_solve, hipFuncAttributeMaxDynamicSharedMemorySize, plan.solve_bytes));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_trim_select, hipFuncAttributeMaxDynamicSharedMemorySize, plan.trim_bytes));
         for (auto& e : act_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         HIP_TRY(ctx, hipEventCreate(&ev_total_a));
         HIP_TRY(ctx, hipEventCreate(&ev_total_b));
@@ -418,36 +361,35 @@ struct limo_ba_batch : Executor {
             ctx->err = std::string(what) + ": " + hipGetErrorString(e);
         }
     }
+    void note_nccl(ncclResult_t r, const char* what) {
+        if (r != ncclSuccess && rc == LIMO_OK) {
+            rc = LIMO_ERR_RUNTIME;
+            ctx->err = std::string(what) + ": " + ncclGetErrorString(r);
+        }
+    }
 #define LAUNCH_CHECK(what) note(hipGetLastError(), what)
 
     // ---- Executor
+    // The constants of a solve with options `o`: make_consts plus what depends on the batch's sharding alone (fixed at creation).
     // Schur granularity: a wave takes two plain Schur blocks (128 landmarks, 8 tiles) or one ground-plane block.  Fixed
     // (not a function of how many windows are in flight): the partial-slab layout of a window, and with it the order in
     // which its Schur complement is summed, is then the same alone and inside any batch - single-window and batched
     // solves give the same bits.  (Measured at 1024 C2 windows: span 2 is as fast as 4, span 1 costs 2 %.)
     // The spans also decide which slabs of S_part are "plain" (written in part only, kba_kernels.hip:schur_lean_group) - a slab must keep
     // its class for the life of the batch.
-    void set_span() {
-        c.schur_span = shard_P > 1 ? 1 : 2;  // (Schur blocks are cut at shard boundaries)
-        c.schur_span_gp = 1;
-        c.schur_nslab = shard_P > 1 ? shard_P : 0;
-        c.schur_packed = shard_P > 1 ? 1 : 0;
+    SolveConsts consts_for(const limo_ba_options& o) const {
+        SolveConsts k = make_consts(o);
+        const bool sharded = shard_P > 1;
+        k.schur_span = sharded ? 1 : 2;  // (Schur blocks are cut at shard boundaries)
+        k.schur_span_gp = 1;
+        k.schur_nslab = sharded ? shard_P : 0;
+        k.schur_packed = sharded ? 1 : 0;
         // the launch sequences of an unsharded batch (lock-step and streaming) keep the partial slabs of fast-class windows packed
         // (kba_items.hpp:slab_packed_write); a sharded solve reduces tile slabs (slab_reduce_entry), and the one-launch solve, whose
         // own slab sum indexes the tile layout, gets a copy of the constants without it (solve_coop)
-        c.slab_packed = shard_P > 1 ? 0 : 1;
+        k.slab_packed = sharded ? 0 : 1;
+        return k;
     }
-
-    // ---- sharding helpers
-    const int32_t* list_blk(size_t i) const { return shard_P > 1 ? rl[i].blk : (use_wl ? d_wl_blk : nullptr); }
-    const int32_t* list_lblk(size_t i) const { return shard_P > 1 ? rl[i].lblk : (use_wl ? d_wl_lblk : nullptr); }
-    const int32_t* list_sblk(size_t i) const { return shard_P > 1 ? rl[i].sblk : d_wl_sblk; }
-    int count_blk(size_t i) const { return shard_P > 1 ? rl[i].n_blk : n_wl_blk; }
-    int count_lblk(size_t i) const { return shard_P > 1 ? rl[i].n_lblk : n_wl_lblk; }
-    int count_sblk(size_t i) const { return shard_P > 1 ? rl[i].n_sblk : n_wl_sblk; }
-    int count_sblk_plain(size_t i) const { return shard_P > 1 ? rl[i].n_sblk_plain : n_wl_sblk_plain; }
-    int count_sblk_fgp(size_t i) const { return shard_P > 1 ? rl[i].n_sblk_fgp : n_wl_sblk_fgp; }
-    int shard_of(size_t i) const { return shard_P > 1 ? local_shards[i] : 0; }
 
     // Per-iteration exchange (point 1 = A1, 2 = A2, 3 = A, 4 = B; kba_buffers.hpp:exchange_layout): ALL-GATHER of the shards'
     // blocks over the ranks - one call per local slot, normally one shard per rank: ONE ncclAllGather of 41 KB at a C4 window -
@@ -467,11 +409,7 @@ struct limo_ba_batch : Executor {
                 if (ctx->xfn) {
                     host_exchange(blocks[i] + off, d_gather, count, 0);
                 } else {
-                    ncclResult_t r = ncclAllGather(blocks[i] + off, d_gather, count, ncclDouble, (ncclComm_t)ctx->comm, s);
-                    if (r != ncclSuccess && rc == LIMO_OK) {
-                        rc = LIMO_ERR_RUNTIME;
-                        ctx->err = std::string("ncclAllGather: ") + ncclGetErrorString(r);
-                    }
+                    note_nccl(ncclAllGather(blocks[i] + off, d_gather, count, ncclDouble, (ncclComm_t)ctx->comm, s), "ncclAllGather");
                 }
                 for (int q = 0; q < ctx->comm_world; ++q) {
                     hipLaunchKernelGGL(k_unpack, dim3(cdiv((int64_t)count, 256)), dim3(256), 0, s, xl, (const WinDesc*)d_win_orig,
@@ -488,29 +426,24 @@ struct limo_ba_batch : Executor {
     void host_exchange(const double* src, double* dst, size_t count, int kind) {
         hipStream_t s = ctx->stream;
         const size_t n_out = kind == 0 ? (size_t)ctx->comm_world * count : count, need = count + n_out;
-        if (ctx->xhost_cap < need) {
-            if (ctx->xhost) (void)hipHostFree(ctx->xhost);
-            ctx->xhost = nullptr;
-            ctx->xhost_cap = 0;
-            if (hipHostMalloc((void**)&ctx->xhost, sizeof(double) * need) != hipSuccess) {
-                note(hipErrorOutOfMemory, "hipHostMalloc(exchange staging)");
-                std::vector<double> z(need, 0.0);  // (the peers are still met: see below)
-                ctx->xfn(z.data(), z.data() + count, (long long)count, kind, ctx->xuser);
-                return;
-            }
-            ctx->xhost_cap = need;
+        if (ctx->xhost.ensure(sizeof(double) * need) != hipSuccess) {
+            note(hipErrorOutOfMemory, "hipHostMalloc(exchange staging)");
+            std::vector<double> z(need, 0.0);  // (the peers are still met: see below)
+            ctx->xfn(z.data(), z.data() + count, (long long)count, kind, ctx->xuser);
+            return;
         }
+        double* const xhost = static_cast<double*>(ctx->xhost.p);
         // The transport is a COLLECTIVE: a rank that skipped it after a local error would leave its peers blocked in it for ever.  So
         // the call is made in every case - after an error with a zeroed contribution - and only the device copies are skipped; the
         // solve of this rank ends with LIMO_ERR_RUNTIME, the peers' solves end (with a result that misses this rank's share).
         if (rc == LIMO_OK) {
-            note(hipMemcpyAsync(ctx->xhost, src, sizeof(double) * count, hipMemcpyDeviceToHost, s), "exchange: device -> host");
+            note(hipMemcpyAsync(xhost, src, sizeof(double) * count, hipMemcpyDeviceToHost, s), "exchange: device -> host");
             note(hipStreamSynchronize(s), "exchange: sync");
         }
-        if (rc != LIMO_OK) std::memset(ctx->xhost, 0, sizeof(double) * count);
-        ctx->xfn(ctx->xhost, ctx->xhost + count, (long long)count, kind, ctx->xuser);
+        if (rc != LIMO_OK) std::memset(xhost, 0, sizeof(double) * count);
+        ctx->xfn(xhost, xhost + count, (long long)count, kind, ctx->xuser);
         if (rc != LIMO_OK) return;
-        note(hipMemcpyAsync(dst, ctx->xhost + count, sizeof(double) * n_out, hipMemcpyHostToDevice, s), "exchange: host -> device");
+        note(hipMemcpyAsync(dst, xhost + count, sizeof(double) * n_out, hipMemcpyHostToDevice, s), "exchange: host -> device");
         note(hipStreamSynchronize(s), "exchange: sync");  // (the staging buffer is reused by the next step)
     }
     // Trimming round: per-landmark residual maxima, one owner per entry and zero elsewhere - an exact sum in any order.
@@ -525,49 +458,23 @@ struct limo_ba_batch : Executor {
         if (!shard_virtual && ctx->xfn) {
             host_exchange(trims[0], trims[0], (size_t)n, 1);
         } else if (!shard_virtual) {
-            ncclResult_t r = ncclAllReduce(trims[0], trims[0], (size_t)n, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, s);
-            if (r != ncclSuccess && rc == LIMO_OK) {
-                rc = LIMO_ERR_RUNTIME;
-                ctx->err = std::string("ncclAllReduce: ") + ncclGetErrorString(r);
-            }
+            note_nccl(ncclAllReduce(trims[0], trims[0], (size_t)n, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, s), "ncclAllReduce");
         }
         ++n_exchanges;
         exchange_bytes += n * (int64_t)sizeof(double);
     }
 
     void full_lists() {
-        use_wl = false;
-        n_wl_blk = P.n_blk;
-        n_wl_lblk = P.n_lblk;
-        n_wl_win = P.n_win;
-        listed = P.n_win;
-        set_span();
-        FullSblk& fl = wl_sblk_full;
-        if (!fl.d) {
-            std::vector<int32_t> v;
-            build_sblk_list(nullptr, c.schur_span, c.schur_span_gp, -1, v, fl.n_plain, fl.n_fgp);
-            fl.n = (int)v.size();
-            if (dmalloc((void**)&fl.d, sizeof(int32_t) * std::max<size_t>(1, v.size())) == LIMO_OK && !v.empty())
-                note(hipMemcpy(fl.d, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice), "upload Schur worklist");
-        }
-        d_wl_sblk = fl.d;
-        n_wl_sblk = fl.n;
-        n_wl_sblk_plain = fl.n_plain;
-        n_wl_sblk_fgp = fl.n_fgp;
-        for (RankLists& r : rl) {
-            r.n_sblk_plain = r.n_full_sblk_plain;
-            r.n_sblk_fgp = r.n_full_sblk_fgp;
-            r.blk = r.full_blk;
-            r.lblk = r.full_lblk;
-            r.sblk = r.full_sblk;
-            r.n_blk = r.n_full_blk;
-            r.n_lblk = r.n_full_lblk;
-            r.n_sblk = r.n_full_sblk;
+        for (size_t i = 0; i < wl.size(); ++i) {
+            if (!wl[i].full.sblk && build_full_sblk(i) != LIMO_OK && rc == LIMO_OK) rc = LIMO_ERR_RUNTIME;
+            wl[i].cur = wl[i].full;
         }
     }
 
-    // Rebuild the worklists from the windows that are active right now (synchronises the stream).
+    // Rebuild the worklists from the windows that are active right now (synchronises the stream).  Unsharded batches only: a sharded
+    // batch has one window (batch_create_impl), and active_count() asks for eight.
     void rebatch() {
+        if (shard_P > 1) return;
         hipStream_t s = ctx->stream;
         hipLaunchKernelGGL(k_export_active, dim3(cdiv(P.n_win, 256)), dim3(256), 0, s, bv, d_flags);
         note(hipMemcpyAsync(h_flags, d_flags, sizeof(int32_t) * P.n_win, hipMemcpyDeviceToHost, s), "memcpy flags");
@@ -581,48 +488,18 @@ struct limo_ba_batch : Executor {
             for (int i = 0; i < d.n_blk; ++i) wb.push_back(d.blk0 + i);
             for (int i = 0; i < d.n_lblk; ++i) wlb.push_back(d.lblk0 + i);
         }
-        set_span();
-        build_sblk_list(&ww, c.schur_span, c.schur_span_gp, -1, wsb, n_wl_sblk_plain, n_wl_sblk_fgp);
-        auto up = [&](int32_t* dst, const std::vector<int32_t>& v) {
+        WorkLists& a = wl[0].cur;
+        build_sblk_list(P, &ww, c.schur_span, c.schur_span_gp, -1, wsb, a.n_sblk_plain, a.n_sblk_fgp);
+        auto up = [&](int32_t* dst, const std::vector<int32_t>& v, const int32_t*& list, int& n) {
             if (!v.empty()) note(hipMemcpyAsync(dst, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, s), "upload worklist");
+            list = dst;
+            n = (int)v.size();
         };
-        up(d_wl_blk, wb);
-        up(d_wl_lblk, wlb);
-        d_wl_sblk = d_wl_sblk_part;
-        up(d_wl_sblk, wsb);
-        up(d_wl_win, ww);
-        std::vector<std::vector<int32_t>> keep;  // host lists of the shards, alive until the sync below
-        for (size_t i = 0; i < rl.size(); ++i) {
-            const int r = local_shards[i];
-            std::vector<int32_t> b1, b2, b3;
-            for (int w : ww) {
-                const WinDesc& d = P.win[w];
-                for (int k = d.blk0; k < d.blk0 + d.n_blk; ++k)
-                    if (P.blk_owner[k] == r) b1.push_back(k);
-                for (int k = d.lblk0; k < d.lblk0 + d.n_lblk; ++k)
-                    if (P.lblk_owner[k] == r) b2.push_back(k);
-            }
-            build_sblk_list(&ww, 1, 1, r, b3, rl[i].n_sblk_plain, rl[i].n_sblk_fgp);
-            up(rl[i].act_blk, b1);
-            up(rl[i].act_lblk, b2);
-            up(rl[i].act_sblk, b3);
-            rl[i].blk = rl[i].act_blk;
-            rl[i].lblk = rl[i].act_lblk;
-            rl[i].sblk = rl[i].act_sblk;
-            rl[i].n_blk = (int)b1.size();
-            rl[i].n_lblk = (int)b2.size();
-            rl[i].n_sblk = (int)b3.size();
-            keep.push_back(std::move(b1));
-            keep.push_back(std::move(b2));
-            keep.push_back(std::move(b3));
-        }
+        up(d_act_blk, wb, a.blk, a.n_blk);
+        up(d_act_lblk, wlb, a.lblk, a.n_lblk);
+        up(d_act_sblk, wsb, a.sblk, a.n_sblk);
+        up(d_act_win, ww, a.win, a.n_win);
         note(hipStreamSynchronize(s), "sync worklists");  // the host vectors go out of scope
-        use_wl = true;
-        n_wl_blk = (int)wb.size();
-        n_wl_lblk = (int)wlb.size();
-        n_wl_sblk = (int)wsb.size();
-        n_wl_win = (int)ww.size();
-        listed = n_wl_win;
     }
 
     // k_lin_lm<true> (the default since round 6): four waves per SIMD, the window's view constants, the landmark block's running sums and
@@ -683,16 +560,16 @@ struct limo_ba_batch : Executor {
             // ground-plane rows first: the landmark pass adds them to the landmark blocks
             EventPair* ep = timed(LIMO_KERNEL_LINEARIZE);
             for (size_t i = 0; i < pv.size(); ++i)
-                if (count_lblk(i)) {
-                    launch_lin_lm(count_lblk(i), s, pv[i], list_lblk(i));
+                if (wl[i].cur.n_lblk) {
+                    launch_lin_lm(wl[i].cur.n_lblk, s, pv[i], wl[i].cur.lblk);
                     LAUNCH_CHECK("k_lin_lm");
                 }
             if (ep) note(hipEventRecord(ep->b, s), "hipEventRecord");
         }
         if (shard_P > 1) {
             for (size_t i = 0; i < pv.size(); ++i)
-                if (n_wl_win) {
-                    hipLaunchKernelGGL(k_shard_reduce, dim3(n_wl_win), dim3(kBlock), 0, s, pv[i], use_wl ? (const int32_t*)d_wl_win : (const int32_t*)nullptr, shard_of(i), 0);
+                if (wl[i].cur.n_win) {
+                    hipLaunchKernelGGL(k_shard_reduce, dim3(wl[i].cur.n_win), dim3(kBlock), 0, s, pv[i], wl[i].cur.win, local_shards[i], 0);
                     LAUNCH_CHECK("k_shard_reduce");
                 }
             // Sharded: the camera assembly only has to come before the Schur complement when it defines the Jacobi scale (the
@@ -715,7 +592,8 @@ struct limo_ba_batch : Executor {
         BatchView bvs = bv;
         bvs.n_active = bv.n_active + 2 * slot;
         bvs.n_active_host = d_h_active + slot;
-        if (n_wl_win) hipLaunchKernelGGL(k_cam_assemble, dim3(n_wl_win), dim3(kBlock), asm_bytes, s, bvs, c, use_wl ? d_wl_win : nullptr);
+        const WorkLists& a = wl[0].cur;
+        if (a.n_win) hipLaunchKernelGGL(k_cam_assemble, dim3(a.n_win), dim3(kBlock), plan.asm_bytes, s, bvs, c, a.win);
         LAUNCH_CHECK("k_cam_assemble");
         note(hipEventRecord(act_ev[slot], s), "record n_active");
     }
@@ -729,7 +607,7 @@ struct limo_ba_batch : Executor {
         const int slot = (cur - 1) & 3;
         note(hipEventSynchronize(act_ev[slot]), "sync n_active");
         if (rc != LIMO_OK) return 0;
-        const int a = h_active[slot];
+        const int a = h_active[slot], listed = wl[0].cur.n_win;
         static const bool trace = std::getenv("KBA_TRACE_ACTIVE") != nullptr;  // profiling aid
         if (trace) std::fprintf(stderr, "[kba] iteration %d: active %d, listed %d, span %d\n", cur - 1, a, listed, c.schur_span);
         // re-batch when at most half of the listed windows still iterate (and the list is worth shrinking)
@@ -749,47 +627,54 @@ struct limo_ba_batch : Executor {
         LAUNCH_CHECK("k_expire");
     }
 
+    // The Schur kernels of one view over its three lists, in this order: both fast-class lists in ONE launch where the caller allows
+    // the pair kernel (kba_kernels.hip:k_schur_lean_pair), else plain groups, then ground-plane groups; then the generic windows.
+    void launch_schur(const BatchView& v, const int32_t* wl_plain, int n_plain, const int32_t* wl_fgp, int n_fgp, const int32_t* wl_gen, int n_gen, bool pair,
+                      hipStream_t s) {
+        int span = c.schur_span, span_gp = c.schur_span_gp, packed = c.slab_packed;
+        if (pair) {
+            void* args[] = {(void*)&v, (void*)&wl_plain, (void*)&n_plain, (void*)&wl_fgp, (void*)&span, (void*)&span_gp, (void*)&packed};
+            note(hipLaunchKernel((const void*)k_schur_lean_pair<2, 3>, dim3(n_plain + n_fgp), dim3(64), args, std::max(plan.plain_lds, plan.leangp_lds), s),
+                 "launch k_schur_lean_pair");
+        }
+        if (!pair && n_plain) {
+            void* args[] = {(void*)&v, (void*)&wl_plain, (void*)&span, (void*)&span_gp, (void*)&packed};
+            note(hipLaunchKernel(schur_fn_plain, dim3(n_plain), dim3(64), args, plan.plain_lds, s), "launch k_schur_lean");
+        }
+        if (!pair && n_fgp) {
+            void* args[] = {(void*)&v, (void*)&wl_fgp, (void*)&span, (void*)&span_gp, (void*)&packed};
+            note(hipLaunchKernel(schur_fn_leangp, dim3(n_fgp), dim3(64), args, plan.leangp_lds, s), "launch k_schur_lean (gp)");
+        }
+        if (n_gen) {
+            void* args[] = {(void*)&v, (void*)&wl_gen, (void*)&span, (void*)&span_gp};
+            note(hipLaunchKernel(schur_fn_gen, dim3(n_gen), dim3(64 * kWideWaves), args, plan.wide_lds, s), "launch k_schur_wide");
+        }
+    }
+
     void step() override {
         hipStream_t s = ctx->stream;
         if (c.slab_packed) spart_has_packed = true;
+        const WorkLists& a = wl[0].cur;  // (the window list is the same for every view)
         for (size_t i = 0; i < pv.size(); ++i)
-            if (count_lblk(i)) {
-                hipLaunchKernelGGL(k_lm_damp, dim3(count_lblk(i)), dim3(kBlock), 0, s, pv[i], c, list_lblk(i));
+            if (wl[i].cur.n_lblk) {
+                hipLaunchKernelGGL(k_lm_damp, dim3(wl[i].cur.n_lblk), dim3(kBlock), 0, s, pv[i], c, wl[i].cur.lblk);
                 LAUNCH_CHECK("k_lm_damp");
             }
         {
             EventPair* ep = timed(LIMO_KERNEL_SCHUR);
             for (size_t i = 0; i < pv.size(); ++i) {
-                int n_plain = count_sblk_plain(i), n_fgp = count_sblk_fgp(i);
-                const int n_gen = count_sblk(i) - n_plain - n_fgp;
-                int span = c.schur_span, span_gp = c.schur_span_gp, packed = c.slab_packed;
-                const int32_t* wlp = list_sblk(i);
-                if (n_plain) {
-                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
-                    note(hipLaunchKernel(schur_fn_plain, dim3(n_plain), dim3(64), args, plain_lds_bytes, s), "launch k_schur_lean");
-                    LAUNCH_CHECK("k_schur_lean");
-                    wlp += n_plain;
-                }
-                if (n_fgp) {
-                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
-                    note(hipLaunchKernel(schur_fn_leangp, dim3(n_fgp), dim3(64), args, leangp_lds_bytes, s), "launch k_schur_lean (gp)");
-                    LAUNCH_CHECK("k_schur_lean (gp)");
-                    wlp += n_fgp;
-                }
-                if (n_gen) {
-                    void* args[] = {(void*)&pv[i], (void*)&wlp, (void*)&span, (void*)&span_gp};
-                    note(hipLaunchKernel(schur_fn_gen, dim3(n_gen), dim3(64 * kWideWaves), args, wide_lds_bytes, s), "launch k_schur_wide");
-                    LAUNCH_CHECK("k_schur_wide");
-                }
+                const WorkLists& l = wl[i].cur;
+                launch_schur(pv[i], l.sblk, l.n_sblk_plain, l.sblk + l.n_sblk_plain, l.n_sblk_fgp, l.sblk + l.n_sblk_plain + l.n_sblk_fgp,
+                             l.n_sblk - l.n_sblk_plain - l.n_sblk_fgp, false, s);
+                LAUNCH_CHECK("Schur kernels");
             }
             if (ep) note(hipEventRecord(ep->b, s), "hipEventRecord");
         }
         if (shard_P > 1) {
-            if (n_wl_win)
+            if (a.n_win)
                 for (size_t i = 0; i < pv.size(); ++i) {
-                    const int32_t* wlw = use_wl ? (const int32_t*)d_wl_win : (const int32_t*)nullptr;
-                    hipLaunchKernelGGL(k_shard_reduce, dim3(n_wl_win), dim3(kBlock), 0, s, pv[i], wlw, shard_of(i), 1);
-                    hipLaunchKernelGGL(k_slab_reduce, dim3(n_wl_win, 8), dim3(kBlock), 0, s, pv[i], wlw, shard_P);
+                    hipLaunchKernelGGL(k_shard_reduce, dim3(a.n_win), dim3(kBlock), 0, s, pv[i], a.win, local_shards[i], 1);
+                    hipLaunchKernelGGL(k_slab_reduce, dim3(a.n_win, 8), dim3(kBlock), 0, s, pv[i], a.win, shard_P);
                     LAUNCH_CHECK("k_slab_reduce");
                 }
             if (assemble_pending) {  // ONE exchange: camera-side sums + ground-plane blocks + scalars + [S | rhs]
@@ -800,21 +685,21 @@ struct limo_ba_batch : Executor {
                 exchange(2);
             }
         }
-        if (n_wl_win) hipLaunchKernelGGL(k_cam_solve, dim3(n_wl_win), dim3(kBlock), solve_bytes, s, bv, c, use_wl ? d_wl_win : nullptr);
+        if (a.n_win) hipLaunchKernelGGL(k_cam_solve, dim3(a.n_win), dim3(kBlock), plan.solve_bytes, s, bv, c, a.win);
         LAUNCH_CHECK("k_cam_solve");
         for (size_t i = 0; i < pv.size(); ++i) {
-            if (count_lblk(i)) {
-                hipLaunchKernelGGL(k_backsub, dim3(count_lblk(i)), dim3(kBlock), 0, s, pv[i], c, list_lblk(i));
+            if (wl[i].cur.n_lblk) {
+                hipLaunchKernelGGL(k_backsub, dim3(wl[i].cur.n_lblk), dim3(kBlock), 0, s, pv[i], c, wl[i].cur.lblk);
                 LAUNCH_CHECK("k_backsub");
             }
         }
-        if (shard_P > 1 && n_wl_win)
+        if (shard_P > 1 && a.n_win)
             for (size_t i = 0; i < pv.size(); ++i) {
-                hipLaunchKernelGGL(k_shard_reduce, dim3(n_wl_win), dim3(kBlock), 0, s, pv[i], use_wl ? (const int32_t*)d_wl_win : (const int32_t*)nullptr, shard_of(i), 2);
+                hipLaunchKernelGGL(k_shard_reduce, dim3(a.n_win), dim3(kBlock), 0, s, pv[i], a.win, local_shards[i], 2);
                 LAUNCH_CHECK("k_shard_reduce");
             }
         exchange(4);
-        if (n_wl_win) hipLaunchKernelGGL(k_step_decide, dim3(n_wl_win), dim3(64), 0, s, bv, c, use_wl ? d_wl_win : nullptr);
+        if (a.n_win) hipLaunchKernelGGL(k_step_decide, dim3(a.n_win), dim3(64), 0, s, bv, c, a.win);
         LAUNCH_CHECK("k_step_decide");
         hipLaunchKernelGGL(k_accept, dim3(cdiv((int64_t)P.TK + P.TL, 256)), dim3(256), 0, s, bv);
         LAUNCH_CHECK("k_accept");
@@ -826,22 +711,20 @@ struct limo_ba_batch : Executor {
         for (const WinDesc& d : P.win) any = any || d.do_trim;
         if (!any) return;
         for (size_t i = 0; i < pv.size(); ++i) {
-            const int nb = shard_P > 1 ? rl[i].n_full_blk : P.n_blk;
-            if (nb) {
-                hipLaunchKernelGGL(k_trim_residual, dim3(nb), dim3(kBlock), 0, s, pv[i], d_plane_rep, d_plane_dep,
-                                   shard_P > 1 ? (const int32_t*)rl[i].full_blk : (const int32_t*)nullptr);
+            if (wl[i].full.n_blk) {
+                hipLaunchKernelGGL(k_trim_residual, dim3(wl[i].full.n_blk), dim3(kBlock), 0, s, pv[i], d_plane_rep, d_plane_dep, wl[i].full.blk);
                 LAUNCH_CHECK("k_trim_residual");
             }
         }
         if (P.TL) {
             for (size_t i = 0; i < pv.size(); ++i) {
                 hipLaunchKernelGGL(k_trim_max, dim3(cdiv(P.TL, 256)), dim3(256), 0, s, pv[i], (const double*)d_plane_rep,
-                                   (const double*)d_plane_dep, shard_of(i), shard_P);
+                                   (const double*)d_plane_dep, local_shards[i], shard_P);
                 LAUNCH_CHECK("k_trim_max");
             }
         }
         exchange_trim();
-        hipLaunchKernelGGL(k_trim_select, dim3(P.n_win), dim3(kBlock), trim_bytes, s, bv, c);
+        hipLaunchKernelGGL(k_trim_select, dim3(P.n_win), dim3(kBlock), plan.trim_bytes, s, bv, c);
         LAUNCH_CHECK("k_trim_select");
     }
 
@@ -886,7 +769,6 @@ struct limo_ba_batch : Executor {
         // windows in flight: a quarter of the batch (so that the ramp-down at the end of the batch is a small part of the
         // solve), at least 1024 (a round of fewer windows is bound by the latency of its window-level kernels)
         n_slots = stream_slots();
-        set_span();
         int mx[SL_COUNT] = {0};
         for (const WinDesc& d : P.win) {
             const int plg = (d.n_sblk_plain + c.schur_span - 1) / c.schur_span, gpg = (d.n_sblk - d.n_sblk_plain + c.schur_span_gp - 1) / c.schur_span_gp;
@@ -971,7 +853,7 @@ struct limo_ba_batch : Executor {
         note(hipStreamWaitEvent(g.trim_stream, g.sched_ev, 0), "wait sched");
         if (cap[SL_TBLK]) hipLaunchKernelGGL(k_trim_residual, dim3(cap[SL_TBLK]), dim3(kBlock), 0, g.trim_stream, sv, d_plane_rep, d_plane_dep, L(SL_TBLK));
         if (cap[SL_TLBLK]) hipLaunchKernelGGL(k_trim_max, dim3(cap[SL_TLBLK]), dim3(kBlock), 0, g.trim_stream, sv, (const double*)d_plane_rep, (const double*)d_plane_dep, 0, 1);
-        hipLaunchKernelGGL(k_trim_select, dim3(cap[SL_TWIN]), dim3(kBlock), trim_bytes, g.trim_stream, sv, c);
+        hipLaunchKernelGGL(k_trim_select, dim3(cap[SL_TWIN]), dim3(kBlock), plan.trim_bytes, g.trim_stream, sv, c);
         LAUNCH_CHECK("trim kernels");
         note(hipEventRecord(g.trim_ev, g.trim_stream), "record trim");
         // ---- linearisation of the windows that need it (their per-view constants: k_sched_fill above)
@@ -980,39 +862,17 @@ struct limo_ba_batch : Executor {
             if (cap[SL_LBLK]) launch_lin_lm(cap[SL_LBLK], s, sv, L(SL_LBLK));
             if (ep) note(hipEventRecord(ep->b, s), "hipEventRecord");
         }
-        hipLaunchKernelGGL(k_cam_assemble, dim3(cap[SL_WIN]), dim3(kBlock), asm_bytes, s, sv, c, L(SL_WIN));
+        hipLaunchKernelGGL(k_cam_assemble, dim3(cap[SL_WIN]), dim3(kBlock), plan.asm_bytes, s, sv, c, L(SL_WIN));
         LAUNCH_CHECK("linearisation kernels");
         // ---- trust-region step of the windows that iterate
         {
             EventPair* ep = time_kernels ? timed(LIMO_KERNEL_SCHUR, s) : nullptr;
-            int span = c.schur_span, span_gp = c.schur_span_gp, packed = c.slab_packed;
             // few windows in flight (the batch drains): both fast-class lists in one launch (kba_kernels.hip:k_schur_lean_pair)
             const bool pair = schur_pair_ok && bound <= kSchurPairBound && cap[SL_SPLAIN] && cap[SL_SFGP];
-            if (pair) {
-                const int32_t *wlp = L(SL_SPLAIN), *wlg = L(SL_SFGP);
-                int n_plain_cap = cap[SL_SPLAIN];
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&n_plain_cap, (void*)&wlg, (void*)&span, (void*)&span_gp, (void*)&packed};
-                note(hipLaunchKernel((const void*)k_schur_lean_pair<2, 3>, dim3(cap[SL_SPLAIN] + cap[SL_SFGP]), dim3(64), args, std::max(plain_lds_bytes, leangp_lds_bytes), s),
-                     "launch k_schur_lean_pair");
-            }
-            if (!pair && cap[SL_SPLAIN]) {
-                const int32_t* wlp = L(SL_SPLAIN);
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
-                note(hipLaunchKernel(schur_fn_plain, dim3(cap[SL_SPLAIN]), dim3(64), args, plain_lds_bytes, s), "launch k_schur_lean");
-            }
-            if (!pair && cap[SL_SFGP]) {
-                const int32_t* wlp = L(SL_SFGP);
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp, (void*)&packed};
-                note(hipLaunchKernel(schur_fn_leangp, dim3(cap[SL_SFGP]), dim3(64), args, leangp_lds_bytes, s), "launch k_schur_lean (gp)");
-            }
-            if (cap[SL_SGEN]) {
-                const int32_t* wlp = L(SL_SGEN);
-                void* args[] = {(void*)&sv, (void*)&wlp, (void*)&span, (void*)&span_gp};
-                note(hipLaunchKernel(schur_fn_gen, dim3(cap[SL_SGEN]), dim3(64 * kWideWaves), args, wide_lds_bytes, s), "launch k_schur_wide");
-            }
+            launch_schur(sv, L(SL_SPLAIN), cap[SL_SPLAIN], L(SL_SFGP), cap[SL_SFGP], L(SL_SGEN), cap[SL_SGEN], pair, s);
             if (ep) note(hipEventRecord(ep->b, s), "hipEventRecord");
         }
-        hipLaunchKernelGGL(k_cam_solve, dim3(cap[SL_WIN]), dim3(kBlock), solve_bytes, s, sv, c, L(SL_WIN));
+        hipLaunchKernelGGL(k_cam_solve, dim3(cap[SL_WIN]), dim3(kBlock), plan.solve_bytes, s, sv, c, L(SL_WIN));
         if (cap[SL_LBLK]) hipLaunchKernelGGL(k_backsub, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
         hipLaunchKernelGGL(k_step_decide, dim3(cap[SL_WIN]), dim3(64), 0, s, sv, c, L(SL_WIN));
         if (cap[SL_LBLK])  // accepted landmarks / re-damping in one launch (kba_kernels.hip:k_after_step)
@@ -1033,13 +893,12 @@ struct limo_ba_batch : Executor {
             if (d.n_lblk > kWgMaxLblk) return false;
         return wg_lds_bytes() <= kCamLdsCapBytes;
     }
-    int wg_lds_bytes() const { return std::max(std::max(asm_bytes, solve_bytes), std::max(trim_bytes, lin_lm_lds_bytes(P.Vmax, true))); }
+    int wg_lds_bytes() const { return plan.onelaunch_lds; }
+    long long cap_ticks() const { return opts.max_solver_time_sec > 0.0 ? std::max(1ll, (long long)(opts.max_solver_time_sec * 1e8)) : 0ll; }
     void solve_wg() {
         const int lds = wg_lds_bytes();
-        set_span();
         note(hipFuncSetAttribute((const void*)k_solve_wg, hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute(k_solve_wg)");
-        const long long cap_ticks = opts.max_solver_time_sec > 0.0 ? std::max(1ll, (long long)(opts.max_solver_time_sec * 1e8)) : 0ll;
-        hipLaunchKernelGGL(k_solve_wg, dim3(P.n_win), dim3(kBlock), lds, ctx->stream, bv, c, cap_ticks, d_plane_rep, d_plane_dep);
+        hipLaunchKernelGGL(k_solve_wg, dim3(P.n_win), dim3(kBlock), lds, ctx->stream, bv, c, cap_ticks(), d_plane_rep, d_plane_dep);
         LAUNCH_CHECK("k_solve_wg");
     }
 
@@ -1054,15 +913,11 @@ struct limo_ba_batch : Executor {
     double* d_coop_red = nullptr;
     bool coop_launched = false;
     int coop_G = 0, coop_xcd = 1;
-    int coop_lds_bytes() const {
-        const int wave = (std::max(plain_lds_bytes, leangp_lds_bytes) + 15) / 16 * 16;
-        return std::max(std::max(std::max(asm_bytes, solve_bytes), std::max(trim_bytes, lin_lm_lds_bytes(P.Vmax, true))), (kBlock / 64) * wave);
-    }
+    int coop_lds_bytes() const { return std::max(plan.onelaunch_lds, (kBlock / 64) * plan.schur_wave_lds); }
     bool coop_solve_applies() {
         if (shard_P != 1 || P.evaluate_only || P.n_win < 1) return false;
         if (const char* e = std::getenv("KBA_NO_COOP_SOLVE"))
             if (std::atoi(e) != 0) return false;
-        set_span();
         int G = 1;
         for (const WinDesc& d : P.win) {
             if (!d.schur_fast || d.cam_scr_off >= 0 || d.nf_pad * d.nf_pad > kCoopRedStride) return false;
@@ -1101,10 +956,10 @@ struct limo_ba_batch : Executor {
         cp.G = coop_G;
         cp.xcd_map = coop_xcd;
         const int coop_grid = coop_xcd ? 8 * coop_G * (((int)P.n_win + 7) / 8) : (int)P.n_win * coop_G;
-        cp.vp = schur_vp;
-        cp.vg = schur_vg;
-        cp.schur_lds = (std::max(plain_lds_bytes, leangp_lds_bytes) + 15) / 16 * 16 / (int)sizeof(double);
-        cp.cap_ticks = opts.max_solver_time_sec > 0.0 ? std::max(1ll, (long long)(opts.max_solver_time_sec * 1e8)) : 0ll;
+        cp.vp = plan.plain_tm;
+        cp.vg = plan.gp_tm;
+        cp.schur_lds = plan.schur_wave_lds / (int)sizeof(double);
+        cp.cap_ticks = cap_ticks();
         // barrier timeout in ticks of the 100 MHz constant clock (read per call; KBA_COOP_TIMEOUT_MS=0: give up at the first wait -
         // how the tests reach the recovery path of limo_ba_batch_solve)
         // default 50 ms (the whole call is ~5 ms; the longest phase between two barriers - the quantile trimming - well under 1 ms):
@@ -1148,7 +1003,6 @@ struct limo_ba_batch : Executor {
         int n_groups = stream_slots() >= 4096 ? 3 : P.n_win >= 512 ? 2 : 1;
         if (const char* e = std::getenv("KBA_GROUPS")) n_groups = std::max(1, std::min(4, std::atoi(e)));
         if (stream_setup(n_groups) != LIMO_OK) return LIMO_ERR_RUNTIME;
-        set_span();
         if (c.slab_packed) spart_has_packed = true;
         hipStream_t s0 = ctx->stream;
         groups[0].stream = s0;
@@ -1311,10 +1165,13 @@ static int batch_create_impl(limo_ctx* ctx, int32_t n, const limo_ba_window* win
         o = *opts;
     else
         limo_ba_default_options(&o);
-    limo_ba_batch* b = new limo_ba_batch();
+    if (po.shards > 1 && n != 1) {  // (what the lock-step solve relies on: a sharded batch never re-batches, limo_ba_batch::rebatch)
+        ctx->err = "a landmark-sharded batch holds exactly one window";
+        return LIMO_ERR_INVALID;
+    }
+    std::unique_ptr<limo_ba_batch> b(new limo_ba_batch());
     b->ctx = ctx;
     b->opts = o;
-    b->c = make_consts(o);
     const auto t_c0 = std::chrono::steady_clock::now();
     // Large batches pack into the context's pinned arena when no other live batch holds it (limo_ctx.hpp:pack_arena).  The first large
     // batch of a context only measures what it would have needed; the arena is made right behind its packing, for the next one.
@@ -1323,35 +1180,35 @@ static int batch_create_impl(limo_ctx* ctx, int32_t n, const limo_ba_window* win
     auto arena_resize = [&](size_t wanted) {  // (only while no batch holds the arena)
         const size_t step = size_t(64) << 20;
         const size_t cap = std::min(limo_ctx::kPackArenaMax, (wanted + wanted / 8 + step - 1) / step * step);
-        if (cap <= ctx->pack_arena_cap) return;
-        if (ctx->pack_arena) {
-            pack_arena_register(ctx->pack_arena, ctx->pack_arena_cap, false);
-            (void)hipHostFree(ctx->pack_arena);
-            ctx->pack_arena = nullptr;
-            ctx->pack_arena_cap = 0;
-        }
-        if (hipHostMalloc(&ctx->pack_arena, cap) == hipSuccess) {
-            ctx->pack_arena_cap = cap;
-            pack_arena_register(ctx->pack_arena, cap, true);
-        } else {
+        if (cap <= ctx->pack_arena.cap) return;
+        if (ctx->pack_arena.p) pack_arena_register(ctx->pack_arena.p, ctx->pack_arena.cap, false);
+        if (ctx->pack_arena.ensure(cap) == hipSuccess)
+            pack_arena_register(ctx->pack_arena.p, cap, true);
+        else
             (void)hipGetLastError();
-            ctx->pack_arena = nullptr;
-        }
     };
     if (lending) {
-        if (ctx->pack_arena && ctx->pack_arena_wanted > ctx->pack_arena_cap) arena_resize(ctx->pack_arena_wanted);  // the last batch did not fit
-        lend.base = static_cast<char*>(ctx->pack_arena);
-        lend.cap = ctx->pack_arena_cap;
-        pack_arena_lend(&lend);
+        if (ctx->pack_arena.p && ctx->pack_arena_wanted > ctx->pack_arena.cap) arena_resize(ctx->pack_arena_wanted);  // the last batch did not fit
+        lend.base = static_cast<char*>(ctx->pack_arena.p);
+        lend.cap = ctx->pack_arena.cap;
     }
-    int rc = pack_windows(n, windows, o, po, b->P, ctx->err);
-    pack_arena_lend(nullptr);
+    int rc = LIMO_OK;
+    try {  // (the pack's host threads hand their exceptions to the caller, kba_pack.cpp:PackPool - none may cross the C ABI)
+        PackArenaLend loan(lending ? &lend : nullptr);
+        rc = pack_windows(n, windows, o, po, b->P, ctx->err);
+    } catch (const std::bad_alloc&) {
+        ctx->err = "pack_windows: out of host memory";
+        return LIMO_ERR_RUNTIME;
+    } catch (const std::exception& e) {
+        ctx->err = std::string("pack_windows: ") + e.what();
+        return LIMO_ERR_RUNTIME;
+    }
     if (lending) {
         ctx->pack_arena_wanted = std::max(ctx->pack_arena_wanted, lend.wanted);
         if (lend.used > 0) {
             ctx->pack_arena_busy = true;
             b->holds_pack_arena = true;
-        } else if (!ctx->pack_arena && lend.wanted > 0) {
+        } else if (!ctx->pack_arena.p && lend.wanted > 0) {
             arena_resize(lend.wanted);  // the first large batch of the context: ready for the next one
         }
     }
@@ -1368,19 +1225,18 @@ static int batch_create_impl(limo_ctx* ctx, int32_t n, const limo_ba_window* win
             if (r % world == me) b->local_shards.push_back(r);
         if (b->local_shards.size() > 8) {
             ctx->err = "at most 8 shards per GPU";
-            delete b;
             return LIMO_ERR_INVALID;
         }
+    } else {
+        b->local_shards.push_back(0);
     }
+    b->c = b->consts_for(o);
     if (rc == LIMO_OK) rc = b->upload();
     if (std::getenv("KBA_PACK_TRACE"))
         std::fprintf(stderr, "[kba] create: pack %.1f ms, upload %.1f ms\n", std::chrono::duration<double, std::milli>(t_c1 - t_c0).count(),
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_c1).count());
-    if (rc != LIMO_OK) {
-        delete b;
-        return rc;
-    }
-    *out = b;
+    if (rc != LIMO_OK) return rc;
+    *out = b.release();
     return LIMO_OK;
 }
 
@@ -1407,7 +1263,7 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
             }
         }
         b->opts = *opts;
-        b->c = make_consts(*opts);
+        b->c = b->consts_for(*opts);
     }
     b->rc = LIMO_OK;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1463,11 +1319,9 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
             b->host_exchange(b->d_lm_tmp, b->bv.lm, (size_t)3 * b->P.TL, 1);
             if (b->rc != LIMO_OK) return b->rc;
         } else {
-            ncclResult_t r = ncclAllReduce(b->d_lm_tmp, b->bv.lm, (size_t)3 * b->P.TL, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, ctx->stream);
-            if (r != ncclSuccess) {
-                ctx->err = std::string("ncclAllReduce(landmarks): ") + ncclGetErrorString(r);
-                return LIMO_ERR_RUNTIME;
-            }
+            const ncclResult_t r = ncclAllReduce(b->d_lm_tmp, b->bv.lm, (size_t)3 * b->P.TL, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, ctx->stream);
+            b->note_nccl(r, "ncclAllReduce(landmarks)");
+            if (r != ncclSuccess) return b->rc;
         }
         ++b->n_exchanges;
         b->exchange_bytes += (int64_t)sizeof(double) * 3 * b->P.TL;
@@ -1508,20 +1362,13 @@ int limo_ba_batch_download(limo_ba_batch* b, limo_ba_window* windows_out, limo_b
         const bool neighbours = hi > lo && inside(b->bv.pose) && inside(b->bv.pdir) && inside(b->bv.pdist) && (P.TL == 0 || inside(b->bv.lm));
         const size_t span = neighbours ? (size_t)(hi - lo) : 0;
         void* hbuf = nullptr;
-        if (neighbours && span <= ctx->staging_cap && ctx->staging) {
-            hbuf = ctx->staging;
+        if (neighbours && span <= ctx->staging.cap && ctx->staging.p) {
+            hbuf = ctx->staging.p;
         } else if (neighbours && span <= limo_ctx::kBigStageMax) {
-            if (ctx->staging_big_cap < span) {
-                if (ctx->staging_big) (void)hipHostFree(ctx->staging_big);
-                ctx->staging_big = nullptr;
-                ctx->staging_big_cap = 0;
-                const size_t cap = std::min(limo_ctx::kBigStageMax, span + span / 4);
-                if (hipHostMalloc(&ctx->staging_big, cap) == hipSuccess)
-                    ctx->staging_big_cap = cap;
-                else
-                    (void)hipGetLastError();  // (no pinned memory to be had: the pageable path below)
-            }
-            if (ctx->staging_big_cap >= span) hbuf = ctx->staging_big;
+            if (ctx->staging_big.ensure(span, span + span / 4, limo_ctx::kBigStageMax) == hipSuccess)
+                hbuf = ctx->staging_big.p;
+            else
+                (void)hipGetLastError();  // (no pinned memory to be had: the pageable path below)
         }
         if (hbuf) {
             HIP_TRY(ctx, hipMemcpyAsync(hbuf, lo, span, hipMemcpyDeviceToHost, ctx->stream));

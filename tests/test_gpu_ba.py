@@ -144,6 +144,35 @@ def test_streaming_and_lock_step_schedules_give_the_same_bits(ctx, monkeypatch):
     assert ra[7]["iterations_total"] == 0 and ra[7]["termination"] == 0
 
 
+def test_one_batch_through_every_launch_sequence_gives_the_same_bits(ctx, monkeypatch):
+    """ONE batch object re-solved through the launch-sequence paths in turn - lock-step, lock-step again (the worklists were re-batched
+    in the first solve), streaming, lock-step: the worklist state, the lazily built full Schur worklist and the streaming set-up meet
+    on one object, and every solve gives the same bits.  24 windows (>= 8: the lock-step solve re-batches), generic-class ones among
+    them (6 - 7 keyframes)."""
+    ws = [synth.make_window(300 + i, n_kf=3 + (i % 5), n_lm=(60, 150, 400)[i % 3], ground_frac=(0.0, 0.2)[i % 2]) for i in range(24)]
+    o = default_options()
+    for k in ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE"):
+        monkeypatch.setenv(k, "1")
+    b = ba.Batch(ctx, [w.copy() for w in ws])
+    results = []
+    for i, stream_min in enumerate(("1000", "1000", "1", "1000")):
+        monkeypatch.setenv("KBA_STREAM_MIN", stream_min)
+        if i:
+            b.reset()
+        b.solve(o)
+        reps = b.download()
+        results.append((reps, [(w.kf_pose.copy(), w.kf_plane_dir.copy(), w.kf_plane_dist.copy(), w.lm_pos.copy()) for w in b.windows], [b.trimmed(i) for i in range(len(ws))]))
+    b.close()
+    ra, pa, ta = results[0]
+    assert any(r["iterations_total"] > 0 for r in ra)
+    for rb, pb, tb in results[1:]:
+        for i in range(len(ws)):
+            for key in ("termination", "iterations_total", "successful_steps", "n_trimmed_landmarks", "final_cost", "initial_cost"):
+                assert ra[i][key] == rb[i][key], (i, key)
+            assert all(np.array_equal(x, y) for x, y in zip(pa[i], pb[i])), i
+            assert np.array_equal(ta[i], tb[i])
+
+
 def test_not_enough_keyframes(ctx):
     """Only a window without active keyframes is refused; two (or one) active keyframes are solved like the reference
     does (its NotEnoughKeyframesException counts PUSHED keyframes: the shim's check) - cases kf2 / kf1 below."""
