@@ -78,6 +78,7 @@ void for_each_buffer(const PackedBatch& P, BatchView& bv, F f) {
     KBA_BUF(sblk_win, NS * I, P.sblk_win.data());
     KBA_BUF(sblk_lm0, NS * I, P.sblk_lm0.data());
     KBA_BUF(sblk_n, NS * I, P.sblk_n.data());
+    KBA_BUF(sgrp, NS * sizeof(SchurGroup), P.sgrp.empty() ? nullptr : P.sgrp.data());
     KBA_BUF(gp_lm, TG * I, P.gp_lm.data());
     KBA_BUF(gp_kf, TG * I, P.gp_kf.data());
     KBA_BUF(gp_w, TG * D, P.gp_w.data());

@@ -46,13 +46,19 @@ struct LinLane {
 //   Rc M  has the entries  G[i][j] = Rc[i][j+1] y[j+2] - Rc[i][j+2] y[j+1]  (indices mod 3: 18 more) - 27 operations with
 //   wave-uniform operands like the 27 of the per-view matrices C_k = Rc M(q, e_k) that rounds 5's first sessions used, but 9
 //   constants per view instead of 27 (a pair's view constants are 37 doubles instead of 55: what the lane waits for in k_lin_lm).
+//   vl[37..45] R(q), vl[46] |q|^2 - 1 (kViewLinRot: view_consts_item only): what the lean Schur waves need of the keyframe besides H, h0
+//   and Rc (kba_kernels.hip:schur_lean_group) - formed here once per linearisation instead of by every Schur wave of every LM iteration.
+//   [47..63] are unused.
 // In k_lin_lm every lane of a wave is at the same view of the same window, so these are wave-uniform (scalar registers).
-KBA_HD void view_consts_compute(const double* cam, const double* pose, double* vl);
+constexpr int kViewLinRot = 37;
+KBA_HD void view_consts_compute(const double* cam, const double* pose, double* vl, double* rot = nullptr);
 KBA_HD void view_consts_item(const BatchView& bv, int view) {
-    view_consts_compute(bv.view_cam + 16 * (int64_t)view, bv.pose + 7 * (int64_t)bv.view_kf[view], bv.view_lin + (int64_t)kViewLin * view);
+    double* vl = bv.view_lin + (int64_t)kViewLin * view;
+    view_consts_compute(bv.view_cam + 16 * (int64_t)view, bv.pose + 7 * (int64_t)bv.view_kf[view], vl, vl + kViewLinRot);
 }
-// cam = the view's 16 camera doubles (f, cx, cy, -, Rc 9, tc 3), pose = its keyframe's 7; vl receives the 37 constants
-KBA_HD void view_consts_compute(const double* cam, const double* pose, double* vl) {
+// cam = the view's 16 camera doubles (f, cx, cy, -, Rc 9, tc 3), pose = its keyframe's 7; vl receives the 37 constants, rot (if
+// given) R(q) (9) and |q|^2 - 1
+KBA_HD void view_consts_compute(const double* cam, const double* pose, double* vl, double* rot) {
     double R[9];
     quat_R(pose, R);
     mat3_mul(cam + 4, R, vl);
@@ -65,6 +71,10 @@ KBA_HD void view_consts_compute(const double* cam, const double* pose, double* v
     vl[27] = cam[2];
     const double qq1 = quat_norm2_minus_1(pose);
     for (int i = 0; i < 9; ++i) vl[28 + i] = -2.0 * (R[i] + ((i & 3) == 0 ? qq1 : 0.0));  // (i = 0, 4, 8: the diagonal)
+    if (rot) {
+        for (int i = 0; i < 9; ++i) rot[i] = R[i];
+        rot[9] = qq1;
+    }
 }
 
 // Inputs of one observation as the linearisation consumes them (a GPU lane fetches them one observation ahead).
@@ -729,6 +739,33 @@ KBA_HD int schur_col(int i, int nfq) {
 KBA_HD int schur_need_index(int n, int ca, int cb) { return ca * (n + 1) - ca * (ca - 1) / 2 + (cb - ca); }
 KBA_HD int64_t slab_packed_base(int q, int n_plain, int nf, int nfq) {
     return q < n_plain ? (int64_t)q * schur_need_pad(nfq) : (int64_t)n_plain * schur_need_pad(nfq) + (int64_t)(q - n_plain) * schur_need_pad(nf);
+}
+// The record of the group of Schur blocks that starts at block sb of window w (kba_layout.hpp:SchurGroup), for the spans given:
+// at pack time for BatchView::sgrp, and by a Schur wave itself when it runs with other spans than those.  Fast-class windows only
+// (WinDesc::schur_fast: kl / view / col0 describe its <= 4 free keyframes).
+KBA_HD SchurGroup schur_group_make(const WinDesc& wd, int w, int sb, int span, int span_gp, const int32_t* sblk_lm0, const int32_t* sblk_n,
+                                   const int32_t* cslot) {
+    SchurGroup g;
+    const int sb_last = schur_group_last(wd, sb, span, span_gp);
+    g.w = w;
+    g.lm_first = sblk_lm0[sb];
+    g.n_lm = sblk_lm0[sb_last] + sblk_n[sb_last] - g.lm_first;
+    g.n_fk = wd.n_fk;
+    g.nf = wd.nf, g.nfq = wd.nfq, g.nf_pad = wd.nf_pad;
+    g.kf0 = wd.kf0, g.view0 = wd.view0, g.cam0 = wd.cam0;
+    g.q_slab = schur_slab_of(wd, sb, span, span_gp);
+    g.pad = 0;
+    for (int k = 0; k < 4; ++k) {
+        const bool on = k < wd.n_fk;
+        g.kl[k] = on ? wd.fk[k] : -1;
+        g.view[k] = on ? wd.fk_view[k] : -1;
+        const int ci = on ? cslot[wd.cam0 + wd.fk[k] * kCamSlots] : -1;
+        g.col0[k] = ci < 0 ? -1 : schur_col(ci, wd.nfq);
+        g.pad2[k] = 0;
+    }
+    g.off_tile = wd.spart_off + (int64_t)g.q_slab * ((int64_t)wd.nf_pad * wd.nf_pad);
+    g.off_packed = wd.spart_off + slab_packed_base(g.q_slab, schur_plain_slabs(wd, span), wd.nf, wd.nfq);
+    return g;
 }
 // Reader: entry (ca, cb) of the enumeration for nf (cb == nf: the rhs) -> index inside a slab of the class, -1: a plain slab
 // has no such entry (it involves a plane slot: an exact zero)

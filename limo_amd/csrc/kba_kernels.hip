@@ -795,9 +795,10 @@ __global__ __launch_bounds__(64 * kWideWaves) void k_schur_wide(BatchView bv, co
 //     indices (slot, state, ground-plane row) are fetched two tiles ahead.
 // One wave per workgroup, no cross-wave synchronisation; `span` consecutive blocks of one class per wave.
 constexpr int kSpBatch = 4;  // k-steps whose panel reads are in flight together
-constexpr int kSpKf = 72;    // doubles per free keyframe in LDS: R (9) | Rc (9) | q (4) | scale of its 10 slots | |q|^2 - 1 (+ 26 unused: the B_k of
-                             // rounds 3-5, M(q, p) = sum_k p_k B_k - now M = -2 [Rh p]_x from R, kba_math.hpp:rot_tangent_from_R) |
-                             // H (9), h0 (3) of its view (view_xy: xn, yn of an observation are rebuilt from the landmark)
+constexpr int kSpKf = 41;    // doubles per free keyframe in LDS: R (9) | Rc (9) | scale of its 10 slots | |q|^2 - 1 | H (9), h0 (3) of its view
+                             // (M = -2 [Rh p]_x from R and |q|^2 - 1, kba_math.hpp:rot_tangent_from_R; view_xy: xn, yn of an observation are
+                             // rebuilt from the landmark).  All but the scales are copies of the view's record in view_lin.
+constexpr int kSpRc = 9, kSpScale = 18, kSpQq1 = 28, kSpH = 29;
 
 __host__ __device__ inline int schur_lean_ld(int ncol) { return ncol | 1; }  // odd row stride: conflict-free fill
 __host__ __device__ inline int schur_lean_lds_bytes(int ncol) {
@@ -820,13 +821,29 @@ __device__ __forceinline__ void schur_wave_sync() {
 }
 template <int TM, bool GP, bool COOP>
 __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, int span, int span_gp, int slab_packed, double* smem) {
-    const int w = bv.sblk_win[sb];
-    // (COOP: k_solve_coop only gets here for a window that iterates - and workgroup 0 may be writing the window's LM state at
-    // this very moment (lm_decide_lin runs beside the Schur phase), so the state is not read here)
-    if (!COOP && !bv.st[w].active) return;
-    const WinDesc& wd = bv.win[w];
-    const int nfq = wd.nfq, nfp = wd.nf_pad;
-    const int ncol = GP ? wd.nf + 1 : nfq + 1;  // columns of the tile, the rhs (column nfq) included
+    // ---- the head: everything a wave waits for before its first tile.  What describes the group is ONE record right behind the
+    //      worklist entry (kba_layout.hpp:SchurGroup, scalar loads; with other spans than the record's - the landmark-sharded solve -
+    //      the wave builds it from the window's descriptor and the block tables as the waves of rounds 3-6 did); then the index
+    //      loads of the first two tiles, the keyframe constants and the data loads of the first tile are ISSUED in this order before
+    //      anything is waited for: the constants arrive under the landmark-side loads, and the wave reaches its first fill behind
+    //      one wait.
+    // (Two routes to ONE description: schur_group_make writes the record at pack time and is what the other route calls on the
+    // device, so the two cannot drift apart field by field; the launch-path tests run the record, the sharded tests the device route.)
+    SchurGroup g;
+    if (span == kSchurSpan && span_gp == kSchurSpanGp) {
+        g = bv.sgrp[sb];
+    } else {
+        const int w = bv.sblk_win[sb];
+        g = schur_group_make(bv.win[w], w, sb, span, span_gp, bv.sblk_lm0, bv.sblk_n, bv.cslot);
+    }
+    // Lock-step lists hold finished windows: their waves leave below, once the first loads are on their way (every address is
+    // valid whatever the window's state).  (COOP: k_solve_coop only gets here for a window that iterates - and workgroup 0 may be
+    // writing the window's LM state at this very moment (lm_decide_lin runs beside the Schur phase), so the state is not read)
+    // (an atomic load: a vector load that joins the index and constant loads below and is waited for with them - as a scalar load it
+    // shared the wait of the kernel-argument pointers in front of the first vector load, a trip of its own behind the record)
+    const int active = COOP ? 1 : __hip_atomic_load(&bv.st[g.w].active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int nfq = g.nfq, nfp = g.nf_pad;
+    const int ncol = GP ? g.nf + 1 : nfq + 1;  // columns of the tile, the rhs (column nfq) included
     const int ld = schur_lean_ld(ncol);
     const int Tt = (ncol + 15) / 16;
     // Two-tile Gram (plain blocks, 17..25 columns): the <= 24 pose columns are covered by TWO 16x16 products instead of
@@ -841,41 +858,15 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     double* kc = Z + 3 * kSchurLm * ld + 16;            // [4][kSpKf]
     int* zcs = reinterpret_cast<int*>(kc + 4 * kSpKf);  // [4][12] tile column of the keyframe's slots (or -1)
     const int lane = COOP ? (int)(threadIdx.x & 63) : (int)threadIdx.x, li = lane & 15, kq = lane >> 4;
-    const int n_fk = wd.n_fk;
-    int my_view = -1, my_kl = -1;
-    if (kq < n_fk) {
-        my_kl = wd.fk[kq];
-        my_view = wd.fk_view[kq];
-        double* mine = kc + kq * kSpKf;
-        const double* pose = bv.pose + 7 * (int64_t)(wd.kf0 + my_kl);
-        if (li == 0) {
-            double R[9];
-            quat_R(pose, R);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) mine[i] = R[i];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) mine[18 + i] = pose[i];
-            mine[32] = quat_norm2_minus_1(pose);
-        } else if (li < 10) {
-            mine[9 + li - 1] = my_view >= 0 ? bv.view_cam[16 * (int64_t)my_view + 4 + li - 1] : 0.0;
-        } else if (li == 13) {
-            for (int i = 0; i < 12; ++i) mine[59 + i] = my_view >= 0 ? bv.view_lin[(int64_t)kViewLin * my_view + i] : 0.0;
-        }
-        if (li < kCamSlots) {
-            const int slot = wd.cam0 + my_kl * kCamSlots + li;
-            mine[22 + li] = bv.scale_c[slot];
-            const int ci = bv.cslot[slot];
-            zcs[kq * 12 + li] = ci < 0 ? -1 : schur_col(ci, nfq);
-        }
-    }
-    if (lane < 16) Z[3 * kSchurLm * ld + lane] = 0.0;
-    schur_wave_sync<COOP>();
-    const bool have = kq < n_fk && zcs[kq * 12] >= 0;  // the keyframe's pose block is free (its six slots together)
-    const double* mine = kc + (kq < n_fk ? kq : 0) * kSpKf;
-    const int32_t* my_slots = bv.lm_slot + (int64_t)(my_view >= 0 ? my_view - wd.view0 : 0) * bv.SL;
-    const int sb_last = schur_group_last(wd, sb, span, span_gp);
-    const int lm_first = bv.sblk_lm0[sb];
-    const int n_lm_blk = bv.sblk_lm0[sb_last] + bv.sblk_n[sb_last] - lm_first;
+    const int n_fk = g.n_fk;
+    // (selected from the record's scalars: indexing it by kq would be a vector load of its own)
+    const int my_kl = kq == 0 ? g.kl[0] : kq == 1 ? g.kl[1] : kq == 2 ? g.kl[2] : g.kl[3];  // -1: kq >= n_fk
+    const int my_view = kq == 0 ? g.view[0] : kq == 1 ? g.view[1] : kq == 2 ? g.view[2] : g.view[3];
+    const int my_col0 = kq == 0 ? g.col0[0] : kq == 1 ? g.col0[1] : kq == 2 ? g.col0[2] : g.col0[3];
+    const bool have = my_col0 >= 0;  // the keyframe's pose block is free (its six slots together)
+    const int slot0 = g.cam0 + (my_kl >= 0 ? my_kl : 0) * kCamSlots;
+    const int32_t* my_slots = bv.lm_slot + (int64_t)(my_view >= 0 ? my_view - g.view0 : 0) * bv.SL;
+    const int lm_first = g.lm_first, n_lm_blk = g.n_lm;
 
     constexpr int NT = (!GP && TM == 2) ? 2 : TM * (TM + 1) / 2;
     v4f64 acc[NT];
@@ -883,20 +874,28 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     for (int i = 0; i < NT; ++i) acc[i] = (v4f64){0.0, 0.0, 0.0, 0.0};
 
     // ---- software pipeline
-    // stage 1 (two tiles ahead): landmark state, observation slot in this lane's keyframe, ground-plane row attached to it
-    auto fetch_index = [&](int l0, int& st, int& slot, int& gg) {
-        st = 0;
-        slot = -1;
-        gg = -1;
-        if (l0 + li < n_lm_blk) {
-            const int gl = lm_first + l0 + li;
-            st = bv.lm_state[gl];
-            if (have && my_view >= 0) slot = my_slots[gl];
-            if (GP && have && st == 1) {
-                const int g = bv.lm_gp[gl];
-                if (g >= 0 && bv.gp_kf[g] - wd.kf0 == my_kl) gg = g;
-            }
-        }
+    // stage 1 (two tiles ahead): landmark state, observation slot in this lane's keyframe, ground-plane row attached to it.
+    // index_issue only ISSUES the loads (branch-free: a lane past the group's end reads the last landmark's entries, a lane without
+    // a view row 0 of the slot table - a use of a loaded value inside a divergent section would wait for it at the section's end);
+    // index_kf issues the one load that depends on another (the row's keyframe); index_mask turns the raw values into what the
+    // data stage consumes, when it consumes them.
+    auto index_issue = [&](int l0, int& st, int& slot, int& gr) {
+        const int i = l0 + li < n_lm_blk ? l0 + li : n_lm_blk - 1;
+        const int gl = lm_first + i;
+        st = bv.lm_state[gl];
+        slot = my_slots[gl];
+        gr = -1;
+        if constexpr (GP) gr = bv.lm_gp[gl];
+    };
+    auto index_kf = [&](int gr) {
+        if constexpr (GP) return bv.gp_kf[gr >= 0 ? gr : 0];
+        return 0;
+    };
+    auto index_mask = [&](int l0, int& st, int& slot, int& gg, int kf) {  // gg: in the raw row, out the row if it hangs on this keyframe
+        const bool in = l0 + li < n_lm_blk;
+        st = in ? st : 0;
+        slot = in && have && my_view >= 0 ? slot : -1;
+        gg = GP && in && have && st == 1 && gg >= 0 && kf - g.kf0 == my_kl ? gg : -1;
     };
     // stage 2 (one tile ahead): the landmark-side inputs
     // (g3 is written by loads only: with a variable that the fill also overwrites - t = Bt g in place - the compiler copied the loaded
@@ -932,13 +931,40 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
             }
         }
     };
-    int n_st, n_slot, n_gg;
+    int n_st, n_slot, n_gg, n_kf;  // raw index values of the tile after the next
     {
-        int st0, slot0, gg0;
-        fetch_index(0, st0, slot0, gg0);
-        fetch_index(kSchurLm, n_st, n_slot, n_gg);
-        fetch_data(0, st0, slot0, gg0);
+        int st0, sl0, gg0;
+        index_issue(0, st0, sl0, gg0);
+        index_issue(kSchurLm, n_st, n_slot, n_gg);
+        // keyframe constants: the 16 lanes of a keyframe copy its view's record (kba_items.hpp:view_consts_item - H, h0, Rc at
+        // [0..20], R, |q|^2 - 1 at [37..46]) with three coalesced loads, ten of them the scales and the columns of its slots.
+        // A free keyframe without a view has no observation (no `seen` lane): its R, Rc, H are never read and stay zero.
+        // (issued branch-free as well: idle lanes read a valid place and drop the value)
+        const double* vl = bv.view_lin + (int64_t)kViewLin * (my_view >= 0 ? my_view : 0);
+        const double v0 = vl[li], v1 = vl[16 + li], v2 = vl[32 + li];
+        const int my_slot = slot0 + (li < kCamSlots ? li : 0);
+        const double sc = bv.scale_c[my_slot];
+        const int ci = bv.cslot[my_slot];
+        const int kf_0 = index_kf(gg0);
+        n_kf = index_kf(n_gg);
+        index_mask(0, st0, sl0, gg0, kf_0);
+        fetch_data(0, st0, sl0, gg0);
+        if (!active) return;
+        if (kq < n_fk) {
+            double* mine_w = kc + kq * kSpKf;
+            const bool vw = my_view >= 0;
+            mine_w[li < 12 ? kSpH + li : kSpRc + li - 12] = vw ? v0 : 0.0;               // [0..11] H, h0 | [12..15] Rc
+            if (li < 5) mine_w[kSpRc + 4 + li] = vw ? v1 : 0.0;                          // [16..20] Rc
+            if (li >= 5 && li < 15) mine_w[li == 14 ? kSpQq1 : li - 5] = vw ? v2 : 0.0;  // [37..45] R | [46] |q|^2 - 1
+            if (li < kCamSlots) {
+                mine_w[kSpScale + li] = sc;
+                zcs[kq * 12 + li] = ci < 0 ? -1 : schur_col(ci, nfq);
+            }
+        }
+        if (lane < 16) Z[3 * kSchurLm * ld + lane] = 0.0;
+        schur_wave_sync<COOP>();
     }
+    const double* mine = kc + (kq < n_fk ? kq : 0) * kSpKf;
     constexpr int NS = GP ? kCamSlots : 6;  // slots of a keyframe this kernel fills
     double yt[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // two-tile path: this lane's share of the rhs, slots of its keyframe
     const int mq = li < 8 ? li : li + 8;            // two-tile path: column of lane li in the second operand {0..7, 16..23}
@@ -956,10 +982,10 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
             for (int i = 0; i < 3 * NS; ++i) Y[i] = 0.0;
             if (seen) {
                 double M[9], Ft[9];
-                rot_tangent_from_R(mine, mine[32], p, M);  // M(q, p) = -2 [Rh(q) p]_x: three entries of -2 Rh p instead of 27 products with the B_k
-                view_xy(mine + 59, p, &c4[1], &c4[2]);
-                ft_build(c4, mine + 9, Ft);
-                schur_pose_block<true>(Ft, mine, M, Bt, mine + 22, Y);
+                rot_tangent_from_R(mine, mine[kSpQq1], p, M);  // M(q, p) = -2 [Rh(q) p]_x: three entries of -2 Rh p instead of 27 products with the B_k
+                view_xy(mine + kSpH, p, &c4[1], &c4[2]);
+                ft_build(c4, mine + kSpRc, Ft);
+                schur_pose_block<true>(Ft, mine, M, Bt, mine + kSpScale, Y);
                 if (two_tile) {
 #pragma unroll
                     for (int a = 0; a < 6; ++a) yt[a] += Y[a * 3 + 0] * t3[0] + Y[a * 3 + 1] * t3[1] + Y[a * 3 + 2] * t3[2];
@@ -970,7 +996,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
                     const double y0 = gE[0] * Bt[0], y1 = gE[0] * Bt[1] + gE[1] * Bt[2], y2 = gE[0] * Bt[3] + gE[1] * Bt[4] + gE[2] * Bt[5];
 #pragma unroll
                     for (int a = 0; a < kCamSlots; ++a) {
-                        const double fa = zcs[kq * 12 + a] >= 0 ? gF[a] * mine[22 + a] : 0.0;
+                        const double fa = zcs[kq * 12 + a] >= 0 ? gF[a] * mine[kSpScale + a] : 0.0;
                         Y[a * 3 + 0] += fa * y0;
                         Y[a * 3 + 1] += fa * y1;
                         Y[a * 3 + 2] += fa * y2;
@@ -998,8 +1024,10 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         }
         // ---- loads of the next tile (they complete under the MFMAs below), indices of the one after
         {
-            const int st = n_st, slot = n_slot, gg = n_gg;
-            fetch_index(l0 + 2 * kSchurLm, n_st, n_slot, n_gg);
+            int st = n_st, slot = n_slot, gg = n_gg;
+            index_mask(l0 + kSchurLm, st, slot, gg, n_kf);
+            index_issue(l0 + 2 * kSchurLm, n_st, n_slot, n_gg);
+            n_kf = index_kf(n_gg);
             fetch_data(l0 + kSchurLm, st, slot, gg);
         }
         schur_wave_sync<COOP>();
@@ -1088,9 +1116,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     //      Either way a slab keeps its class and its place for the life of the batch (schur_slab_of: plain groups first,
     //      fixed spans).
     const bool packed = !COOP && slab_packed != 0;
-    const int q_slab = schur_slab_of(wd, sb, span, span_gp);
-    double* out = bv.S_part + wd.spart_off +
-                  (packed ? slab_packed_base(q_slab, schur_plain_slabs(wd, span), wd.nf, nfq) : (int64_t)q_slab * ((int64_t)nfp * nfp));
+    double* out = bv.S_part + (packed ? g.off_packed : g.off_tile);
     const int T = nfp / 16;
     if (two_tile && packed) {
         // the two products and the rhs sums go from the registers to their packed places (no staging matrix: nothing has to be
@@ -1100,11 +1126,11 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
             const int row = kq + 4 * r;
             {   // first product: entry (row, 8 + li)
                 const int col = 8 + li;
-                if (row <= col && col < nfq) out[slab_packed_write(false, row, col, wd.nf, nfq)] = acc[0][r];
+                if (row <= col && col < nfq) out[slab_packed_write(false, row, col, g.nf, nfq)] = acc[0][r];
             }
             {   // second product: entry (m(row), m(li))
                 const int a = row < 8 ? row : row + 8, b = mq;
-                if (a <= b && b < nfq && !(a < 8 && b >= 16)) out[slab_packed_write(false, a, b, wd.nf, nfq)] = acc[1][r];
+                if (a <= b && b < nfq && !(a < 8 && b >= 16)) out[slab_packed_write(false, a, b, g.nf, nfq)] = acc[1][r];
             }
         }
         if (have) {  // rhs: sum of this keyframe's six slot values over the 16 landmark lanes
@@ -1115,7 +1141,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
                 v += __shfl_xor(v, 2, 64);
                 v += __shfl_xor(v, 4, 64);
                 v += __shfl_xor(v, 8, 64);
-                if (li == 0) out[slab_packed_write(false, zcs[kq * 12] + a, nfq, wd.nf, nfq)] = v;
+                if (li == 0) out[slab_packed_write(false, zcs[kq * 12] + a, nfq, g.nf, nfq)] = v;
             }
         }
         return;
@@ -1165,7 +1191,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         for (int r = 0; r < 4; ++r) {
             const int row = kq + 4 * r, col = li;
             if (packed) {
-                const int k = slab_packed_write(false, row, col, wd.nf, nfq);
+                const int k = slab_packed_write(false, row, col, g.nf, nfq);
                 if (k >= 0) out[k] = acc[0][r];
             } else {
                 out[row * nfp + col] = (row < ncol && col < ncol) ? acc[0][r] : 0.0;
@@ -1183,7 +1209,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
                         // f64 16x16x4 C/D layout: row = (lane>>4) + 4*reg, col = lane&15
                         const int row = tr * 16 + kq + 4 * r, col = tc * 16 + li;
                         if (packed) {
-                            const int k = slab_packed_write(GP, row, col, wd.nf, nfq);
+                            const int k = slab_packed_write(GP, row, col, g.nf, nfq);
                             if (k >= 0) out[k] = acc[idx][r];
                         } else {
                             out[row * nfp + col] = (row < ncol && col < ncol) ? acc[idx][r] : 0.0;

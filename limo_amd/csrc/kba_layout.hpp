@@ -21,7 +21,7 @@ namespace kba {
 constexpr int kMaxKf = 20;        // max keyframes per window: the reference's default max_size_optimization_window
                                   // (bundle_adjuster_keyframes.hpp:129); the KITTI launch runs 12
 constexpr int kMaxViews = 64;     // max (keyframe, camera) views per window (LDS tables of the Schur kernels)
-constexpr int kViewLin = 64;      // doubles per view in BatchView::view_lin (kba_items.hpp:view_consts_item: 55 used)
+constexpr int kViewLin = 64;      // doubles per view in BatchView::view_lin (kba_items.hpp:view_consts_item: 47 used)
 constexpr int kCamSlots = 10;     // tangent dims per keyframe in the reduced camera system
 constexpr int kMaxNc = kMaxKf * kCamSlots;
 constexpr int kBlock = 256;       // lanes per workgroup in the scan kernels
@@ -31,6 +31,7 @@ constexpr int kObsBlock = kBlock * kObsPerLane;  // observations per linearize /
 constexpr int kSchurLm = 16;      // landmarks per Schur LDS tile (48 rows = 12 MFMA k-steps)
 constexpr int kSchurLmPerBlock = 64;   // landmarks per Schur block; a wave takes SolveConsts::schur_span (2; 1 when landmark-sharded)
                                        // consecutive blocks of a window and writes one partial slab
+constexpr int kSchurSpan = 2, kSchurSpanGp = 1;  // the spans of an unsharded batch: the ones BatchView::sgrp is built for
 constexpr int kMaxRegRows = 1 + (kMaxKf - 1) * 5 + 3 * kMaxKf;  // scale + per pair (3+1+1) + global normal 3/kf
 
 // number of doubles in a block partial of the linearize kernel: cost, 21 (U upper) + 6 (g)
@@ -89,6 +90,28 @@ struct WinDesc {
     int64_t cam_scr_off;      // >= 0: the window's camera system does not fit into LDS (more than ~12 keyframes): offset of its
                               // scratch in BatchView::cam_scratch (k_cam_assemble / k_cam_solve work there, in L2, instead)
 };
+
+// What a lean Schur wave (kba_kernels.hip:schur_lean_group) needs to know about its group of Schur blocks before it can issue
+// its first loads - fixed for the life of the batch given the spans, so it is written once at pack time, one record per Schur
+// block (BatchView::sgrp[sb]: the group that STARTS at block sb with the spans kSchurSpan / kSchurSpanGp), 128 bytes that the wave
+// reads with scalar loads straight behind its worklist entry: no trip to sblk_win, the window's descriptor and the block tables
+// first.  With other spans (the landmark-sharded solve) the wave builds the same record from those (kba_items.hpp:schur_group_make).
+struct alignas(128) SchurGroup {
+    int32_t w;                 // window
+    int32_t lm_first, n_lm;    // first (global) landmark and landmark count of the group
+    int32_t n_fk;              // free keyframes of the window (<= 4: the fast class)
+    int32_t nf, nfq, nf_pad;   // WinDesc::nf, nfq, nf_pad
+    int32_t kf0, view0, cam0;  // WinDesc::kf0, view0, cam0
+    int32_t q_slab;            // the group's partial slab (kba_items.hpp:schur_slab_of)
+    int32_t pad;
+    int32_t kl[4];             // per free keyframe: local keyframe index (or -1),
+    int32_t view[4];           //   its view (global index, or -1),
+    int32_t col0[4];           //   tile column of its first pose slot, or -1: its pose block is not free
+    int64_t off_tile;          // the slab's place in S_part, tile layout (spart_off + q_slab * nf_pad^2)
+    int64_t off_packed;        //   and packed layout (kba_items.hpp:slab_packed_base)
+    int32_t pad2[4];
+};
+static_assert(sizeof(SchurGroup) == 128, "one cache line per record");
 
 // Per-window Levenberg-Marquardt state (device resident; see kba_lm.hpp).
 struct WinState {
@@ -184,8 +207,9 @@ struct BatchView {
     double* view_lin_c;         // [TV*kViewLin] for the CANDIDATE poses (k_cam_solve): H, h0, intrinsics at the same places, and at
                                 // [28..39] K = Rc dR (9), k0 = Rc delta_t (3) of the proposed camera step (back-substitution:
                                 // F_pose delta_pose of an observation = c^T (K p + k0), no per-observation M(q, p))
-    double* view_lin;           // [TV*kViewLin] per-view constants of the CURRENT poses (k_view_consts): H = Rc R(q) (9),
-                                // h0 = Rc t + tc (3), Rc (9), q (4), f, cx, cy - wave-uniform operands of k_lin_lm
+    double* view_lin;           // [TV*kViewLin] per-view constants of the CURRENT poses (kba_items.hpp:view_consts_item): H = Rc R(q) (9),
+                                // h0 = Rc t + tc (3), Rc (9), q (4), f, cx, cy, -2 Rh(q) (9) - wave-uniform operands of k_lin_lm - and at
+                                // [37..45] R(q), [46] |q|^2 - 1: with H, h0, Rc what a lean Schur wave copies into LDS per free keyframe
     const int32_t* blk_view;    // [n_blk]
     const int32_t* blk_obs0;    // [n_blk]
     const int32_t* blk_n;       // [n_blk]
@@ -197,6 +221,7 @@ struct BatchView {
     const int32_t* sblk_win;    // [n_sblk]
     const int32_t* sblk_lm0;
     const int32_t* sblk_n;
+    const SchurGroup* sgrp;     // [n_sblk] the group that starts at the block, spans kSchurSpan / kSchurSpanGp
     // --- ground-plane residuals
     // --- landmark-sharded solve: what a shard contributes per LM iteration, already summed over ITS workgroups /
     //     rows (kba_items.hpp:shard_reduce_*), in the shard's own contiguous block (kba_buffers.hpp:exchange_layout):

@@ -776,6 +776,14 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
     P.n_blk = (int)P.blk_view.size();
     P.n_lblk = (int)P.lblk_win.size();
     P.n_sblk = (int)P.sblk_win.size();
+    // what a lean Schur wave needs to know about the group that starts at a block (spans of an unsharded batch)
+    P.sgrp.assign((size_t)P.n_sblk, SchurGroup{});
+    for_windows([&](int w) {
+        const WinDesc& d = P.win[w];
+        if (!d.schur_fast) return;
+        for (int sb = d.sblk0; sb < d.sblk0 + d.n_sblk; ++sb)
+            P.sgrp[sb] = schur_group_make(d, w, sb, kSchurSpan, kSchurSpanGp, P.sblk_lm0.data(), P.sblk_n.data(), P.cslot.data());
+    });
     if (P.evaluate_only) {
         // The materialised pass (k_evaluate) writes the rows that EXIST: the depth rows go into COMPACT planes over the depth
         // observations only, indexed by the observation's rank among them in packed order (obs_rank).  Its work items are

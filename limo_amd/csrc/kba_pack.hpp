@@ -102,6 +102,7 @@ struct PackedBatch {
     uvec<float> obs_u, obs_v, obs_d;
     uvec<int32_t> obs_src;  // packed observation -> index in the caller's window
     std::vector<int32_t> lblk_win, lblk_lm0, lblk_n, sblk_win, sblk_lm0, sblk_n;
+    std::vector<SchurGroup> sgrp;  // [n_sblk] kba_layout.hpp:SchurGroup (fast-class windows; zero elsewhere)
     std::vector<int32_t> gp_lm, gp_kf;
     std::vector<double> gp_w;
 };

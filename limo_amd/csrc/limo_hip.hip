@@ -380,8 +380,8 @@ struct limo_ba_batch : Executor {
     SolveConsts consts_for(const limo_ba_options& o) const {
         SolveConsts k = make_consts(o);
         const bool sharded = shard_P > 1;
-        k.schur_span = sharded ? 1 : 2;  // (Schur blocks are cut at shard boundaries)
-        k.schur_span_gp = 1;
+        k.schur_span = sharded ? 1 : kSchurSpan;  // (Schur blocks are cut at shard boundaries)
+        k.schur_span_gp = kSchurSpanGp;
         k.schur_nslab = sharded ? shard_P : 0;
         k.schur_packed = sharded ? 1 : 0;
         // the launch sequences of an unsharded batch (lock-step and streaming) keep the partial slabs of fast-class windows packed

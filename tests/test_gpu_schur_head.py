@@ -1,0 +1,184 @@
+"""The head of a lean Schur wave (kba_kernels.hip:schur_lean_group): group record, keyframe constants from view_lin, first loads.
+
+What a wave knows before its first tile comes from the per-group record written at pack time (kba_layout.hpp:SchurGroup) and from the
+view's record in view_lin (R and |q|^2 - 1 next to H, h0, Rc: kba_items.hpp:view_consts_item).  Four launch sequences reach the same
+device function with the same record - the one-launch solve (k_solve_coop, tile slabs), the lock-step launches, the streaming solve
+with the pair kernel of its draining rounds and without it - and must give the same bytes for poses, planes, landmarks, trimmed set
+and every integer and cost field of the report.  One streaming solve runs in a process of its own under KBA_POISON=1 (every device
+block starts as NaN bytes; the switch is read once per process): a record entry or a view_lin place that a wave reads before anybody
+wrote it shows as NaN there, not as the luck of a zeroed allocation.
+
+Shapes - the smallest at which the head can go wrong (landmarks before the selection of synth.make_window; a Schur block is 64
+landmarks of one class, a plain group two blocks, a ground-plane group one):
+  * 1, 2, 3, 4 free keyframes (n_kf 2 .. 5): 3 .. 0 idle 16-lane groups of the wave;
+  * a plain class with an odd number of blocks: the last plain group is ONE block;
+  * a group of fewer than 16 landmarks (one tile: both index prefetches and the data prefetch run past its end) - the ground-plane
+    class of the 65-landmark window;
+  * a last block of one landmark (65 plain landmarks);
+  * no ground-plane landmark at all, and only ground-plane landmarks;
+  * a free keyframe WITHOUT a view: synth.make_window gives every keyframe observations, so the case takes one of its windows and
+    removes the observations of keyframe 2.  With ground-plane rows in the window the pose block of that keyframe stays in the
+    problem and free (kba_pack.cpp: the ground-plane regularisers touch every keyframe), its entry of the record has view -1;
+  * a lock-step batch of three windows that need different iteration counts: the static lists keep the finished windows, whose
+    waves leave at the `active` test after their first loads are issued.
+"""
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":
+    sys.path.insert(0, ROOT)
+
+from limo_amd import ba, default_options, synth  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CASES = [
+    dict(seed=7300, n_kf=2, n_lm=300),
+    dict(seed=7301, n_kf=3, n_lm=300),
+    dict(seed=7302, n_kf=4, n_lm=300),
+    dict(seed=7303, n_kf=5, n_lm=400),
+    dict(seed=7304, n_kf=5, n_lm=190, with_ground_plane=False),  # odd number of plain blocks, no ground-plane landmark
+    dict(seed=7305, n_kf=4, n_lm=200, ground_frac=1.0),          # only ground-plane landmarks
+    dict(seed=7103, n_kf=3, n_lm=65, with_ground_plane=False),   # 64 + 1 plain landmarks
+    dict(seed=7102, n_kf=3, n_lm=65),                            # ground-plane class of fewer than 16 landmarks
+    dict(seed=7306, n_kf=4, n_lm=300, drop_kf=2),                # free keyframe without a view
+]
+LOCK_STEP_BATCH = (3, 6, 0)  # three windows of different sizes in one lock-step batch
+REPORT_KEYS = ("termination", "num_solves", "iterations_total", "iterations_final", "successful_steps", "n_depth_blocks", "n_repr_blocks",
+               "n_gp_blocks", "n_trimmed_landmarks", "num_linearizations", "initial_cost", "final_cost")
+_ENV = ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE", "KBA_STREAM_MIN", "KBA_NO_SCHUR_PAIR")
+LOCK_STEP = {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"}
+STREAMING = {"KBA_STREAM_MIN": "1"}
+
+
+def _window(c):
+    w = synth.make_window(c["seed"], **{k: v for k, v in c.items() if k not in ("seed", "drop_kf")})
+    if "drop_kf" in c:
+        keep = w.obs_kf != c["drop_kf"]
+        for name in ("obs_kf", "obs_lm", "obs_cam", "obs_u", "obs_v", "obs_d"):
+            setattr(w, name, np.ascontiguousarray(getattr(w, name)[keep]))
+        w.validate()
+    return w
+
+
+def _blocks(w):
+    """Schur blocks (plain, ground-plane) of the window."""
+    n_gp = int(w.lm_is_ground.sum())
+    return (w.n_lm - n_gp + 63) // 64, (n_gp + 63) // 64
+
+
+def _result(b, reps, i):
+    w = b.windows[i]
+    return (tuple(reps[i][k] for k in REPORT_KEYS), w.kf_pose.tobytes(), w.kf_plane_dir.tobytes(), w.kf_plane_dist.tobytes(), w.lm_pos.tobytes(),
+            b.trimmed(i).tobytes())
+
+
+def _digest(r):
+    h = hashlib.sha256(repr(r[0]).encode())
+    for x in r[1:]:
+        h.update(x)
+    return h.hexdigest()
+
+
+def _solve_batch(ctx, windows):
+    b = ba.Batch(ctx, [w.copy() for w in windows])
+    b.solve(default_options())
+    reps = b.download()
+    out = [_result(b, reps, i) for i in range(len(windows))]
+    b.close()
+    return out
+
+
+def _solve(ctx, windows, monkeypatch, env):
+    for k in _ENV:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    out = _solve_batch(ctx, windows)
+    for k in _ENV:
+        monkeypatch.delenv(k, raising=False)
+    return out
+
+
+_cache = {}  # results computed once, shared, never changed
+
+
+def _one_launch(ctx, i, monkeypatch):
+    if ("one", i) not in _cache:
+        _cache["one", i] = _solve(ctx, [_window(CASES[i])], monkeypatch, {})[0]
+    return _cache["one", i]
+
+
+def _streaming(ctx, monkeypatch):
+    if "stream" not in _cache:
+        _cache["stream"] = _solve(ctx, [_window(c) for c in CASES], monkeypatch, STREAMING)
+    return _cache["stream"]
+
+
+def _same(a, b, what):
+    assert a[0] == b[0], (what, dict(zip(REPORT_KEYS, a[0])), dict(zip(REPORT_KEYS, b[0])))
+    for name, x, y in zip(("kf_pose", "kf_plane_dir", "kf_plane_dist", "lm_pos", "trimmed"), a[1:], b[1:]):
+        assert x == y, (what, name)
+    assert np.isfinite(np.frombuffer(a[1])).all() and np.isfinite(np.frombuffer(a[4])).all(), what
+
+
+def test_shapes_are_what_the_cases_are_for():
+    ws = [_window(c) for c in CASES]
+    assert [w.n_kf - 1 for w in ws[:4]] == [1, 2, 3, 4]      # free keyframes (the first one is Pose-fixed)
+    assert all(w.n_lm <= 400 for w in ws)
+    assert all(_blocks(w)[0] >= 2 and _blocks(w)[1] >= 1 for w in ws[:4])
+    assert _blocks(ws[4])[0] % 2 == 1 and _blocks(ws[4])[0] >= 3 and ws[4].lm_is_ground.sum() == 0  # last plain group: one block
+    assert ws[5].lm_is_ground.all() and _blocks(ws[5])[1] >= 2
+    assert ws[6].n_lm == 65 and ws[6].lm_is_ground.sum() == 0                                       # blocks of 64 + 1 landmarks
+    assert 0 < ws[7].lm_is_ground.sum() < 16                                                         # a one-tile group
+    d = CASES[8]["drop_kf"]
+    assert (ws[8].obs_kf == d).sum() == 0 and ws[8].kf_fixation[d] == 2 and ws[8].lm_is_ground.sum() > 0
+    assert np.bincount(ws[8].obs_lm, minlength=ws[8].n_lm).min() >= 1  # every landmark is still observed
+    assert len({ws[i].n_lm for i in LOCK_STEP_BATCH}) == 3
+
+
+@pytest.mark.parametrize("i", range(len(CASES)))
+def test_lock_step_equals_one_launch(ctx, i, monkeypatch):
+    got = _solve(ctx, [_window(CASES[i])], monkeypatch, LOCK_STEP)[0]
+    _same(_one_launch(ctx, i, monkeypatch), got, CASES[i])
+
+
+def test_streaming_equals_one_launch(ctx, monkeypatch):
+    got = _streaming(ctx, monkeypatch)
+    for i in range(len(CASES)):
+        _same(_one_launch(ctx, i, monkeypatch), got[i], CASES[i])
+
+
+def test_streaming_without_the_pair_kernel_equals_streaming(ctx, monkeypatch):
+    got = _solve(ctx, [_window(c) for c in CASES], monkeypatch, dict(STREAMING, KBA_NO_SCHUR_PAIR="1"))
+    ref = _streaming(ctx, monkeypatch)
+    for i in range(len(CASES)):
+        _same(ref[i], got[i], CASES[i])
+
+
+def test_lock_step_batch_with_finished_windows(ctx, monkeypatch):
+    got = _solve(ctx, [_window(CASES[i]) for i in LOCK_STEP_BATCH], monkeypatch, LOCK_STEP)
+    iters = [g[0][REPORT_KEYS.index("iterations_total")] for g in got]
+    assert len(set(iters)) > 1, iters  # some windows finish while others iterate: their waves take the `active` exit
+    for k, i in enumerate(LOCK_STEP_BATCH):
+        _same(_one_launch(ctx, i, monkeypatch), got[k], CASES[i])
+
+
+def test_streaming_under_poison_equals_streaming(ctx, monkeypatch):
+    env = {k: v for k, v in os.environ.items() if k not in _ENV}
+    env.update(STREAMING, KBA_POISON="1")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l.split()[1] for l in r.stdout.splitlines() if l.startswith("digest ")]
+    assert lines == [_digest(x) for x in _streaming(ctx, monkeypatch)]
+
+
+if __name__ == "__main__":  # the streaming solve of all cases in a process of its own (KBA_POISON is read once per process)
+    for res in _solve_batch(ba.Context(0), [_window(c) for c in CASES]):
+        print("digest", _digest(res))
