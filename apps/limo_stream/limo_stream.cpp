@@ -7,6 +7,9 @@
 //
 //   limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--poses out.txt] [--gt-poses gt.txt]
 //               [--dump-velodyne DIR] [--velodyne DIR] [--no-depth] [--depth-ahead thread|stream|none] [--quiet]
+//               [--depth-params FILE]
+// --depth-params reads the depth estimator's settings from a mono_lidar_fusion_parameters.yaml (the file the reference
+// application loads; limo_amd/kba/depth_params_yaml.hpp) instead of using the built-in defaults, which are that file's values.
 // --dump-velodyne writes every synthetic sweep as a KITTI velodyne scan (DIR/NNNNNN.bin); --velodyne replays scans from
 // such a directory instead of ray-casting them (the scans of a real KITTI sequence have the same format; the tracked
 // features of a real sequence come from the feature tracker, which is outside this path).
@@ -25,6 +28,7 @@
 #include <map>
 #include <string>
 
+#include "../../limo_amd/kba/depth_params_yaml.hpp"
 #include "../../limo_amd/kba/kitti_io.hpp"
 #include "../../limo_amd/kba/stream_driver.hpp"
 #include "synth_world.hpp"
@@ -34,7 +38,7 @@ using namespace keyframe_bundle_adjustment;
 int main(int argc, char** argv) {
     int n_frames = 200, n_feat = 1500, n_az = 2000, window = 5, misannounce_every = 0;
     uint64_t seed = 7;
-    std::string poses_path, gt_path, dump_dir, replay_dir;
+    std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path;
     bool use_depth = true, quiet = false, five_point_prior = false;
     StreamParams::DepthAhead depth_ahead = StreamParams::DepthAhead::Thread;
     double min_flow = -1., time_between_keyframes = -1.;
@@ -52,6 +56,7 @@ int main(int argc, char** argv) {
         else if (arg("--gt-poses")) gt_path = argv[++i];
         else if (arg("--dump-velodyne")) dump_dir = argv[++i];
         else if (arg("--velodyne")) replay_dir = argv[++i];
+        else if (arg("--depth-params")) depth_params_path = argv[++i];
         else if (!std::strcmp(argv[i], "--no-depth")) use_depth = false;
         else if (!std::strcmp(argv[i], "--no-prefetch")) depth_ahead = StreamParams::DepthAhead::None;
         else if (arg("--depth-ahead")) {
@@ -65,7 +70,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
         else if (!std::strcmp(argv[i], "--five-point-prior")) five_point_prior = true;  // the node's prior without tf (mono_lidar.cpp:157-186)
         else {
-            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--five-point-prior] [--quiet]\n");
+            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--quiet]\n");
             return 2;
         }
     }
@@ -85,6 +90,13 @@ int main(int argc, char** argv) {
     sp.image_height = (int)world.H;
     sp.height_over_ground = synth_world::World::kHeightOverGround;
     StreamDriver driver(sp, cam, world.cam_lidar);
+    if (!depth_params_path.empty()) {
+        std::string err;
+        if (!depth_params_yaml::load(depth_params_path, &driver.depthParams(), &err)) {
+            std::fprintf(stderr, "limo_stream: --depth-params %s\n", err.c_str());
+            return 2;
+        }
+    }
 
     std::mt19937_64 rng(seed * 31 + 1);
     const int history = 10;

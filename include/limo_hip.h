@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define LIMO_ABI_VERSION 5 /* 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
+#define LIMO_ABI_VERSION 6 /* 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
 
 /* Keyframe::FixationStatus, keyframe.hpp:30 */
 enum limo_fixation { LIMO_FIX_POSE = 0, LIMO_FIX_SCALE = 1, LIMO_FIX_NONE = 2 };
@@ -63,7 +63,9 @@ enum limo_status {
                                     bundle_adjuster_keyframes.cpp:630): the caller's check; the window of
                                     ACTIVE keyframes may hold 1 or 2 and is solved like the reference does */
     LIMO_ERR_RUNTIME = -3,      /* HIP runtime error                                       */
-    LIMO_ERR_NO_DEVICE = -4     /* no gfx950 device / extension cannot run                 */
+    LIMO_ERR_NO_DEVICE = -4,    /* no gfx950 device / extension cannot run                 */
+    LIMO_ERR_UNSUPPORTED = -5   /* a setting the parameter file defines but this library does not build
+                                   (limo_last_error names the key)                          */
 };
 
 /* Termination of one Ceres-style solve (ceres::TerminationType restated). */
@@ -356,13 +358,14 @@ int limo_landmark_init(limo_ctx* ctx, int32_t n, const int32_t* ray_off /* [n+1]
 int limo_trim_quantile(int32_t n, const int64_t* ids, const double* values, double quantile, int64_t* outliers_out);
 
 /* --- LiDAR depth assignment -------------------------------------------------------------------------- */
-/* Parameters mirror mono_lidar_fusion_parameters.yaml key by key (defaults = that file). */
+/* Parameters mirror mono_lidar_fusion_parameters.yaml key by key (defaults = that file; limo_amd/kba/depth_params_yaml.hpp
+ * reads the file itself into this struct). */
 typedef struct limo_depth_params {
     int32_t pixelarea_search_width;        /* 6   yaml:14 */
     int32_t pixelarea_search_height;       /* 9   yaml:17 */
     int32_t pixelarea_search_offset_x;     /* 0   yaml:21 */
     int32_t pixelarea_search_offset_y;     /* 0   yaml:24 */
-    int32_t neighbors_count_min;           /* 3   yaml:48 */
+    int32_t neighbors_count_min;           /* 3   ours: minimum count of the rectangle search (the file has one for the radius search only, yaml:48) */
     int32_t do_use_histogram_segmentation; /* 1   yaml:58 */
     double histogram_segmentation_bin_width;   /* 0.3 yaml:61 */
     int32_t histogram_segmentation_min_pointcount; /* 1 yaml:63 */
@@ -389,8 +392,63 @@ typedef struct limo_depth_params {
     double ransac_plane_point_distance_treshold; /* 0.2 */
     int32_t plane_estimator_use_mestimator; /* 1  */
     uint64_t ransac_seed;                  /* ours: RANSAC sampling seed (deterministic) */
+    /* ---- ABI 6: the keys of the file the default configuration does not read, in the file's order.  A struct whose
+     * fields from here on are all zero selects exactly the path of ABI 5 (rectangle search, largest triangle, rejecting
+     * gates, all band returns, weighted / unweighted least-squares patch).  What each mode computes where the file
+     * leaves a choice open is written next to the code (limo_amd/csrc/depth.hip, "MODES"). */
+    int32_t neighbor_search_mode;          /* 0   yaml:5   0 = rectangle, 1 = search around the feature (below) */
+    int32_t do_use_nearestNeighborSearch;  /* 0   yaml:32  mode 1 only; != 0 -> LIMO_ERR_UNSUPPORTED */
+    int32_t nnSearch_count;                /* 10  yaml:35  */
+    int32_t do_use_radiusSearch;           /* 1   yaml:42  mode 1 only: all visible returns within the radius */
+    double radiusSearch_radius;            /* 10  yaml:45  pixels */
+    int32_t radiusSearch_count_min;        /* 3   yaml:48  fewer neighbours reject the feature */
+    int32_t do_use_depth_segmentation;     /* 0   yaml:74  != 0 -> LIMO_ERR_UNSUPPORTED */
+    double depth_segmentation_max_treshold_gradient;                        /* 10   yaml:77 */
+    double depth_segmentation_max_neighbor_distance;                        /* 0.2  yaml:79 */
+    double depth_segmentation_max_neighbor_distance_gradient;               /* 0.02 yaml:81 */
+    double depth_segmentation_max_seedpoint_to_seedpoint_distance;          /* 0.5  yaml:83 */
+    double depth_segmentation_max_seedpoint_to_seedpoint_distance_gradient; /* 0.05 yaml:85 */
+    double depth_segmentation_max_neighbor_to_seedpoint_distance;           /* 0.5  yaml:87 */
+    double depth_segmentation_max_neighbor_to_seedpoint_distance_gradient;  /* 0.05 yaml:89 */
+    int32_t depth_segmentation_max_pointcount;                              /* 4    yaml:91 */
+    int32_t treshold_depth_mode;           /* 0   yaml:99  1 = a depth outside (min, max) becomes the bound it crossed */
+    int32_t treshold_depth_local_mode;     /* 0   yaml:110 the same for the local bounds */
+    int32_t do_use_PCA;                    /* 0   yaml:119 patch by PCA; needs do_use_triangle_size_maximation == 0 */
+    double pca_debug;                      /* 0.01  yaml:120 accepted, ignored */
+    double pca_treshold_3_abs_min;         /* 0.005 yaml:121 largest eigenvalue at least this */
+    double pca_treshold_3_2_rel_max;       /* 15    yaml:122 largest <= this * middle */
+    double pca_treshold_2_1_rel_min;       /* 1.5   yaml:123 middle >= this * smallest */
+    int32_t ransac_plane_use_camx_treshold;/* 0   yaml:145 ground band limited to a corridor in front of the camera */
+    double ransac_plane_treshold_camx;     /* 0.2 yaml:147 its FULL width in metres: |x_cam| <= width / 2 */
+    int32_t plane_estimator_use_triangle_maximation; /* 0 yaml:153 ground patch = largest triangle of the patch points */
+    int32_t plane_estimator_use_leastsquares;        /* 0 yaml:156 ground patch = least squares, weights 1 */
+    double plane_estimator_z_x_min_relation;         /* 0 yaml:162 != 0 -> LIMO_ERR_UNSUPPORTED */
+    int32_t do_debug_singleFeatures;       /* 0   yaml:183 accepted, ignored */
+    int32_t do_publish_points;             /* 0   yaml:184 accepted, ignored */
+    int32_t do_depth_calc_statistics;      /* 0   yaml:185 accepted, ignored */
 } limo_depth_params;
+/* The values of the parameter file.  Settings the library refuses (every depth call, before anything is launched):
+ *   LIMO_ERR_UNSUPPORTED  do_use_depth_segmentation != 0; do_use_nearestNeighborSearch != 0 with neighbor_search_mode == 1;
+ *                         plane_estimator_z_x_min_relation != 0
+ *   LIMO_ERR_INVALID      do_use_PCA together with do_use_triangle_size_maximation; more than one plane_estimator_use_*;
+ *                         neighbor_search_mode == 1 with neither search flag set (or a mode other than 0 / 1)
+ * limo_last_error names the key. */
 void limo_depth_default_params(limo_depth_params* out);
+
+/* Which gate decided a feature (limo_depth_last_reasons).  A feature whose depth a clamping gate (treshold_depth_mode /
+ * treshold_depth_local_mode = 1) replaced by a bound carries that gate's code together with a depth. */
+enum limo_depth_reason {
+    LIMO_DEPTH_OK = 0,          /* a depth was assigned, no gate intervened                        */
+    LIMO_DEPTH_NEIGHBOURS = 1,  /* fewer neighbours than neighbors_count_min / radiusSearch_count_min */
+    LIMO_DEPTH_HISTOGRAM = 2,   /* no histogram bin is a local maximum with enough points          */
+    LIMO_DEPTH_SEGMENT3 = 3,    /* fewer than 3 points in the selected segment                     */
+    LIMO_DEPTH_PLANAR = 4,      /* largest triangle fails the planarity gate                       */
+    LIMO_DEPTH_PARALLEL = 5,    /* view ray (nearly) parallel to the patch                         */
+    LIMO_DEPTH_GLOBAL = 6,      /* global depth gate (rejected, or clamped to treshold_depth_min / _max) */
+    LIMO_DEPTH_LOCAL = 7,       /* local depth gate (rejected, or clamped to the local bound)      */
+    LIMO_DEPTH_PCA = 8,         /* eigenvalue gates of the PCA patch                               */
+    LIMO_DEPTH_DEGENERATE = 9   /* no patch: coincident points                                     */
+};
 
 /*
  * Assign a depth to each feature of one frame from one LiDAR sweep.
@@ -451,6 +509,11 @@ int limo_depth_estimate_batch(limo_ctx* ctx, int32_t n_frames, const limo_depth_
  * can look at it.
  */
 int limo_depth_last_ground_plane(limo_ctx* ctx, int32_t frame, double* plane4, int32_t* inliers /* may be NULL */);
+/*
+ * The gate that decided each feature of frame `frame` of the last launch group (enum limo_depth_reason, one byte per
+ * feature; n_feat = that frame's feature count).  Counting them answers "which gate starves my workload of depths".
+ */
+int limo_depth_last_reasons(limo_ctx* ctx, int32_t frame, uint8_t* reasons, size_t n_feat);
 /*
  * Measurement aid (bench.py `roofline_depth`): with timing on, every launch group records HIP events on the context's
  * stream around its kernels; limo_depth_last_kernel_ms returns the device time of the last group in milliseconds:

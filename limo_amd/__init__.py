@@ -7,3 +7,4 @@ ctypes bindings (`_ffi`), a numpy window container (`window`) and the synthetic 
 """
 from . import _ffi  # noqa: F401
 from .window import Window, default_options, struct_array  # noqa: F401
+from .depth_params import load_depth_params  # noqa: F401

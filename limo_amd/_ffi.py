@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LIMO_HIP_LIB") or os.path.join(_HERE, "lib", "liblimo_hip.so")  # LIMO_HIP_LIB: A/B another build of the SAME library
 
 LIMO_FIX_POSE, LIMO_FIX_SCALE, LIMO_FIX_NONE = 0, 1, 2
-LIMO_OK, LIMO_ERR_INVALID, LIMO_ERR_NOT_ENOUGH_KF, LIMO_ERR_RUNTIME, LIMO_ERR_NO_DEVICE = 0, -1, -2, -3, -4
+LIMO_OK, LIMO_ERR_INVALID, LIMO_ERR_NOT_ENOUGH_KF, LIMO_ERR_RUNTIME, LIMO_ERR_NO_DEVICE, LIMO_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 LIMO_CONVERGENCE, LIMO_NO_CONVERGENCE, LIMO_FAILURE = 0, 1, 2
 
 c_double_p = C.POINTER(C.c_double)
@@ -187,13 +187,50 @@ class DepthParams(C.Structure):  # struct limo_depth_params
         ("ransac_plane_point_distance_treshold", C.c_double),
         ("plane_estimator_use_mestimator", C.c_int32),
         ("ransac_seed", C.c_uint64),
+        # ABI 6: the rest of the parameter file, in the file's order
+        ("neighbor_search_mode", C.c_int32),
+        ("do_use_nearestNeighborSearch", C.c_int32),
+        ("nnSearch_count", C.c_int32),
+        ("do_use_radiusSearch", C.c_int32),
+        ("radiusSearch_radius", C.c_double),
+        ("radiusSearch_count_min", C.c_int32),
+        ("do_use_depth_segmentation", C.c_int32),
+        ("depth_segmentation_max_treshold_gradient", C.c_double),
+        ("depth_segmentation_max_neighbor_distance", C.c_double),
+        ("depth_segmentation_max_neighbor_distance_gradient", C.c_double),
+        ("depth_segmentation_max_seedpoint_to_seedpoint_distance", C.c_double),
+        ("depth_segmentation_max_seedpoint_to_seedpoint_distance_gradient", C.c_double),
+        ("depth_segmentation_max_neighbor_to_seedpoint_distance", C.c_double),
+        ("depth_segmentation_max_neighbor_to_seedpoint_distance_gradient", C.c_double),
+        ("depth_segmentation_max_pointcount", C.c_int32),
+        ("treshold_depth_mode", C.c_int32),
+        ("treshold_depth_local_mode", C.c_int32),
+        ("do_use_PCA", C.c_int32),
+        ("pca_debug", C.c_double),
+        ("pca_treshold_3_abs_min", C.c_double),
+        ("pca_treshold_3_2_rel_max", C.c_double),
+        ("pca_treshold_2_1_rel_min", C.c_double),
+        ("ransac_plane_use_camx_treshold", C.c_int32),
+        ("ransac_plane_treshold_camx", C.c_double),
+        ("plane_estimator_use_triangle_maximation", C.c_int32),
+        ("plane_estimator_use_leastsquares", C.c_int32),
+        ("plane_estimator_z_x_min_relation", C.c_double),
+        ("do_debug_singleFeatures", C.c_int32),
+        ("do_publish_points", C.c_int32),
+        ("do_depth_calc_statistics", C.c_int32),
     ]
+
+
+# enum limo_depth_reason: the gate that decided a feature (limo_depth_last_reasons)
+(DEPTH_OK, DEPTH_NEIGHBOURS, DEPTH_HISTOGRAM, DEPTH_SEGMENT3, DEPTH_PLANAR, DEPTH_PARALLEL, DEPTH_GLOBAL, DEPTH_LOCAL, DEPTH_PCA,
+ DEPTH_DEGENERATE) = range(10)
+DEPTH_REASON_NAMES = ["OK", "NEIGHBOURS", "HISTOGRAM", "SEGMENT3", "PLANAR", "PARALLEL", "GLOBAL", "LOCAL", "PCA", "DEGENERATE"]
 
 
 # limo_exchange_fn: (send, recv, count, kind, user) - kind 0 all-gather, 1 sum over the ranks
 EXCHANGE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_longlong, C.c_int, C.c_void_p)
 
-ABI_VERSION = 5  # LIMO_ABI_VERSION of include/limo_hip.h
+ABI_VERSION = 6  # LIMO_ABI_VERSION of include/limo_hip.h
 
 # every symbol include/limo_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -232,6 +269,7 @@ ABI_SYMBOLS = [
     "limo_depth_estimate_end",
     "limo_depth_estimate_batch",
     "limo_depth_last_ground_plane",
+    "limo_depth_last_reasons",
     "limo_depth_set_timing",
     "limo_depth_last_kernel_ms",
 ]
@@ -339,5 +377,7 @@ def load():
     lib.limo_depth_set_timing.argtypes = [vp, C.c_int32]
     lib.limo_depth_last_kernel_ms.argtypes = [vp, c_double_p]
     lib.limo_depth_last_ground_plane.argtypes = [vp, C.c_int32, c_double_p, c_int32_p]
+    if not older:
+        lib.limo_depth_last_reasons.argtypes = [vp, C.c_int32, c_uint8_p, C.c_size_t]
     _lib = lib
     return lib

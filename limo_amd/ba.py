@@ -283,6 +283,15 @@ def depth_last_ground_plane(ctx, frame=0):
     return n.value, pl
 
 
+def depth_last_reasons(ctx, n_feat, frame=0):
+    """limo_depth_last_reasons: the gate that decided each of the n_feat features of a frame of the last depth call on
+    this context (uint8 array of _ffi.DEPTH_* codes)."""
+    out = np.zeros(n_feat, np.uint8)
+    rc = ctx.lib.limo_depth_last_reasons(ctx.ptr, frame, out.ctypes.data_as(_ffi.c_uint8_p), n_feat)
+    _check(rc, ctx.ptr, "limo_depth_last_reasons")
+    return out
+
+
 def depth_estimate_batch(ctx, frames, params=None, use_ground_labels=True, device=False):
     """limo_depth_estimate_batch over a list of frame dicts of one rig (calibration of frames[0]).
     device=False: numpy clouds / features in, list of float32 depth arrays out.

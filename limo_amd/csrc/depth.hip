@@ -39,6 +39,33 @@
 // HBM bytes moved (16 B / return + 20 B / visible return; 212 B / feature): k_project reads 16 B / return
 // and writes 4 B / visible return + 4 B / band return; k_ransac / k_refine read 16 B / return; k_features reads
 // ~20 B / candidate return (index + record) + 8 B / cell.
+//
+// MODES.  limo_depth_params carries every key of the parameter file; a struct whose ABI-6 part is zero runs exactly the
+// path above.  The estimator's source is absent, so where the file leaves a choice open the choice made here is the
+// contract (tests/cpp/depth_modes_ref.cpp restates all of it on the CPU and the GPU tests compare bit for bit):
+//   radius search   neighbor_search_mode 1 + do_use_radiusSearch: neighbours = visible returns with
+//                   (u-fu)*(u-fu) + (v-fv)*(v-fv) <= radius*radius, circle centred on the feature (the rectangle's offsets
+//                   do not apply), list in return order; fewer than radiusSearch_count_min -> NEIGHBOURS
+//                   (neighbors_count_min is the rectangle's key and is not read).  Up to 128 neighbours (k_features<true>,
+//                   its own LDS layout; the rectangle keeps 64).
+//   PCA patch       do_use_PCA 1, do_use_triangle_size_maximation 0, on the segment the histogram keeps (>= 3 points):
+//                   centroid = (sequential sum) / n, scatter = (sequential sum of e e^T) / n, cyclic Jacobi, eigenvalues
+//                   l1 <= l2 <= l3; PCA unless l3 >= pca_treshold_3_abs_min, l3 <= pca_treshold_3_2_rel_max * l2 and
+//                   l2 >= pca_treshold_2_1_rel_min * l1; plane through the centroid, normal = eigenvector of l1; then the
+//                   ray / plane step and the gates as for the triangle.  The triangle's planarity key is not read.
+//   clamp modes     treshold_depth_mode 1: a depth <= min becomes min, >= max becomes max (the local gate then sees that
+//                   value); treshold_depth_local_mode 1: < lo becomes lo, > hi becomes hi.  NaN is rejected.  The reason
+//                   code of a clamped feature is the gate's (GLOBAL / LOCAL; the later gate wins).
+//   corridor        ransac_plane_use_camx_treshold 1: a band return takes part in RANSAC and in the refinement only if
+//                   |x_cam| <= ransac_plane_treshold_camx / 2 ("width" = full width).
+//   ground patch    plane_estimator_use_mestimator: weights 1 / (|dist| + 0.01); _use_leastsquares or none: weights 1;
+//                   _use_triangle_maximation: plane through the largest triangle of the patch points (first maximum in
+//                   (i<j<k) order), with the planarity gate when do_check_triangleplanar_condition; a patch of fewer than
+//                   3 points, one that fails the gate or is degenerate, or whose normal has |n . n_ground| < 0.9 falls back
+//                   to the sweep's plane.
+// Refused before anything is launched (check_params): depth segmentation, nearest-neighbour search, z/x flatness relation
+// (LIMO_ERR_UNSUPPORTED), contradictory settings (LIMO_ERR_INVALID).
+// k_features writes the code of the gate that decided a feature (enum limo_depth_reason) beside its depth.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
@@ -54,7 +81,8 @@ namespace {
 
 constexpr int kCell = 8;        // pixels per image cell
 constexpr int kCellCap = 48;    // returns kept per cell (a spinning 64-beam scanner: 5-13 per cell); more => LIMO_ERR_INVALID
-constexpr int kMaxNb = 64;      // neighbours per feature; more => LIMO_ERR_INVALID
+constexpr int kMaxNb = 64;      // neighbours per feature (rectangle search); more => LIMO_ERR_INVALID
+constexpr int kMaxNbRadius = 128;  // ... of the radius search (10 px at 4000 azimuth steps: up to 74)
 constexpr int kMaxBins = 512;   // histogram bins per feature (0.3 m bins => 150 m of depth range)
 constexpr int kMaxHyp = 4096;   // RANSAC hypotheses
 constexpr int kMaxBatch = 32;   // frames per launch group (per-frame sizes and pointers travel as kernel arguments)
@@ -80,6 +108,8 @@ struct DepthView {
     const float* feat_uv[kMaxBatch];
     const uint8_t* feat_ground[kMaxBatch];  // null: no ground labels
     float* out[kMaxBatch];
+    uint8_t* reasons;                 // [frame][feat_stride] enum limo_depth_reason of every feature
+    size_t feat_stride;
     int n_pts[kMaxBatch], n_feat[kMaxBatch];
     // workspace; frame f lives at base + f * stride
     size_t pt_stride;                 // returns
@@ -114,7 +144,10 @@ __device__ __forceinline__ bool pixel_of(const DepthView& d, const Cam& c, doubl
 }
 __device__ __forceinline__ bool in_band(const DepthView& d, const float4 q) {
     const double z = q.z;
-    return z >= d.p.ransac_plane_min_z && z <= d.p.ransac_plane_max_z;
+    if (!(z >= d.p.ransac_plane_min_z && z <= d.p.ransac_plane_max_z)) return false;
+    // corridor in front of the camera (MODES): camera-frame x of the return, the statement of cam_point
+    if (d.p.ransac_plane_use_camx_treshold && !(fabs(cam_point(d, q).x) <= d.p.ransac_plane_treshold_camx / 2.0)) return false;
+    return true;
 }
 __device__ __forceinline__ float4 load_return(const float* cloud, int i) { return reinterpret_cast<const float4*>(cloud)[i]; }
 
@@ -458,7 +491,8 @@ __device__ __forceinline__ void jacobi_rot(double (&a)[3][3], double (&V)[3][3])
     }
 }
 
-__device__ void smallest_eigvec(const double* C6, double* n) {  // C6 = xx xy xz yy yz zz
+// n = unit eigenvector of the smallest eigenvalue; lam (may be null) = the three eigenvalues in ascending order
+__device__ void eig_sym3(const double* C6, double* n, double* lam) {  // C6 = xx xy xz yy yz zz
     double a[3][3] = {{C6[0], C6[1], C6[2]}, {C6[1], C6[3], C6[4]}, {C6[2], C6[4], C6[5]}};
     double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
     for (int sweep = 0; sweep < 50; ++sweep) {
@@ -478,7 +512,14 @@ __device__ void smallest_eigvec(const double* C6, double* n) {  // C6 = xx xy xz
     n[0] = v0 / nn;
     n[1] = v1 / nn;
     n[2] = v2 / nn;
+    if (lam) {
+        const double ea = m == 0 ? e1 : e0, eb = m == 2 ? e1 : e2;  // the other two diagonal entries
+        lam[0] = m == 0 ? e0 : m == 1 ? e1 : e2;
+        lam[1] = eb < ea ? eb : ea;
+        lam[2] = eb < ea ? ea : eb;
+    }
 }
+__device__ __forceinline__ void smallest_eigvec(const double* C6, double* n) { eig_sym3(C6, n, nullptr); }
 
 // One wave per frame, after k_refine: the ground plane of the frame (n, d with n.p + d = 0, d >= 0: the camera is on the
 // positive side).
@@ -536,23 +577,88 @@ __device__ __forceinline__ double sin_at(const double* o, const double* a, const
     return sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) / (n1 * n2);
 }
 
+template <int NB>
 struct WaveLds {
     int cell_off[65];       // exclusive prefix of the candidate counts of the cells under the rectangle
-    int tmp_idx[kMaxNb];    // neighbours in arrival order
-    double tmp_xyz[kMaxNb][3];
-    int nb_idx[kMaxNb];     // neighbours ordered by return index
-    double nb_xyz[kMaxNb][3];
-    double seg[kMaxNb][3];  // points of the selected histogram bin / ground patch
+    int tmp_idx[NB];        // neighbours in arrival order
+    double tmp_xyz[NB][3];
+    int nb_idx[NB];         // neighbours ordered by return index
+    double nb_xyz[NB][3];
+    double seg[NB][3];      // points of the selected histogram bin / ground patch
     int bins[kMaxBins];
 };
 
+// D4: the three points of seg[0..nseg) spanning the largest triangle: every lane takes point pairs (i<j) and scans k>j; wave
+// arg-max with the lexicographically first (i,j,k) among equal areas.  best < 0: nothing compared (NaN coordinates).
+struct Tri {
+    double best;
+    int i, j, k;
+};
+__device__ __forceinline__ Tri max_triangle(const double (*seg)[3], int nseg, int lane) {
+    double best = -1.0;
+    int bi = 0x7fff, bj = 0x7fff, bk = 0x7fff;
+    for (int pq = lane; pq < nseg * nseg; pq += 64) {
+        const int i = pq / nseg, j = pq % nseg;
+        if (j <= i) continue;
+        const double e1[3] = {seg[j][0] - seg[i][0], seg[j][1] - seg[i][1], seg[j][2] - seg[i][2]};
+        for (int l = j + 1; l < nseg; ++l) {
+            const double e2[3] = {seg[l][0] - seg[i][0], seg[l][1] - seg[i][1], seg[l][2] - seg[i][2]};
+            const double c0 = e1[1] * e2[2] - e1[2] * e2[1], c1 = e1[2] * e2[0] - e1[0] * e2[2], c2 = e1[0] * e2[1] - e1[1] * e2[0];
+            const double a2 = c0 * c0 + c1 * c1 + c2 * c2;
+            if (a2 > best) {  // pairs are visited in increasing (i,j), l increasing: first maximum wins
+                best = a2;
+                bi = i;
+                bj = j;
+                bk = l;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64), oj = __shfl_xor(bj, off, 64), ok2 = __shfl_xor(bk, off, 64);
+        const bool better = ob > best || (ob == best && (oi < bi || (oi == bi && (oj < bj || (oj == bj && ok2 < bk)))));
+        if (better) {
+            best = ob;
+            bi = oi;
+            bj = oj;
+            bk = ok2;
+        }
+    }
+    return {best, bi, bj, bk};
+}
+
+// Plane (unit normal pn, offset pd) through the triangle A B C: LIMO_DEPTH_OK, or the gate that refuses it.
+__device__ __forceinline__ int triangle_plane(const DepthView& d, const double* A, const double* B, const double* Cc, double* pn, double* pd) {
+    if (d.p.do_check_triangleplanar_condition) {
+        const double s = fmin(sin_at(A, B, Cc), fmin(sin_at(B, A, Cc), sin_at(Cc, A, B)));
+        if (s < d.p.triangleplanar_crossnorm_treshold) return LIMO_DEPTH_PLANAR;
+    }
+    const double e1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, e2[3] = {Cc[0] - A[0], Cc[1] - A[1], Cc[2] - A[2]};
+    pn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+    pn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+    pn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+    const double nn = sqrt(pn[0] * pn[0] + pn[1] * pn[1] + pn[2] * pn[2]);
+    if (!(nn > 0.0)) return LIMO_DEPTH_DEGENERATE;
+    pn[0] /= nn;
+    pn[1] /= nn;
+    pn[2] /= nn;
+    *pd = -(pn[0] * A[0] + pn[1] * A[1] + pn[2] * A[2]);
+    return LIMO_DEPTH_OK;
+}
+
+// RADIUS: the neighbour search of neighbor_search_mode 1 (circle, up to kMaxNbRadius neighbours: two per lane) instead of
+// the rectangle.  EXT: some other mode of the ABI-6 part of the parameters is on (PCA patch, clamping gates, triangle
+// ground patch); the <false, false> kernel is the path of the default configuration and reads none of those keys.
+template <bool RADIUS, bool EXT>
 __global__ __launch_bounds__(256) void k_features(DepthView d) {
-    __shared__ WaveLds lds[4];
+    constexpr int NB = RADIUS ? kMaxNbRadius : kMaxNb;
+    constexpr int PER = NB / 64;  // neighbours per lane
+    __shared__ WaveLds<NB> lds[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int fr = blockIdx.y;
     const int k = blockIdx.x * 4 + wave;
     if (k >= d.n_feat[fr]) return;  // whole wave exits together
-    WaveLds& L = lds[wave];
+    WaveLds<NB>& L = lds[wave];
     const int* cell_count = d.zone + (size_t)fr * d.zone_stride;
     const int* cell_pts = d.cell_pts + (size_t)fr * d.n_cells * kCellCap;
     const double* plane = d.plane + 8 * (size_t)fr;
@@ -560,11 +666,14 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
     const float* feat_uv = d.feat_uv[fr];
     const uint8_t* feat_ground = d.feat_ground[fr];
     const double fu = feat_uv[2 * (size_t)k], fv = feat_uv[2 * (size_t)k + 1];
-    const double hw = 0.5 * d.p.pixelarea_search_width, hh = 0.5 * d.p.pixelarea_search_height;
-    const double cu = fu + d.p.pixelarea_search_offset_x, cv = fv + d.p.pixelarea_search_offset_y;
-    // ---- D2: candidates = the returns listed in the cells under the rectangle.  All cells in one pass: lane c takes the
-    //      count of cell c, a wave prefix sum gives every candidate a lane (three dependent loads per pass - count, index,
-    //      record - instead of three per cell); the rectangle test uses the pixel recomputed from the record.
+    const double hw = RADIUS ? d.p.radiusSearch_radius : 0.5 * d.p.pixelarea_search_width;
+    const double hh = RADIUS ? d.p.radiusSearch_radius : 0.5 * d.p.pixelarea_search_height;
+    const double cu = RADIUS ? fu : fu + d.p.pixelarea_search_offset_x, cv = RADIUS ? fv : fv + d.p.pixelarea_search_offset_y;
+    const double r2 = d.p.radiusSearch_radius * d.p.radiusSearch_radius;
+    // ---- D2: candidates = the returns listed in the cells under the rectangle (the circle's bounding square).  All cells in
+    //      one pass: lane c takes the count of cell c, a wave prefix sum gives every candidate a lane (three dependent loads
+    //      per pass - count, index, record - instead of three per cell); the rectangle / circle test uses the pixel
+    //      recomputed from the record.
     const int cx0 = max(0, (int)floor((cu - hw) / kCell)), cx1 = min(d.cells_x - 1, (int)floor((cu + hw) / kCell));
     const int cy0 = max(0, (int)floor((cv - hh) / kCell)), cy1 = min(d.cells_y - 1, (int)floor((cv + hh) / kCell));
     const int ncx = max(0, cx1 - cx0 + 1), ncell = ncx * max(0, cy1 - cy0 + 1);
@@ -606,12 +715,20 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
                 idx = cell_pts[(size_t)cl * kCellCap + (j - L.cell_off[lo])];
                 P = cam_point(d, load_return(cloud, idx));
                 double u, v;
-                in = pixel_of(d, P, &u, &v) && fabs(u - cu) <= hw && fabs(v - cv) <= hh;
+                if (RADIUS) {
+                    in = pixel_of(d, P, &u, &v);
+                    if (in) {
+                        const double du = u - fu, dv = v - fv;
+                        in = du * du + dv * dv <= r2;
+                    }
+                } else {
+                    in = pixel_of(d, P, &u, &v) && fabs(u - cu) <= hw && fabs(v - cv) <= hh;
+                }
             }
             const unsigned long long m = __ballot(in);
             if (in) {
                 const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
-                if (pos < kMaxNb) {
+                if (pos < NB) {
                     L.tmp_idx[pos] = idx;
                     L.tmp_xyz[pos][0] = P.x;
                     L.tmp_xyz[pos][1] = P.y;
@@ -622,35 +739,45 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (n > kMaxNb) {
+    if (n > NB) {
         ovf |= OVF_NEIGHBOURS;
-        n = kMaxNb;
+        n = NB;
     }
     if (ovf) *reinterpret_cast<volatile int*>(d.overflow) = (int)ovf;  // pinned host word; the call then fails with LIMO_ERR_INVALID
     // order by return index (rank sort inside the wave) so every later step sees the lidar order the oracle sees
     __builtin_amdgcn_wave_barrier();
-    if (lane < n) {
-        const int mine = L.tmp_idx[lane];
-        int rank = 0;
-        for (int q = 0; q < n; ++q) rank += L.tmp_idx[q] < mine;
-        L.nb_idx[rank] = mine;
-        L.nb_xyz[rank][0] = L.tmp_xyz[lane][0];
-        L.nb_xyz[rank][1] = L.tmp_xyz[lane][1];
-        L.nb_xyz[rank][2] = L.tmp_xyz[lane][2];
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+        const int me = lane + 64 * r;
+        if (me < n) {
+            const int mine = L.tmp_idx[me];
+            int rank = 0;
+            for (int q = 0; q < n; ++q) rank += L.tmp_idx[q] < mine;
+            L.nb_idx[rank] = mine;
+            L.nb_xyz[rank][0] = L.tmp_xyz[me][0];
+            L.nb_xyz[rank][1] = L.tmp_xyz[me][1];
+            L.nb_xyz[rank][2] = L.tmp_xyz[me][2];
+        }
     }
     __builtin_amdgcn_wave_barrier();
     float result = -1.0f;
-    if (n >= d.p.neighbors_count_min) {
+    int reason = LIMO_DEPTH_NEIGHBOURS;  // (lane 0 holds the code that is written)
+    if (n >= (RADIUS ? d.p.radiusSearch_count_min : d.p.neighbors_count_min)) {
         const bool ground_feat = feat_ground && feat_ground[k] && plane[4] != 0.0;
         double depth = -1.0, zlo = 0.0, zhi = 0.0;
         bool have = false;
+        reason = LIMO_DEPTH_DEGENERATE;
         if (ground_feat) {
-            // ---- D6b: inverse-distance weighted patch over the neighbours close to the sweep's ground plane (lane 0,
-            //      sequential in return order: the oracle's summation order)
+            // ---- D6b: patch over the neighbours close to the sweep's ground plane (lane 0, sequential in return order: the
+            //      oracle's summation order): inverse-distance weighted or unweighted least squares, or (MODES) the largest
+            //      triangle
+            const bool tri_patch = EXT && d.p.plane_estimator_use_triangle_maximation;
+            const double gn[3] = {plane[0], plane[1], plane[2]}, gd = plane[3];
+            double pn[3] = {gn[0], gn[1], gn[2]}, pd = gd;
+            bool local = false;
+            int m = 0;
             if (lane == 0) {
-                const double gn[3] = {plane[0], plane[1], plane[2]}, gd = plane[3];
                 double sw = 0, c[3] = {0, 0, 0};
-                int m = 0;
                 zlo = 1.79769313486231570e308;
                 zhi = -zlo;
                 double* wgt = reinterpret_cast<double*>(L.bins);  // weights parked in the (unused) histogram storage
@@ -670,9 +797,7 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
                         ++m;
                     }
                 }
-                double pn[3] = {gn[0], gn[1], gn[2]}, pd = gd;
-                bool local = false;
-                if (m >= 3) {
+                if (!tri_patch && m >= 3) {
                     for (int a = 0; a < 3; ++a) c[a] /= sw;
                     double C6[6] = {0, 0, 0, 0, 0, 0};
                     for (int q = 0; q < m; ++q) {
@@ -695,19 +820,43 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
                         pd = -(ln[0] * c[0] + ln[1] * c[1] + ln[2] * c[2]);
                     }
                 }
+            }
+            if (tri_patch) {
+                m = __shfl(m, 0, 64);
+                __builtin_amdgcn_wave_barrier();
+                if (m >= 3) {
+                    const Tri t = max_triangle(L.seg, m, lane);
+                    double ln[3], ld;
+                    if (lane == 0 && t.best >= 0.0 && triangle_plane(d, L.seg[t.i], L.seg[t.j], L.seg[t.k], ln, &ld) == LIMO_DEPTH_OK &&
+                        fabs(ln[0] * gn[0] + ln[1] * gn[1] + ln[2] * gn[2]) >= 0.9) {
+                        local = true;
+                        pn[0] = ln[0];
+                        pn[1] = ln[1];
+                        pn[2] = ln[2];
+                        pd = ld;
+                    }
+                }
+            }
+            if (lane == 0) {
                 if (!local) {
                     zlo = 0.0;
                     zhi = 1.79769313486231570e308;
                 }
                 have = ray_plane_depth(pn, pd, fu, fv, d, &depth);
+                if (!have) reason = LIMO_DEPTH_PARALLEL;
             }
         } else {
             // ---- D3: depth histogram, nearest local maximum
             double zmin = 1.79769313486231570e308, zmax = -1.79769313486231570e308;
-            double myz = 0.0;
-            if (lane < n) {
-                myz = L.nb_xyz[lane][2];
-                zmin = zmax = myz;
+            double myz[PER];
+#pragma unroll
+            for (int r = 0; r < PER; ++r) {
+                myz[r] = 0.0;
+                if (lane + 64 * r < n) {
+                    myz[r] = L.nb_xyz[lane + 64 * r][2];
+                    zmin = fmin(zmin, myz[r]);
+                    zmax = fmax(zmax, myz[r]);
+                }
             }
             for (int off = 32; off > 0; off >>= 1) {
                 zmin = fmin(zmin, __shfl_xor(zmin, off, 64));
@@ -724,10 +873,14 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
                     const int nbins = (int)span + 1;
                     for (int b = lane; b < nbins; b += 64) L.bins[b] = 0;
                     __builtin_amdgcn_wave_barrier();
-                    int mybin = -1;
-                    if (lane < n) {
-                        mybin = min(nbins - 1, (int)floor((myz - zmin) / bw));
-                        atomicAdd(&L.bins[mybin], 1);
+                    int mybin[PER];
+#pragma unroll
+                    for (int r = 0; r < PER; ++r) {
+                        mybin[r] = -1;
+                        if (lane + 64 * r < n) {
+                            mybin[r] = min(nbins - 1, (int)floor((myz[r] - zmin) / bw));
+                            atomicAdd(&L.bins[mybin[r]], 1);
+                        }
                     }
                     __builtin_amdgcn_wave_barrier();
                     int pick = 0x7fffffff;
@@ -739,102 +892,117 @@ __global__ __launch_bounds__(256) void k_features(DepthView d) {
                     if (pick == 0x7fffffff) {
                         seg_ok = false;
                     } else {
-                        const bool mine = lane < n && mybin == pick;
-                        const unsigned long long m = __ballot(mine);
-                        if (mine) {
-                            const int pos = __popcll(m & ((1ull << lane) - 1ull));
-                            L.seg[pos][0] = L.nb_xyz[lane][0];
-                            L.seg[pos][1] = L.nb_xyz[lane][1];
-                            L.seg[pos][2] = L.nb_xyz[lane][2];
+#pragma unroll
+                        for (int r = 0; r < PER; ++r) {  // (neighbours 0..63, then 64..127: the segment keeps return order)
+                            const bool mine = lane + 64 * r < n && mybin[r] == pick;
+                            const unsigned long long m = __ballot(mine);
+                            if (mine) {
+                                const int pos = nseg + __popcll(m & ((1ull << lane) - 1ull));
+                                L.seg[pos][0] = L.nb_xyz[lane + 64 * r][0];
+                                L.seg[pos][1] = L.nb_xyz[lane + 64 * r][1];
+                                L.seg[pos][2] = L.nb_xyz[lane + 64 * r][2];
+                            }
+                            nseg += __popcll(m);
                         }
-                        nseg = __popcll(m);
                     }
                 }
             } else {
-                if (lane < n) {
-                    L.seg[lane][0] = L.nb_xyz[lane][0];
-                    L.seg[lane][1] = L.nb_xyz[lane][1];
-                    L.seg[lane][2] = L.nb_xyz[lane][2];
-                }
+#pragma unroll
+                for (int r = 0; r < PER; ++r)
+                    if (lane + 64 * r < n) {
+                        L.seg[lane + 64 * r][0] = L.nb_xyz[lane + 64 * r][0];
+                        L.seg[lane + 64 * r][1] = L.nb_xyz[lane + 64 * r][1];
+                        L.seg[lane + 64 * r][2] = L.nb_xyz[lane + 64 * r][2];
+                    }
                 nseg = n;
             }
             __builtin_amdgcn_wave_barrier();
+            if (!seg_ok) reason = LIMO_DEPTH_HISTOGRAM;
+            else if (nseg < 3) reason = LIMO_DEPTH_SEGMENT3;
             if (seg_ok && nseg >= 3) {
-                // ---- D4: largest triangle: every lane takes point pairs (i<j) and scans k>j; wave arg-max with the
-                //      lexicographically first (i,j,k) among equal areas
-                double best = -1.0;
-                int bi = 0x7fff, bj = 0x7fff, bk = 0x7fff;
-                for (int pq = lane; pq < nseg * nseg; pq += 64) {
-                    const int i = pq / nseg, j = pq % nseg;
-                    if (j <= i) continue;
-                    const double e1[3] = {L.seg[j][0] - L.seg[i][0], L.seg[j][1] - L.seg[i][1], L.seg[j][2] - L.seg[i][2]};
-                    for (int l = j + 1; l < nseg; ++l) {
-                        const double e2[3] = {L.seg[l][0] - L.seg[i][0], L.seg[l][1] - L.seg[i][1], L.seg[l][2] - L.seg[i][2]};
-                        const double c0 = e1[1] * e2[2] - e1[2] * e2[1], c1 = e1[2] * e2[0] - e1[0] * e2[2], c2 = e1[0] * e2[1] - e1[1] * e2[0];
-                        const double a2 = c0 * c0 + c1 * c1 + c2 * c2;
-                        if (a2 > best) {  // pairs are visited in increasing (i,j), l increasing: first maximum wins
-                            best = a2;
-                            bi = i;
-                            bj = j;
-                            bk = l;
+                double pn[3], pd = 0.0;
+                int why = LIMO_DEPTH_DEGENERATE;
+                if (EXT && d.p.do_use_PCA && !d.p.do_use_triangle_size_maximation) {
+                    // ---- PCA patch (MODES), lane 0, sequential in segment order
+                    if (lane == 0) {
+                        const double nn = (double)nseg;
+                        double c[3] = {0, 0, 0};
+                        for (int q = 0; q < nseg; ++q)
+                            for (int a = 0; a < 3; ++a) c[a] += L.seg[q][a];
+                        for (int a = 0; a < 3; ++a) c[a] /= nn;
+                        double C6[6] = {0, 0, 0, 0, 0, 0};
+                        for (int q = 0; q < nseg; ++q) {
+                            const double e[3] = {L.seg[q][0] - c[0], L.seg[q][1] - c[1], L.seg[q][2] - c[2]};
+                            C6[0] += e[0] * e[0];
+                            C6[1] += e[0] * e[1];
+                            C6[2] += e[0] * e[2];
+                            C6[3] += e[1] * e[1];
+                            C6[4] += e[1] * e[2];
+                            C6[5] += e[2] * e[2];
+                        }
+                        for (int a = 0; a < 6; ++a) C6[a] /= nn;
+                        double lam[3];
+                        eig_sym3(C6, pn, lam);
+                        if (lam[2] >= d.p.pca_treshold_3_abs_min && lam[2] <= d.p.pca_treshold_3_2_rel_max * lam[1] &&
+                            lam[1] >= d.p.pca_treshold_2_1_rel_min * lam[0]) {
+                            pd = -(pn[0] * c[0] + pn[1] * c[1] + pn[2] * c[2]);
+                            why = LIMO_DEPTH_OK;
+                        } else {
+                            why = LIMO_DEPTH_PCA;
                         }
                     }
+                } else {
+                    // ---- D4: plane through the largest triangle
+                    const Tri t = max_triangle(L.seg, nseg, lane);
+                    if (lane == 0 && t.best >= 0.0) why = triangle_plane(d, L.seg[t.i], L.seg[t.j], L.seg[t.k], pn, &pd);
                 }
-                for (int off = 32; off > 0; off >>= 1) {
-                    const double ob = __shfl_xor(best, off, 64);
-                    const int oi = __shfl_xor(bi, off, 64), oj = __shfl_xor(bj, off, 64), ok2 = __shfl_xor(bk, off, 64);
-                    const bool better = ob > best || (ob == best && (oi < bi || (oi == bi && (oj < bj || (oj == bj && ok2 < bk)))));
-                    if (better) {
-                        best = ob;
-                        bi = oi;
-                        bj = oj;
-                        bk = ok2;
-                    }
-                }
-                if (lane == 0 && best >= 0.0) {
-                    const double* A = L.seg[bi];
-                    const double* B = L.seg[bj];
-                    const double* Cc = L.seg[bk];
-                    bool ok = true;
-                    if (d.p.do_check_triangleplanar_condition) {
-                        const double s = fmin(sin_at(A, B, Cc), fmin(sin_at(B, A, Cc), sin_at(Cc, A, B)));
-                        if (s < d.p.triangleplanar_crossnorm_treshold) ok = false;
-                    }
-                    if (ok) {
-                        const double e1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, e2[3] = {Cc[0] - A[0], Cc[1] - A[1], Cc[2] - A[2]};
-                        double pn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-                        const double nn = sqrt(pn[0] * pn[0] + pn[1] * pn[1] + pn[2] * pn[2]);
-                        if (nn > 0.0) {
-                            pn[0] /= nn;
-                            pn[1] /= nn;
-                            pn[2] /= nn;
-                            const double pd = -(pn[0] * A[0] + pn[1] * A[1] + pn[2] * A[2]);
-                            have = ray_plane_depth(pn, pd, fu, fv, d, &depth);
-                            zlo = 1.79769313486231570e308;
-                            zhi = -zlo;
-                            for (int q = 0; q < nseg; ++q) {
-                                zlo = fmin(zlo, L.seg[q][2]);
-                                zhi = fmax(zhi, L.seg[q][2]);
-                            }
+                if (lane == 0) {
+                    reason = why;
+                    if (why == LIMO_DEPTH_OK) {
+                        have = ray_plane_depth(pn, pd, fu, fv, d, &depth);
+                        if (!have) reason = LIMO_DEPTH_PARALLEL;
+                        zlo = 1.79769313486231570e308;
+                        zhi = -zlo;
+                        for (int q = 0; q < nseg; ++q) {
+                            zlo = fmin(zlo, L.seg[q][2]);
+                            zhi = fmax(zhi, L.seg[q][2]);
                         }
                     }
                 }
             }
         }
-        // ---- D5: gates
+        // ---- D5: gates (rejecting; clamping in the modes of MODES)
         if (lane == 0 && have) {
             bool ok = true;
-            if (d.p.treshold_depth_enabled && !(depth > d.p.treshold_depth_min && depth < d.p.treshold_depth_max)) ok = false;
+            reason = LIMO_DEPTH_OK;
+            if (d.p.treshold_depth_enabled && !(depth > d.p.treshold_depth_min && depth < d.p.treshold_depth_max)) {
+                reason = LIMO_DEPTH_GLOBAL;
+                if (EXT && d.p.treshold_depth_mode && depth == depth)
+                    depth = depth <= d.p.treshold_depth_min ? d.p.treshold_depth_min : d.p.treshold_depth_max;
+                else
+                    ok = false;
+            }
             if (ok && d.p.treshold_depth_local_enabled) {
                 const double v = d.p.treshold_depth_local_value;
                 const double lo = d.p.treshold_depth_local_valuetype ? zlo * (1.0 - v) : zlo - v;
                 const double hi = d.p.treshold_depth_local_valuetype ? zhi * (1.0 + v) : zhi + v;
-                if (!(depth >= lo && depth <= hi)) ok = false;
+                if (!(depth >= lo && depth <= hi)) {
+                    reason = LIMO_DEPTH_LOCAL;
+                    if (EXT && d.p.treshold_depth_local_mode && depth < lo)
+                        depth = lo;
+                    else if (EXT && d.p.treshold_depth_local_mode && depth > hi)
+                        depth = hi;
+                    else
+                        ok = false;
+                }
             }
             if (ok) result = (float)depth;
         }
     }
-    if (lane == 0) d.out[fr][k] = result;
+    if (lane == 0) {
+        d.out[fr][k] = result;
+        d.reasons[(size_t)fr * d.feat_stride + k] = (uint8_t)reason;
+    }
 }
 
 // ------------------------------------------------------------------------------------------ workspace
@@ -847,6 +1015,8 @@ struct DepthWs {
     int cur = 0;                     // zone of the next call
     int last_frames = 0;             // frames of the last launch group (limo_depth_last_ground_plane)
     uint32_t last_ground_mask = 0;
+    size_t last_n_feat[kMaxBatch] = {};  // features per frame of the last launch group (limo_depth_last_reasons)
+    bool last_radius = false;        // the last launch group searched by radius (text of the overflow error)
     bool last_timed = false;         // the last enqueued group recorded its events
     bool open = false;               // a limo_depth_estimate_begin whose _end has not been called
     size_t open_feat = 0;            // its n_feat
@@ -857,12 +1027,12 @@ struct DepthWs {
     int *cell_pts = nullptr, *band_idx = nullptr, *band_n = nullptr, *pick = nullptr, *zone[2] = {nullptr, nullptr};
     double* plane = nullptr;
     float *feat_uv = nullptr, *out = nullptr;
-    uint8_t* feat_ground = nullptr;
+    uint8_t *feat_ground = nullptr, *reasons = nullptr;
     float* h_feat = nullptr;   // pinned staging: uv of every frame, then the ground labels; and the depths coming back
     float* h_out = nullptr;
     int* h_ovf = nullptr;      // pinned word the kernels raise when a capacity of this file is exceeded
     void release() {
-        void* ptrs[] = {cloud, cell_pts, band_idx, band_n, pick, zone[0], zone[1], plane, feat_uv, out, feat_ground};
+        void* ptrs[] = {cloud, cell_pts, band_idx, band_n, pick, zone[0], zone[1], plane, feat_uv, out, feat_ground, reasons};
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
         if (h_feat) (void)hipHostFree(h_feat);
@@ -917,6 +1087,7 @@ int ensure_capacity(limo_ctx* ctx, DepthWs& W, int frames, size_t n_pts, size_t 
     rc |= grow(ctx, &W.feat_uv, (size_t)F * Q * 2);
     rc |= grow(ctx, &W.feat_ground, (size_t)F * Q);
     rc |= grow(ctx, &W.out, (size_t)F * Q);
+    rc |= grow(ctx, &W.reasons, (size_t)F * Q);
     // zone of a frame: cell counters | inlier counts | counters | moments (64-bit) | scan words (64-bit, 8-byte aligned)
     W.off_hyp = (int)round_up(C, 2);
     W.off_ctr = W.off_hyp + kMaxHyp;
@@ -1011,6 +1182,8 @@ int enqueue_group(limo_ctx* ctx, int n_frames, const limo_depth_frame* frames, c
     d.plane = W.plane;
     d.pick = W.pick;
     d.overflow = W.h_ovf;
+    d.reasons = W.reasons;
+    d.feat_stride = W.cap_feat;
     const int z = W.cur;
     d.zone = W.zone[z];
     d.zone_next = W.zone[z ^ 1];
@@ -1061,6 +1234,12 @@ int enqueue_group(limo_ctx* ctx, int n_frames, const limo_depth_frame* frames, c
     W.cur = z ^ 1;
     W.last_frames = n_frames;
     W.last_ground_mask = d.ground_mask;
+    for (int k = 0; k < n_frames; ++k) W.last_n_feat[k] = frames[k].n_feat;
+    // which k_features: the search mode, and whether any other mode of the ABI-6 part of the parameters is on
+    const bool radius = p.neighbor_search_mode == 1;
+    const bool ext = radius || (p.do_use_PCA && !p.do_use_triangle_size_maximation) || p.treshold_depth_mode || p.treshold_depth_local_mode ||
+                     p.plane_estimator_use_triangle_maximation;
+    W.last_radius = radius;
     const unsigned F = (unsigned)n_frames;
     auto mark = [&](int k) {
         if (W.timing) (void)hipEventRecord(W.ev[k], s);
@@ -1080,7 +1259,13 @@ int enqueue_group(limo_ctx* ctx, int n_frames, const limo_depth_frame* frames, c
     }
     mark(2);
     if (max_feat) {
-        hipLaunchKernelGGL(k_features, dim3((unsigned)((max_feat + 3) / 4), F), dim3(256), 0, s, d);
+        const dim3 grid((unsigned)((max_feat + 3) / 4), F);
+        if (radius)
+            hipLaunchKernelGGL((k_features<true, true>), grid, dim3(256), 0, s, d);
+        else if (ext)
+            hipLaunchKernelGGL((k_features<false, true>), grid, dim3(256), 0, s, d);
+        else
+            hipLaunchKernelGGL((k_features<false, false>), grid, dim3(256), 0, s, d);
         mark(3);
         if (!device_ptrs) HIP_TRY(ctx, hipMemcpyAsync(W.h_out, W.out, sizeof(float) * Q * n_frames, hipMemcpyDeviceToHost, s));
     }
@@ -1102,10 +1287,29 @@ int finish_group(limo_ctx* ctx, DepthWs& W) {
         W.last_ms[3] = (double)a + b + c;
     }
     if (*W.h_ovf) {
-        ctx->err = std::string("limo_depth_estimate: ") + ((*W.h_ovf & OVF_CELL) ? "more than 48 returns project into one 8x8 px image cell" : "more than 64 returns inside one search rectangle") +
+        ctx->err = std::string("limo_depth_estimate: ") + ((*W.h_ovf & OVF_CELL) ? "more than 48 returns project into one 8x8 px image cell" : W.last_radius ? "more than 128 returns inside one search radius" : "more than 64 returns inside one search rectangle") +
                    " (not a single sweep of a spinning scanner?)";
         return LIMO_ERR_INVALID;
     }
+    return LIMO_OK;
+}
+
+// The settings this library refuses (include/limo_hip.h, limo_depth_default_params): the error text names the key.
+int check_params(limo_ctx* ctx, const limo_depth_params& p) {
+    auto fail = [&](int rc, const char* key, const char* why) {
+        ctx->err = std::string("limo_depth_estimate: ") + key + ": " + why;
+        return rc;
+    };
+    if (p.do_use_depth_segmentation) return fail(LIMO_ERR_UNSUPPORTED, "do_use_depth_segmentation", "the region-growing depth segmentation is not built");
+    if (p.neighbor_search_mode == 1 && p.do_use_nearestNeighborSearch)
+        return fail(LIMO_ERR_UNSUPPORTED, "do_use_nearestNeighborSearch", "the n-nearest-neighbours search is not built (do_use_radiusSearch is)");
+    if (p.plane_estimator_z_x_min_relation != 0.0) return fail(LIMO_ERR_UNSUPPORTED, "plane_estimator_z_x_min_relation", "the z/x flatness relation is not built");
+    if (p.do_use_PCA && p.do_use_triangle_size_maximation) return fail(LIMO_ERR_INVALID, "do_use_PCA", "set together with do_use_triangle_size_maximation (use one of them)");
+    if ((p.plane_estimator_use_triangle_maximation != 0) + (p.plane_estimator_use_leastsquares != 0) + (p.plane_estimator_use_mestimator != 0) > 1)
+        return fail(LIMO_ERR_INVALID, "plane_estimator_use_*", "more than one of plane_estimator_use_triangle_maximation / _leastsquares / _mestimator is set");
+    if (p.neighbor_search_mode != 0 && p.neighbor_search_mode != 1) return fail(LIMO_ERR_INVALID, "neighbor_search_mode", "0 (rectangle) or 1 (search around the feature)");
+    if (p.neighbor_search_mode == 1 && !p.do_use_radiusSearch) return fail(LIMO_ERR_INVALID, "neighbor_search_mode", "1 needs do_use_radiusSearch or do_use_nearestNeighborSearch");
+    if (p.neighbor_search_mode == 1 && !(p.radiusSearch_radius >= 0.0 && p.radiusSearch_radius <= 4096.0)) return fail(LIMO_ERR_INVALID, "radiusSearch_radius", "not a radius in pixels");
     return LIMO_OK;
 }
 
@@ -1157,6 +1361,36 @@ void limo_depth_default_params(limo_depth_params* p) {
     p->ransac_plane_point_distance_treshold = 0.2;
     p->plane_estimator_use_mestimator = 1;
     p->ransac_seed = 1;
+    p->neighbor_search_mode = 0;
+    p->do_use_nearestNeighborSearch = 0;
+    p->nnSearch_count = 10;
+    p->do_use_radiusSearch = 1;
+    p->radiusSearch_radius = 10;
+    p->radiusSearch_count_min = 3;
+    p->do_use_depth_segmentation = 0;
+    p->depth_segmentation_max_treshold_gradient = 10;
+    p->depth_segmentation_max_neighbor_distance = 0.2;
+    p->depth_segmentation_max_neighbor_distance_gradient = 0.02;
+    p->depth_segmentation_max_seedpoint_to_seedpoint_distance = 0.5;
+    p->depth_segmentation_max_seedpoint_to_seedpoint_distance_gradient = 0.05;
+    p->depth_segmentation_max_neighbor_to_seedpoint_distance = 0.5;
+    p->depth_segmentation_max_neighbor_to_seedpoint_distance_gradient = 0.05;
+    p->depth_segmentation_max_pointcount = 4;
+    p->treshold_depth_mode = 0;
+    p->treshold_depth_local_mode = 0;
+    p->do_use_PCA = 0;
+    p->pca_debug = 0.01;
+    p->pca_treshold_3_abs_min = 0.005;
+    p->pca_treshold_3_2_rel_max = 15;
+    p->pca_treshold_2_1_rel_min = 1.5;
+    p->ransac_plane_use_camx_treshold = 0;
+    p->ransac_plane_treshold_camx = 0.2;
+    p->plane_estimator_use_triangle_maximation = 0;
+    p->plane_estimator_use_leastsquares = 0;
+    p->plane_estimator_z_x_min_relation = 0;
+    p->do_debug_singleFeatures = 0;
+    p->do_publish_points = 0;
+    p->do_depth_calc_statistics = 0;
 }
 
 int limo_depth_estimate_batch(limo_ctx* ctx, int32_t n_frames, const limo_depth_frame* frames, const double* T_cam_lidar, double f,
@@ -1172,6 +1406,7 @@ int limo_depth_estimate_batch(limo_ctx* ctx, int32_t n_frames, const limo_depth_
     else
         limo_depth_default_params(&p);
     if (p.ransac_plane_max_iterations > kMaxHyp) p.ransac_plane_max_iterations = kMaxHyp;
+    if (int rc = check_params(ctx, p)) return rc;
     for (int k0 = 0; k0 < n_frames; k0 += kMaxBatch)
         if (int rc = run_group(ctx, std::min(kMaxBatch, n_frames - k0), frames + k0, T_cam_lidar, f, cx, cy, img_w, img_h, p,
                                (flags & LIMO_DEPTH_DEVICE_POINTERS) != 0))
@@ -1216,6 +1451,25 @@ int limo_depth_last_ground_plane(limo_ctx* ctx, int32_t frame, double* plane4, i
     return LIMO_OK;
 }
 
+int limo_depth_last_reasons(limo_ctx* ctx, int32_t frame, uint8_t* reasons, size_t n_feat) {
+    if (!ctx || !ctx->depth_ws) return LIMO_ERR_INVALID;
+    DepthWs& W = *static_cast<DepthWs*>(ctx->depth_ws);
+    if (frame < 0 || frame >= W.last_frames || n_feat != W.last_n_feat[frame] || (n_feat && !reasons)) {
+        ctx->err = "limo_depth_last_reasons: frame / n_feat are not those of the last launch group";
+        return LIMO_ERR_INVALID;
+    }
+    if (W.open) {
+        ctx->err = "limo_depth_last_reasons: a limo_depth_estimate_begin is open on this context (limo_depth_estimate_end first)";
+        return LIMO_ERR_INVALID;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return LIMO_ERR_NO_DEVICE;
+    if (n_feat) {
+        HIP_TRY(ctx, hipMemcpyAsync(reasons, W.reasons + (size_t)frame * W.cap_feat, n_feat, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return LIMO_OK;
+}
+
 int limo_depth_estimate_begin(limo_ctx* ctx, const float* cloud_xyzi, size_t n_pts, const double* T_cam_lidar, double f, double cx,
                               double cy, int32_t img_w, int32_t img_h, const float* feat_uv, size_t n_feat, const uint8_t* feat_is_ground,
                               const limo_depth_params* params) {
@@ -1227,6 +1481,7 @@ int limo_depth_estimate_begin(limo_ctx* ctx, const float* cloud_xyzi, size_t n_p
     else
         limo_depth_default_params(&p);
     if (p.ransac_plane_max_iterations > kMaxHyp) p.ransac_plane_max_iterations = kMaxHyp;
+    if (int rc = check_params(ctx, p)) return rc;
     limo_depth_frame fr;
     fr.cloud_xyzi = cloud_xyzi;
     fr.n_pts = n_pts;
