@@ -16,6 +16,8 @@
  *                                       (Ceres 1.13, DENSE_SCHUR, Levenberg-Marquardt).
  *   limo_ba_adjust_pose_only            BundleAdjusterKeyframes::adjustPoseOnly(),
  *                                       bundle_adjuster_keyframes.cpp:820-888.
+ *   limo_ba_adjust_pose_only_batch /    the same call for N independent frames at once (several sequences replayed side by
+ *   limo_ba_batch_create_pose_only      side, many frames relocalised against a map): one pack, one upload, one launch.
  *   limo_ba_evaluate                    ceres::Problem::Evaluate as used at
  *                                       robust_optimization/src/robust_solving.cpp:44 and
  *                                       keyframe_bundle_adjustment/src/definitions.cpp:94 (residuals, cost) plus
@@ -49,7 +51,7 @@
 extern "C" {
 #endif
 
-#define LIMO_ABI_VERSION 6 /* 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
+#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch: two more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
 
 /* Keyframe::FixationStatus, keyframe.hpp:30 */
 enum limo_fixation { LIMO_FIX_POSE = 0, LIMO_FIX_SCALE = 1, LIMO_FIX_NONE = 2 };
@@ -288,6 +290,27 @@ typedef struct limo_speed_prior {
 } limo_speed_prior;
 int limo_ba_adjust_pose_only(limo_ctx* ctx, limo_ba_window* window, const limo_speed_prior* prior,
                              const limo_ba_options* opts, limo_ba_report* report);
+
+/*
+ * N independent adjustPoseOnly problems (each window: n_kf == 1, landmarks constant).  priors: NULL, or n entries;
+ * an entry with speed_weight <= 0 means "no prior for this window".
+ *   - Window i of a batch gets the result of limo_ba_adjust_pose_only(window i, prior i) BIT FOR BIT: the pose, every
+ *     integer of the report, initial_cost and final_cost.  time_sec is the time of the whole batch.
+ *   - min_landmarks_for_trimming is the caller's (the reference uses 30 for adjustPoseOnly), as for the single call.  The
+ *     resident form takes it from limo_ba_batch_solve(opts), the way limo_ba_batch_create works.
+ *   - An invalid window (n_kf != 1, an index out of range, ...) fails the whole call with LIMO_ERR_INVALID; limo_last_error
+ *     names the window ("window 3: ...").  n_windows <= 0 and NULL arguments: as limo_ba_batch_create.
+ *   - Launch path of a batch of more than one window: ONE launch of k_solve_wg, a workgroup per window, for any N (the
+ *     workgroups never wait for each other) when every window has <= 2048 landmarks; otherwise, and under KBA_NO_WG_SOLVE=1,
+ *     the lock-step launch sequence - same bits.  Such a batch never streams through slots and never runs k_solve_coop.  A
+ *     batch of one window takes the paths of the single call.  The wall-clock cap is honoured per solve on both paths.
+ * Resident form: the returned batch is used with limo_ba_batch_solve / _reset / _download / _trimmed / _destroy like any other.
+ */
+int limo_ba_batch_create_pose_only(limo_ctx* ctx, int32_t n_windows, const limo_ba_window* windows,
+                                   const limo_speed_prior* priors, limo_ba_batch** out);
+/* create + solve + download + destroy; poses optimised in place, reports[n] may be NULL. */
+int limo_ba_adjust_pose_only_batch(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
+                                   const limo_ba_options* opts, limo_ba_report* reports);
 
 /*
  * The residual rows of a window that are NOT reprojection / depth blocks, linearised at the window's current parameters the

@@ -261,6 +261,8 @@ ABI_SYMBOLS = [
     "limo_ba_evaluate_batch_time",
     "limo_ba_evaluate_rows",
     "limo_ba_adjust_pose_only",
+    "limo_ba_batch_create_pose_only",
+    "limo_ba_adjust_pose_only_batch",
     "limo_landmark_init",
     "limo_trim_quantile",
     "limo_depth_default_params",
@@ -343,6 +345,9 @@ def load():
         C.POINTER(BaOptions),
         C.POINTER(BaReport),
     ]
+    if hasattr(lib, "limo_ba_batch_create_pose_only"):  # (added without an ABI bump: an A/B build of version 6 from before them lacks the two)
+        lib.limo_ba_batch_create_pose_only.argtypes = [vp, C.c_int32, C.POINTER(BaWindow), C.POINTER(SpeedPrior), C.POINTER(vp)]
+        lib.limo_ba_adjust_pose_only_batch.argtypes = [vp, C.c_int32, C.POINTER(BaWindow), C.POINTER(SpeedPrior), C.POINTER(BaOptions), C.POINTER(BaReport)]
     lib.limo_landmark_init.argtypes = [vp, C.c_int32, c_int32_p, C.POINTER(Ray), c_uint8_p, c_double_p, c_uint8_p]
     lib.limo_trim_quantile.argtypes = [C.c_int32, c_int64_p, c_double_p, C.c_double, c_int64_p]
     lib.limo_depth_default_params.argtypes = [C.POINTER(DepthParams)]

@@ -122,6 +122,16 @@ class Context:
         _check(rc, self.ptr, "limo_ba_adjust_pose_only")
         return rep.as_dict()
 
+    def adjust_pose_only_batch(self, windows, priors, opts):
+        """limo_ba_adjust_pose_only_batch: N independent pose-only windows in one call.  priors: None, or one entry per window
+        (a _ffi.SpeedPrior, or None for a window without prior).  The windows' poses are updated in place; returns the reports."""
+        windows = list(windows)
+        arr = struct_array(windows)
+        reps = (_ffi.BaReport * max(1, len(windows)))()
+        rc = self.lib.limo_ba_adjust_pose_only_batch(self.ptr, len(windows), arr, prior_array(priors, len(windows)), C.byref(opts), reps)
+        _check(rc, self.ptr, "limo_ba_adjust_pose_only_batch")
+        return [reps[i].as_dict() for i in range(len(windows))]
+
     def evaluate(self, window, opts, apply_loss=True):
         s = window.as_struct()
         M = window.n_obs
@@ -148,17 +158,39 @@ class Context:
         return _ffi.rows_as_dicts(rows, n.value)
 
 
+def prior_array(priors, n):
+    """limo_speed_prior[n] for a list of _ffi.SpeedPrior / None (None: speed_weight 0, no prior for that window); None for priors=None."""
+    if priors is None:
+        return None
+    priors = list(priors)
+    if len(priors) != n:
+        raise ValueError("priors: %d entries for %d windows" % (len(priors), n))
+    arr = (_ffi.SpeedPrior * max(1, n))()
+    for i, p in enumerate(priors):
+        if p is not None:
+            arr[i] = p
+    return arr
+
+
 class Batch:
     """Many independent windows resident in HBM (limo_ba_batch_*)."""
 
-    def __init__(self, ctx, windows, arr=None):
+    def __init__(self, ctx, windows, arr=None, pose_only=False, priors=None):
         """arr: struct_array(windows) made earlier (the array of limo_ba_window a C / C++ caller holds anyway: building it from
-        numpy windows is ~20 us of Python per window and not part of the library call)."""
+        numpy windows is ~20 us of Python per window and not part of the library call).
+        pose_only=True: every window is an adjustPoseOnly problem (limo_ba_batch_create_pose_only), priors = None or one
+        _ffi.SpeedPrior / None per window."""
         self.ctx = ctx
         self.lib = ctx.lib
         self.windows = list(windows)
         self._arr = struct_array(self.windows) if arr is None else arr
         self.ptr = C.c_void_p()
+        if pose_only:
+            rc = self.lib.limo_ba_batch_create_pose_only(ctx.ptr, len(self.windows), self._arr, prior_array(priors, len(self.windows)), C.byref(self.ptr))
+            _check(rc, ctx.ptr, "limo_ba_batch_create_pose_only")
+            return
+        if priors is not None:
+            raise ValueError("priors belong to a pose_only batch")
         _check(self.lib.limo_ba_batch_create(ctx.ptr, len(self.windows), self._arr, C.byref(self.ptr)), ctx.ptr, "limo_ba_batch_create")
 
     def solve(self, opts):

@@ -289,7 +289,7 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
     });
     for (int w = 0; w < n; ++w) {
         if (rc1[w] != LIMO_OK) {
-            err = err1[w];
+            err = po.per_window_prior ? "window " + std::to_string(w) + ": " + err1[w] : std::string(err1[w]);
             return rc1[w];
         }
         const limo_ba_window& W = windows[w];
@@ -583,12 +583,13 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
         } else if (po.pose_only) {
             set_block(present, 0, 0, 6);
             set_block(freem, 0, 0, 6);  // the new keyframe is not in active_keyframe_ids_, so never constant
-            if (po.prior && po.prior->speed_weight > 0.0) {
-                d.speed_w = po.prior->speed_weight;
-                d.speed_dt = po.prior->dt_cur;
-                for (int i = 0; i < 3; ++i) d.speed_vel[i] = po.prior->vel_prev[i];
-                quat_R(po.prior->pose_before, d.speed_Rb);
-                for (int i = 0; i < 3; ++i) d.speed_tb[i] = po.prior->pose_before[4 + i];
+            const limo_speed_prior* prior = po.per_window_prior ? (po.window_priors ? po.window_priors + w : nullptr) : po.prior;
+            if (prior && prior->speed_weight > 0.0) {
+                d.speed_w = prior->speed_weight;
+                d.speed_dt = prior->dt_cur;
+                for (int i = 0; i < 3; ++i) d.speed_vel[i] = prior->vel_prev[i];
+                quat_R(prior->pose_before, d.speed_Rb);
+                for (int i = 0; i < 3; ++i) d.speed_tb[i] = prior->pose_before[4 + i];
             }
         } else {
             // scale regularisation, :704-716 / :890-904
@@ -700,7 +701,7 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
         for (int w = 0; w < n; ++w) {
             Local& L = locals[w];
             if (L.rc != LIMO_OK) {
-                err = L.err;
+                err = po.per_window_prior ? "window " + std::to_string(w) + ": " + L.err : L.err;
                 return L.rc;
             }
             base[w] = run;

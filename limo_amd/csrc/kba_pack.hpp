@@ -112,6 +112,11 @@ struct PackOptions {
     bool evaluate_only = false;  // no problem-build logic (no ground plane / regularisers), every parameter free
     const limo_speed_prior* prior = nullptr;
     int shards = 1;  // > 1: lay the batch out for landmark sharding (no workgroup straddles two shards)
+    // A batch of adjustPoseOnly problems (limo_ba_batch_create_pose_only): window w takes window_priors[w] (null: no window has a
+    // prior; an entry with speed_weight <= 0: that window has none) instead of `prior`, and an invalid window is named by its index
+    // in the error text.
+    bool per_window_prior = false;
+    const limo_speed_prior* window_priors = nullptr;
 };
 
 // Returns LIMO_OK or a negative limo_status; err receives a message.

@@ -52,6 +52,7 @@ struct limo_ba_batch : Executor {
     limo_ctx* ctx = nullptr;
     PackedBatch P;
     bool holds_pack_arena = false;  // P's big arrays live in ctx->pack_arena
+    bool pose_batch = false;        // made by limo_ba_batch_create_pose_only: limo_ba_batch_solve picks its launch path by that
     BatchView bv;
     SolveConsts c;
     limo_ba_options opts;
@@ -1216,6 +1217,7 @@ static int batch_create_impl(limo_ctx* ctx, int32_t n, const limo_ba_window* win
     if (rc == LIMO_OK) {
         if (hipSetDevice(ctx->device) != hipSuccess) rc = LIMO_ERR_NO_DEVICE;
     }
+    b->pose_batch = po.per_window_prior;
     b->shard_P = b->P.n_shards;
     b->shard_virtual = !shards_are_ranks;
     b->shard_rank = shards_are_ranks ? ctx->comm_rank : 0;
@@ -1276,8 +1278,12 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     const bool env_stream = std::getenv("KBA_STREAM_MIN") != nullptr;  // (read per call: the tests switch paths)
     const int stream_min = env_stream ? std::atoi(std::getenv("KBA_STREAM_MIN")) : 16;
     const int coop_max = std::getenv("KBA_COOP_MAX_WIN") ? std::min(std::atoi(std::getenv("KBA_COOP_MAX_WIN")), (int)limo_ba_batch::kCoopMaxWg) : limo_ba_batch::kCoopMaxWin;
-    const bool can_stream = b->shard_P == 1 && b->opts.max_solver_time_sec <= 0.0 && b->P.n_win >= stream_min && !b->P.evaluate_only;
-    const bool one_launch = !(env_stream && can_stream) && b->P.n_win <= coop_max;  // (KBA_STREAM_MIN set: the caller asks for the streaming solve)
+    // A batch of SEVERAL adjustPoseOnly windows (limo_ba_batch_create_pose_only) takes k_solve_wg at any size - its workgroups never
+    // wait for each other, so the grid need not be resident at once - or else the lock-step sequence.  Never the slot scheduler
+    // (its Schur worklists have not seen windows without Schur blocks) and never device-wide barriers over several such windows.
+    const bool pose_multi = b->pose_batch && b->P.n_win > 1;
+    const bool can_stream = b->shard_P == 1 && b->opts.max_solver_time_sec <= 0.0 && b->P.n_win >= stream_min && !b->P.evaluate_only && !pose_multi;
+    const bool one_launch = pose_multi || (!(env_stream && can_stream) && b->P.n_win <= coop_max);  // (KBA_STREAM_MIN set: the caller asks for the streaming solve)
     auto launch_sequence = [&]() {
         if (can_stream)
             b->solve_streaming();
@@ -1290,7 +1296,7 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     // first solve's result - and not any more in a context whose launches keep timing out: something shares the GPU)
     // (three strikes switch the one-launch path off - but not for the life of the context: after kCoopRetryAfter solves through the launch
     // sequence ONE more attempt is made (a profiler session or a neighbour process that has gone away); its success clears the strikes)
-    else if (one_launch && b->pristine && b->coop_solve_applies() && (ctx->coop_strikes < 3 || ++ctx->coop_benched >= limo_ctx::kCoopRetryAfter) && b->solve_coop())
+    else if (one_launch && !pose_multi && b->pristine && b->coop_solve_applies() && (ctx->coop_strikes < 3 || ++ctx->coop_benched >= limo_ctx::kCoopRetryAfter) && b->solve_coop())
         ctx->coop_benched = 0;
     else
         launch_sequence();
@@ -1615,6 +1621,45 @@ int limo_ba_adjust_pose_only(limo_ctx* ctx, limo_ba_window* window, const limo_s
     po.pose_only = true;
     po.prior = prior;
     return solve_one(ctx, window, opts, po, report, "limo_ba_adjust_pose_only");
+}
+
+int limo_ba_batch_create_pose_only(limo_ctx* ctx, int32_t n_windows, const limo_ba_window* windows, const limo_speed_prior* priors,
+                                   limo_ba_batch** out) {
+    // (do_trim from the default options here, refreshed by limo_ba_batch_solve(opts): as limo_ba_batch_create)
+    PackOptions po;
+    po.pose_only = true;
+    po.per_window_prior = true;
+    po.window_priors = priors;
+    return batch_create_impl(ctx, n_windows, windows, nullptr, po, out);
+}
+
+// KBA_HOST_TRACE=1 prints where the host time of the call goes, as for the single call.
+int limo_ba_adjust_pose_only_batch(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
+                                   const limo_ba_options* opts, limo_ba_report* reports) {
+    using Clock = std::chrono::steady_clock;
+    static const bool trace = std::getenv("KBA_HOST_TRACE") != nullptr;
+    const auto t_a = Clock::now();
+    PackOptions po;
+    po.pose_only = true;
+    po.per_window_prior = true;
+    po.window_priors = priors;
+    limo_ba_batch* b = nullptr;
+    int rc = batch_create_impl(ctx, n_windows, windows, opts, po, &b);
+    if (rc != LIMO_OK) return rc;
+    const auto t0 = Clock::now();
+    rc = limo_ba_batch_solve(b, nullptr);
+    const auto t1 = Clock::now();
+    if (rc == LIMO_OK) rc = limo_ba_batch_download(b, windows, reports);
+    const auto t2 = Clock::now();
+    if (reports && rc == LIMO_OK)
+        for (int w = 0; w < n_windows; ++w) reports[w].time_sec = std::chrono::duration<double>(t2 - t0).count();
+    limo_ba_batch_destroy(b);
+    if (trace) {
+        auto us = [](Clock::time_point a, Clock::time_point c) { return std::chrono::duration<double, std::micro>(c - a).count(); };
+        std::fprintf(stderr, "[kba] limo_ba_adjust_pose_only_batch (%d windows): create %.0f us, solve %.0f us, download %.0f us, destroy %.0f us\n", (int)n_windows,
+                     us(t_a, t0), us(t0, t1), us(t1, t2), us(t2, Clock::now()));
+    }
+    return rc;
 }
 
 int limo_ba_evaluate(limo_ctx* ctx, const limo_ba_window* window, const limo_ba_options* opts, int apply_loss,
