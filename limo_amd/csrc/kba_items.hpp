@@ -428,7 +428,7 @@ KBA_HD void lin_lm_finish(const BatchView& bv, const SolveConsts& c, int gl, con
     part[0] = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
     part[1] = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
     // (V' + D^2) = L L^T for the step that follows this linearisation (the radius is final: kba_lm.hpp:lm_decide_step);
-    // the stand-alone k_lm_damp only runs after rejected steps
+    // the stand-alone pass (k_after_step) only runs after rejected steps
     part[5] = lm_damp_store(bv, c, t.radius, gl, sc, V, g) ? 1.0 : 0.0;
 }
 // Plain form of one landmark for the CPU emulation (k_lin_lm runs the same statements software-pipelined and

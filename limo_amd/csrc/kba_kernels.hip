@@ -7,15 +7,15 @@
 //                                                    F^T F / F^T r camera sums; the landmark's ground-plane row
 //                                                    (GroundPlaneHeightRegularization, cost_functors_ceres.hpp:355-392); E^T E,
 //                                                    E^T r (SchurEliminator chunk), Jacobi column scale, damped 3x3 Cholesky
-// k_lm_damp /     1 per landmark             HBM     (E^T E + D^2) Cholesky inverse per landmark after a REJECTED step (k_after_step: the streaming
-// k_after_step                                       solve's form, at the end of the round)
+// k_after_step    1 per landmark             HBM     (E^T E + D^2) Cholesky inverse per landmark after a REJECTED step, at the end of the
+//                                                    iteration that rejected it
 // k_schur_lean/_wide  wave / 512 lanes       MFMA    S -= sum_i Y'_i Y'_i^T   (v_mfma_f64_16x16x4_f64 SYRK from LDS tiles)
 // k_cam_assemble  workgroup per window       -       camera-camera blocks, regularisers, IterationZero / step tail
 // k_cam_solve     workgroup per window       -       reduced camera system: dense Cholesky in LDS, camera step
 // k_backsub       1 per landmark             HBM     BackSubstitute + candidate point + model-cost-change parts +
 //                                                    Evaluator::Evaluate(cost only) of its observations and of its
 //                                                    ground-plane row at the candidate
-// k_step_decide   1 per window               -       TrustRegionMinimizer step acceptance (kba_lm.hpp)
+// k_step_decide   1 per window               -       TrustRegionMinimizer step acceptance (kba_lm.hpp); an accepted step's keyframes move
 // k_trim_*        1 per obs / lm / window    HBM     robust_optimization::solveTrimmed residual evaluation + quantile
 // k_evaluate      1 per obs, wave = 64       HBM     Problem::Evaluate: residuals, J_pose, J_point of every observation written out (the
 //                 aligned observations       stores  MATERIALISED pass SURVEY 8d grades); k_eval_rows: the ground-plane / regulariser rows
@@ -178,10 +178,7 @@ __global__ void k_solve_init(BatchView bv, SolveConsts c, int max_iter, int sele
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= bv.n_win) return;
     WinState& s = bv.st[w];
-    bool sel = true;
-    if (select >= 1) sel = bv.win[w].do_trim != 0;
-    if (select == 2) sel = sel && (s.solve_initial_cost - s.solve_final_cost <= 0.0);
-    lm_solve_init(s, sel, max_iter, c);
+    lm_solve_init(s, sched_selected(select, bv.win[w], s), max_iter, c);
 }
 
 // activity flags for host-side re-batching (worklists of the windows that still iterate)
@@ -404,8 +401,7 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     const int state = in_block ? bv.lm_state[gl] : 0;
     LinIn in;
     // A window whose last step was ACCEPTED linearises at the candidate point: the landmark is read from lm_c and moves into lm
-    // right here (the streaming solve has no pass of its own for that: k_after_step; the other paths copy it themselves - the same
-    // values, so reading lm_c instead of lm changes nothing for them).
+    // right here, on every launch path - no path has a pass of its own for that (the keyframes: accept_keyframes, with the decision).
     const bool take_candidate = st.accept != 0;  // (workgroup-uniform)
     const double* lm_src = take_candidate ? bv.lm_c : bv.lm;
     in.p[0] = lm_src[3 * (int64_t)gl];
@@ -599,11 +595,6 @@ __device__ __forceinline__ void lm_damp_block(const BatchView& bv, const SolveCo
     if ((int)threadIdx.x < bv.lblk_n[b]) fail = lm_damp_lane(bv, c, w, bv.lblk_lm0[b] + threadIdx.x);
     const int any = __syncthreads_or(fail);
     if (threadIdx.x == 0) bv.lblk_part[(int64_t)b * 8 + 5] = any ? 1.0 : 0.0;
-}
-__global__ __launch_bounds__(kBlock) void k_lm_damp(BatchView bv, SolveConsts c, const int32_t* wl) {
-    const int b = wl_at(bv, wl, blockIdx.x);
-    if (b < 0) return;
-    lm_damp_block(bv, c, b);
 }
 
 // back-substitution of the landmarks + the cost of their observations at the candidate point (kba_items.hpp:backsub_lane)
@@ -1328,53 +1319,22 @@ __global__ __launch_bounds__(64) void k_step_decide(BatchView bv, SolveConsts c,
     reduce_step(bv, w, threadIdx.x, blockDim.x, red);
     __syncthreads();
     if (threadIdx.x == 0) lm_decide_step(bv.st[w], bv.red[w], c);
-    if (!bv.counted) return;
-    // streaming solve: the accepted keyframe parameters move here, per window (a pass per landmark workgroup would never reach
-    // a window WITHOUT landmark workgroups - every landmark filtered out, regularisers only)
+    // the accepted keyframe parameters move here, per window (a pass per landmark workgroup would never reach a window WITHOUT
+    // landmark workgroups - every landmark filtered out, regularisers only); the landmarks move in the relinearisation (lin_lm_block)
     __syncthreads();
-    const WinDesc& wd = bv.win[w];
-    if (bv.st[w].accept && (int)threadIdx.x < wd.n_kf) {
-        const int64_t i = wd.kf0 + threadIdx.x;
-        for (int q = 0; q < 7; ++q) bv.pose[7 * i + q] = bv.pose_c[7 * i + q];
-        for (int q = 0; q < 3; ++q) bv.pdir[3 * i + q] = bv.pdir_c[3 * i + q];
-        bv.pdist[i] = bv.pdist_c[i];
-    }
+    if (bv.st[w].accept) accept_keyframes(bv, bv.win[w], threadIdx.x, blockDim.x);
 }
 
-// candidate -> current for accepted windows (keyframe part: first TK threads, landmark part: the rest; lock-step solve - the
-// streaming solve moves the keyframes in k_step_decide and the landmarks in its relinearisation, lin_lm_block)
-__global__ void k_accept(BatchView bv) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < bv.TK) {
-        if (!bv.st[bv.kf_win[i]].accept) return;
-        for (int q = 0; q < 7; ++q) bv.pose[7 * (int64_t)i + q] = bv.pose_c[7 * (int64_t)i + q];
-        for (int q = 0; q < 3; ++q) bv.pdir[3 * (int64_t)i + q] = bv.pdir_c[3 * (int64_t)i + q];
-        bv.pdist[i] = bv.pdist_c[i];
-        return;
-    }
-    const int l = i - bv.TK;
-    if (l >= bv.TL) return;
-    if (!bv.st[bv.lm_win[l]].accept) return;
-    for (int q = 0; q < 3; ++q) bv.lm[3 * (int64_t)l + q] = bv.lm_c[3 * (int64_t)l + q];
-}
-
-// Streaming solve: what a REJECTED step asks of a window's landmarks - the landmark blocks are damped again with the new radius, before
-// the next round's Schur complement (the former k_lm_damp, at the end of the round instead of in the middle of the next one).  After
-// an ACCEPTED step there is nothing to do here: the relinearisation (lin_lm_block) reads the candidate landmarks, moves them into lm
-// and damps (the former k_accept: 48 B per landmark read and written by a pass of its own).  (Tried and dropped: the decision itself REPLICATED in every landmark workgroup instead of k_step_decide's launch - eight
+// What a REJECTED step asks of a window's landmarks - the landmark blocks are damped again with the new radius, at the end of the
+// iteration, before the next one's Schur complement.  After an ACCEPTED step there is nothing to do here: the relinearisation
+// (lin_lm_block) reads the candidate landmarks, moves them into lm and damps.  (accept and redamp are never both set: lm_decide_step.)
+// (Tried and dropped: the decision itself REPLICATED in every landmark workgroup instead of k_step_decide's launch - eight
 // workgroups per window each summing the ground-plane costs and evaluating the regulariser rows cost 70 us per round more than the
 // launch they saved: profiles/r06_experiment_launch_train.txt.)
 __global__ __launch_bounds__(kBlock) void k_after_step(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int b = wl_at(bv, wl, blockIdx.x);
     if (b < 0) return;
-    const int w = bv.lblk_win[b];
-    const WinState& st = bv.st[w];
-    if (!st.accept && st.active && st.redamp) {
-        int fail = 0;
-        if ((int)threadIdx.x < bv.lblk_n[b]) fail = lm_damp_lane(bv, c, w, bv.lblk_lm0[b] + threadIdx.x);
-        const int any = __syncthreads_or(fail);
-        if (threadIdx.x == 0) bv.lblk_part[(int64_t)b * 8 + 5] = any ? 1.0 : 0.0;
-    }
+    lm_damp_block(bv, c, b);
 }
 
 // ------------------------------------------------------------------------------------------ trimming
@@ -1624,15 +1584,9 @@ __global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c
     // cost did not drop), trim], then solve(max_iters, all) - one loop over the solves, so the body exists once.
     const int n_solves = 2 * c.num_trim_rounds + 1;
     for (int si = 0; si < n_solves; ++si) {
-        const bool final_solve = si == n_solves - 1, retry = !final_solve && (si & 1);
-        const int max_iter = final_solve ? c.max_iters : (retry ? 3 * c.trim_iters : c.trim_iters);
+        const SchedSolve sv = sched_solve(si, c);
         __syncthreads();
-        if (tid == 0) {  // k_solve_init
-            bool sel = true;
-            if (!final_solve) sel = wd.do_trim != 0;
-            if (retry) sel = sel && (st.solve_initial_cost - st.solve_final_cost <= 0.0);
-            lm_solve_init(st, sel, max_iter, c);
-        }
+        if (tid == 0) lm_solve_init(st, sched_selected(sv.select, wd, st), sv.max_iter, c);  // k_solve_init
         __syncthreads();
         KBA_WTICK(0);
         const long long t0 = cap_ticks > 0 ? (long long)wall_clock64() : 0ll;
@@ -1668,7 +1622,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c
                 active = st.active;
             }
             if (!active) break;
-            // ---- step(): k_lm_damp, (no Schur blocks: no free landmark), k_cam_solve, k_backsub, k_step_decide, k_accept
+            // ---- step(): k_after_step of the last iteration, (no Schur blocks: no free landmark), k_cam_solve, k_backsub, k_step_decide
             if (st.redamp) {
                 for (int b = lb0; b < lb1; ++b) lm_damp_block(bv, c, b);
                 __syncthreads();
@@ -1693,20 +1647,11 @@ __global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c
 #ifdef KBA_WG_TICKS
             ++n_it;
 #endif
-            if (st.accept) {
-                if (tid < wd.n_kf) {
-                    const int64_t i = wd.kf0 + tid;
-                    for (int q = 0; q < 7; ++q) bv.pose[7 * i + q] = bv.pose_c[7 * i + q];
-                    for (int q = 0; q < 3; ++q) bv.pdir[3 * i + q] = bv.pdir_c[3 * i + q];
-                    bv.pdist[i] = bv.pdist_c[i];
-                }
-                for (int64_t l = wd.lm0 + tid; l < wd.lm0 + wd.n_lm; l += kBlock)
-                    for (int q = 0; q < 3; ++q) bv.lm[3 * l + q] = bv.lm_c[3 * l + q];
-            }
+            if (st.accept) accept_keyframes(bv, wd, tid, kBlock);  // (the landmarks: lin_lm_block of the relinearisation)
             __syncthreads();
             KBA_WTICK(9);
         }
-        if (retry && wd.do_trim) {  // trim(): k_trim_residual, k_trim_max, k_trim_select
+        if (sv.select == 2 && wd.do_trim) {  // trim() behind a round's retry: k_trim_residual, k_trim_max, k_trim_select
             __syncthreads();
             for (int b = wd.blk0; b < wd.blk0 + wd.n_blk; ++b)
                 for (int q = 0; q < kObsPerLane; ++q) trim_residual_lane(bv, b, tid + q * kBlock, plane_rep, plane_dep);
@@ -1865,16 +1810,10 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
     // comes after every other reader's last use of the old value: all workgroups take the same branches.
     const int n_solves = 2 * c.num_trim_rounds + 1;
     for (int si = 0; si < n_solves; ++si) {
-        const bool final_solve = si == n_solves - 1, retry = !final_solve && (si & 1);
-        const int max_iter = final_solve ? c.max_iters : (retry ? 3 * c.trim_iters : c.trim_iters);
+        const SchedSolve sv = sched_solve(si, c);
         KBA_GSYNC();
         if (g == 0) {
-            if (tid == 0) {  // k_solve_init
-                bool sel = true;
-                if (!final_solve) sel = wd.do_trim != 0;
-                if (retry) sel = sel && (st.solve_initial_cost - st.solve_final_cost <= 0.0);
-                lm_solve_init(st, sel, max_iter, c);
-            }
+            if (tid == 0) lm_solve_init(st, sched_selected(sv.select, wd, st), sv.max_iter, c);  // k_solve_init
             __syncthreads();
             if (st.active && st.need_lin && tid < wd.n_view) view_consts_item(bv, wd.view0 + tid);  // k_view_consts
         }
@@ -1944,7 +1883,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
                 }
                 KBA_CTICK(4);
             } else {
-                // ---- k_lm_damp (after a rejected step), then the Schur complement
+                // ---- k_after_step of the last iteration (a rejected step), then the Schur complement
                 for (int b = lb0 + g; b < lb1; b += G) lm_damp_block(bv, c, b);
                 KBA_CTICK(13);
                 KBA_GSYNC();
@@ -1988,28 +1927,22 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
             KBA_CTICK(8);
             KBA_GSYNC();
             KBA_CTICK(9);
-            // ---- k_step_decide, the keyframe part of k_accept, k_view_consts of the next linearisation
+            // ---- k_step_decide (with the accepted keyframes' move), k_view_consts of the next linearisation
             if (g == 0) {
                 reduce_step(bv, w, tid, kBlock, red, 64);
                 __syncthreads();
                 if (tid == 0) lm_decide_step(st, bv.red[w], c);
                 __syncthreads();
-                if (st.accept && tid < wd.n_kf) {
-                    const int64_t i = wd.kf0 + tid;
-                    for (int q = 0; q < 7; ++q) bv.pose[7 * i + q] = bv.pose_c[7 * i + q];
-                    for (int q = 0; q < 3; ++q) bv.pdir[3 * i + q] = bv.pdir_c[3 * i + q];
-                    bv.pdist[i] = bv.pdist_c[i];
-                }
+                if (st.accept) accept_keyframes(bv, wd, tid, kBlock);
                 __syncthreads();
                 if (st.active && st.need_lin && tid < wd.n_view) view_consts_item(bv, wd.view0 + tid);
             }
             KBA_CTICK(10);
             KBA_GSYNC();
             KBA_CTICK(11);
-            // (the landmark part of k_accept is inside the relinearisation since round 6: lin_lm_block reads the candidate landmarks of
-            // an accepted step and moves them into place - the workgroup that linearises a block is the one that used to copy it)
+            // (the accepted landmarks move inside the relinearisation: lin_lm_block)
         }
-        if (retry && wd.do_trim) {  // trim(): k_trim_residual, k_trim_max, k_trim_select
+        if (sv.select == 2 && wd.do_trim) {  // trim() behind a round's retry: k_trim_residual, k_trim_max, k_trim_select
             KBA_GSYNC();
             for (int b = wd.blk0 + g; b < wd.blk0 + wd.n_blk; b += G)
                 for (int q = 0; q < kObsPerLane; ++q) trim_residual_lane(bv, b, tid + q * kBlock, a.plane_rep, a.plane_dep);

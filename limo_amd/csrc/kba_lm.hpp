@@ -54,6 +54,23 @@ KBA_HD void lm_finalize_unsuccessful(WinState& s, const SolveConsts& c) {
     }
 }
 
+// The solveTrimmed schedule as a list of solves (kba_pack.cpp:run_schedule): per trimming round a trimming solve and its retry
+// (then the trimming), at the end the final solve.  Solve number si: its iteration limit and which windows it selects -
+// Executor::solve_init's `select`: 0 every window, 1 the windows that trim, 2 of those the ones whose last solve did not reduce the cost.
+struct SchedSolve {
+    int max_iter, select;
+};
+KBA_HD SchedSolve sched_solve(int si, const SolveConsts& c) {
+    if (si == 2 * c.num_trim_rounds) return {c.max_iters, 0};
+    return (si & 1) ? SchedSolve{3 * c.trim_iters, 2} : SchedSolve{c.trim_iters, 1};
+}
+KBA_HD bool sched_selected(int select, const WinDesc& wd, const WinState& s) {
+    bool sel = true;
+    if (select >= 1) sel = wd.do_trim != 0;
+    if (select == 2) sel = sel && (s.solve_initial_cost - s.solve_final_cost <= 0.0);  // robust_solving.cpp:172-181
+    return sel;
+}
+
 // Streaming solve: advance window w in the solveTrimmed schedule at the start of a round (the lock-step form of the
 // same schedule is kba_pack.cpp:run_schedule).  Returns 0 = nothing to do this round (cannot happen for a window in a
 // slot), 1 = the window takes part in this round - it iterates, or (phase == PH_TRIM) it is trimmed during this round
@@ -195,6 +212,17 @@ KBA_HD void lm_decide_step(WinState& s, const WinRed& r, const SolveConsts& c) {
         s.decrease_factor *= 2.0;
         s.redamp = 1;
         lm_finalize_unsuccessful(s, c);
+    }
+}
+
+// An ACCEPTED step: candidate -> current for the window's keyframes (pose 7, plane direction 3, plane distance 1), a keyframe per
+// lane.  The landmarks follow inside the relinearisation every accepted step is followed by (kba_kernels.hip:lin_lm_block).
+KBA_HD void accept_keyframes(const BatchView& bv, const WinDesc& wd, int lane, int n_lanes) {
+    for (int k = lane; k < wd.n_kf; k += n_lanes) {
+        const int64_t i = wd.kf0 + k;
+        for (int q = 0; q < 7; ++q) bv.pose[7 * i + q] = bv.pose_c[7 * i + q];
+        for (int q = 0; q < 3; ++q) bv.pdir[3 * i + q] = bv.pdir_c[3 * i + q];
+        bv.pdist[i] = bv.pdist_c[i];
     }
 }
 

@@ -656,11 +656,6 @@ struct limo_ba_batch : Executor {
         hipStream_t s = ctx->stream;
         if (c.slab_packed) spart_has_packed = true;
         const WorkLists& a = wl[0].cur;  // (the window list is the same for every view)
-        for (size_t i = 0; i < pv.size(); ++i)
-            if (wl[i].cur.n_lblk) {
-                hipLaunchKernelGGL(k_lm_damp, dim3(wl[i].cur.n_lblk), dim3(kBlock), 0, s, pv[i], c, wl[i].cur.lblk);
-                LAUNCH_CHECK("k_lm_damp");
-            }
         {
             EventPair* ep = timed(LIMO_KERNEL_SCHUR);
             for (size_t i = 0; i < pv.size(); ++i) {
@@ -702,8 +697,11 @@ struct limo_ba_batch : Executor {
         exchange(4);
         if (a.n_win) hipLaunchKernelGGL(k_step_decide, dim3(a.n_win), dim3(64), 0, s, bv, c, a.win);
         LAUNCH_CHECK("k_step_decide");
-        hipLaunchKernelGGL(k_accept, dim3(cdiv((int64_t)P.TK + P.TL, 256)), dim3(256), 0, s, bv);
-        LAUNCH_CHECK("k_accept");
+        for (size_t i = 0; i < pv.size(); ++i)  // a rejected step: its landmark blocks are damped again for the next iteration
+            if (wl[i].cur.n_lblk) {
+                hipLaunchKernelGGL(k_after_step, dim3(wl[i].cur.n_lblk), dim3(kBlock), 0, s, pv[i], c, wl[i].cur.lblk);
+                LAUNCH_CHECK("k_after_step");
+            }
     }
 
     void trim() override {
@@ -876,7 +874,7 @@ struct limo_ba_batch : Executor {
         hipLaunchKernelGGL(k_cam_solve, dim3(cap[SL_WIN]), dim3(kBlock), plan.solve_bytes, s, sv, c, L(SL_WIN));
         if (cap[SL_LBLK]) hipLaunchKernelGGL(k_backsub, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
         hipLaunchKernelGGL(k_step_decide, dim3(cap[SL_WIN]), dim3(64), 0, s, sv, c, L(SL_WIN));
-        if (cap[SL_LBLK])  // accepted landmarks / re-damping in one launch (kba_kernels.hip:k_after_step)
+        if (cap[SL_LBLK])  // re-damping after a rejected step (kba_kernels.hip:k_after_step)
             hipLaunchKernelGGL(k_after_step, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
         LAUNCH_CHECK("step kernels");
         note(hipEventRecord(g.round_ev[round & 3], s), "record round");

@@ -134,10 +134,7 @@ struct EmuBatch : Executor {
     void solve_init(int max_iter, int select) override {
         for (int w = 0; w < bv.n_win; ++w) {
             WinState& s = bv.st[w];
-            bool sel = true;
-            if (select >= 1) sel = bv.win[w].do_trim != 0;
-            if (select == 2) sel = sel && (s.solve_initial_cost - s.solve_final_cost <= 0.0);
-            lm_solve_init(s, sel, max_iter, c);
+            lm_solve_init(s, sched_selected(select, bv.win[w], s), max_iter, c);
         }
         first_lin = true;  // the next linearisation defines the Jacobi scaling (WinState::compute_scale)
         assemble_pending = false;
@@ -236,15 +233,6 @@ struct EmuBatch : Executor {
         std::vector<double> z;
         for (size_t si = 0; si < pv.size(); ++si) {
             BatchView& v = pv[si];
-            // landmark damping
-            for (int b = 0; b < v.n_lblk; ++b) {
-                if (!owns(si, shard_P > 1 ? P.lblk_owner[b] : 0)) continue;
-                const int w = v.lblk_win[b];
-                if (!v.st[w].active || !v.st[w].redamp) continue;
-                int fail = 0;
-                for (int t = 0; t < v.lblk_n[b]; ++t) fail |= lm_damp_lane(v, c, w, v.lblk_lm0[b] + t);
-                v.lblk_part[(int64_t)b * 8 + 5] = fail ? 1.0 : 0.0;
-            }
             // Schur slabs: upper triangle of Z^T Z per Schur workgroup (rhs = column nfq, see kba_items.hpp)
             for (int sb = 0; sb < v.n_sblk; ++sb) {
                 if (!owns(si, shard_P > 1 ? P.sblk_owner[sb] : 0)) continue;
@@ -356,14 +344,25 @@ struct EmuBatch : Executor {
                              bv.st[w].iter, x_cost_before, bv.red[w].cand_cost, bv.red[w].mcc, std::sqrt(bv.red[w].step2), radius_before,
                              bv.st[w].accept, bv.st[w].active, bv.st[w].term);
         }
-        // accept: candidate -> current
+        // accept: candidate -> current (k_step_decide).  The landmarks move here as well - the plain statement: lin_lm_lane reads lm
+        // (the kernels' relinearisation reads lm_c and moves them itself, kba_kernels.hip:lin_lm_block)
         for (int w = 0; w < bv.n_win; ++w) {
             if (!bv.st[w].accept) continue;
             const WinDesc& wd = bv.win[w];
-            std::memcpy(bv.pose + 7 * (size_t)wd.kf0, bv.pose_c + 7 * (size_t)wd.kf0, sizeof(double) * 7 * wd.n_kf);
-            std::memcpy(bv.pdir + 3 * (size_t)wd.kf0, bv.pdir_c + 3 * (size_t)wd.kf0, sizeof(double) * 3 * wd.n_kf);
-            std::memcpy(bv.pdist + wd.kf0, bv.pdist_c + wd.kf0, sizeof(double) * wd.n_kf);
+            accept_keyframes(bv, wd, 0, 1);
             std::memcpy(bv.lm + 3 * (size_t)wd.lm0, bv.lm_c + 3 * (size_t)wd.lm0, sizeof(double) * 3 * wd.n_lm);
+        }
+        // a rejected step: the landmark blocks are damped again with the new radius (k_after_step)
+        for (size_t si = 0; si < pv.size(); ++si) {
+            BatchView& v = pv[si];
+            for (int b = 0; b < v.n_lblk; ++b) {
+                if (!owns(si, shard_P > 1 ? P.lblk_owner[b] : 0)) continue;
+                const int w = v.lblk_win[b];
+                if (!v.st[w].active || !v.st[w].redamp) continue;
+                int fail = 0;
+                for (int t = 0; t < v.lblk_n[b]; ++t) fail |= lm_damp_lane(v, c, w, v.lblk_lm0[b] + t);
+                v.lblk_part[(int64_t)b * 8 + 5] = fail ? 1.0 : 0.0;
+            }
         }
     }
 
