@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch: two more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
+#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch and with limo_ctx_last_solve_info: more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
 
 /* Keyframe::FixationStatus, keyframe.hpp:30 */
 enum limo_fixation { LIMO_FIX_POSE = 0, LIMO_FIX_SCALE = 1, LIMO_FIX_NONE = 2 };
@@ -252,6 +252,19 @@ int limo_ctx_exchange_stats(limo_ctx* ctx, int64_t* stats3);
  * constant clock, which keeps running while a wave is preempted (shared GPU, debugger, profiler); the redo starts from the
  * batch's initial state and gives the same results - the caller never sees an error, this counter is how it can tell. */
 int64_t limo_ctx_coop_fallbacks(const limo_ctx* ctx);
+/* Which launch path the last limo_ba_batch_solve on this context took - the calls that make and destroy their own batch
+ * (limo_ba_solve, limo_ba_adjust_pose_only[_batch], limo_ba_solve_sharded) included.  All paths give the same bits; this is how
+ * a test or a profile tells which one it has looked at.
+ *   info[0]  path that produced the result: 1 WG (k_solve_wg, one launch, a workgroup per window), 2 COOP (k_solve_coop, one
+ *            launch, G workgroups per window), 3 STREAMING (windows move through slots), 4 LOCKSTEP (a launch per phase)
+ *   info[1]  1: a cooperative launch gave up at a barrier and the solve was redone through the path of info[0] (see above)
+ *   info[2]  G of the cooperative launch that was made (0: none)
+ *   info[3]  slot groups and  info[4]  slots of a streaming solve
+ *   info[5]  rounds the streaming solve enqueued
+ *   info[6]  launches of k_schur_lean_pair (both fast-class Schur lists of a draining round in one launch)
+ *   info[7]  the linearisation that ran: 1 k_lin_lm<true> (LDS; also what the one-launch kernels contain), 0 k_lin_lm<false>
+ *            (scalar loads: KBA_LIN_VLDS=0, windows with many views) */
+int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]);
 
 /*
  * Evaluate the reprojection / depth residual blocks of a window at its current parameters

@@ -257,6 +257,7 @@ ABI_SYMBOLS = [
     "limo_ba_solve_sharded",
     "limo_ctx_exchange_stats",
     "limo_ctx_coop_fallbacks",
+    "limo_ctx_last_solve_info",
     "limo_ba_evaluate",
     "limo_ba_evaluate_batch_time",
     "limo_ba_evaluate_rows",
@@ -379,6 +380,8 @@ def load():
     lib.limo_ctx_exchange_stats.argtypes = [vp, c_int64_p]
     lib.limo_ctx_coop_fallbacks.argtypes = [vp]
     lib.limo_ctx_coop_fallbacks.restype = C.c_int64
+    if hasattr(lib, "limo_ctx_last_solve_info"):  # (added without an ABI bump, as the two above)
+        lib.limo_ctx_last_solve_info.argtypes = [vp, c_int64_p]
     lib.limo_depth_set_timing.argtypes = [vp, C.c_int32]
     lib.limo_depth_last_kernel_ms.argtypes = [vp, c_double_p]
     lib.limo_depth_last_ground_plane.argtypes = [vp, C.c_int32, c_double_p, c_int32_p]

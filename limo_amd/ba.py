@@ -80,6 +80,16 @@ class Context:
         """limo_ctx_coop_fallbacks: one-launch solves on this context that timed out at a barrier and were redone as launches."""
         return int(self.lib.limo_ctx_coop_fallbacks(self.ptr))
 
+    SOLVE_PATHS = {1: "WG", 2: "COOP", 3: "STREAMING", 4: "LOCKSTEP"}
+
+    def last_solve_info(self):
+        """limo_ctx_last_solve_info: which launch path the last solve on this context took (path: WG, COOP, STREAMING or LOCKSTEP)
+        and what it launched."""
+        v = (C.c_int64 * 8)()
+        _check(self.lib.limo_ctx_last_solve_info(self.ptr, v), self.ptr, "limo_ctx_last_solve_info")
+        keys = ("recovered", "coop_G", "groups", "slots", "rounds", "pair_launches", "lin_variant")
+        return dict({"path": self.SOLVE_PATHS.get(int(v[0]), "NONE")}, **{k: int(v[1 + i]) for i, k in enumerate(keys)})
+
     def comm_init(self, unique_id, rank, world):
         _check(self.lib.limo_ctx_comm_init(self.ptr, unique_id, int(rank), int(world)), self.ptr, "limo_ctx_comm_init")
 

@@ -208,9 +208,7 @@ __global__ void k_expire(BatchView bv) {
 //   k_sched_advance  one lane per slot: phase machine, slot refill, the slot's nine list counts
 //   k_sched_scan     one workgroup: exclusive scan of the counts over the slots -> offsets, list lengths, progress word
 //   k_sched_fill     one wave per slot: writes the slot's entries at its offsets
-constexpr int kSchedThreads = 1024;
-constexpr int kSchedSlotsPerLane = 4;
-constexpr int kSchedMaxSlots = kSchedThreads * kSchedSlotsPerLane;
+// (kSchedThreads, kSchedSlotsPerLane, kSchedMaxSlots: kba_layout.hpp - the host's solve plan needs them too)
 
 // bv.slot_cnt: [n_slots][SL_COUNT + 1] - counts of the slot's window per list, [SL_COUNT] = kind (0 nothing, 1 iterates,
 // 2 is trimmed this round); overwritten with the offsets by k_sched_scan.
@@ -1684,8 +1682,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c
 // as the launches: bit-identical results (tests/test_gpu_ba.py).  Fast-class windows only (WinDesc::schur_fast, camera
 // system in LDS); a barrier that is not met within half a second aborts the launch (pinned flag), it cannot hang the GPU.
 struct CoopParams {
-    int32_t G;                 // workgroups per window
-    int32_t xcd_map;           // 1: the workgroups of a window share an XCD (grid = 8 G ceil(n_win / 8))
+    int32_t G;                 // workgroups per window (the grid is 8 G ceil(n_win / 8): see k_solve_coop)
     int32_t vp, vg;            // k_schur_lean variant (TM) of the plain / ground-plane groups
     int32_t schur_lds;         // doubles of LDS per wave in the Schur phase
     long long cap_ticks;       // wall-clock cap of a solve (100 MHz ticks), 0: none
@@ -1695,7 +1692,6 @@ struct CoopParams {
     double *plane_rep, *plane_dep;
     double* red;               // [n_win][kCoopRedStride] the window's Schur slabs summed (see k_cam_solve below)
 };
-constexpr int kCoopRedStride = 64 * 64;  // nf_pad <= 64 for fast-class windows (<= 4 free keyframes: 40 slots + rhs)
 
 // One device-wide barrier of the G workgroups of a window.  A barrier that is not met within `timeout` ticks of the 100 MHz
 // constant clock ABORTS the launch: every workgroup of the window returns, the pinned flag tells the host, and the host
@@ -1739,22 +1735,15 @@ __device__ __forceinline__ bool coop_sync(int32_t* bar, int32_t* abort_word, int
 }
 
 __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts c, CoopParams a) {
-    // Workgroup -> (window, member).  xcd_map: the G workgroups of a window are placed on ONE XCD (block b runs on XCD b % 8 -
+    // Workgroup -> (window, member).  The G workgroups of a window are placed on ONE XCD (block b runs on XCD b % 8 -
     // observed, not promised: it buys speed, never correctness): what one of them writes with plain stores stays in the L2 the
     // others read from, so the first touches behind every barrier are L2 hits instead of round trips over the fabric
     // (MI355X_MICROARCH.md, handoff-payload: same-XCD 1.7x).  Window w lives on XCD w % 8; the grid is 8 G ceil(n_win / 8) and the
     // blocks that map to no window leave at once.
     const int G = a.G;
-    int w, g;
-    if (a.xcd_map) {
-        const int x = blockIdx.x & 7, s = blockIdx.x >> 3;
-        w = x + 8 * (s / G);
-        g = s % G;
-        if (w >= bv.n_win) return;
-    } else {
-        w = blockIdx.x / G;
-        g = blockIdx.x % G;
-    }
+    const int xcd = blockIdx.x & 7, member = blockIdx.x >> 3;
+    const int w = xcd + 8 * (member / G), g = member % G;
+    if (w >= bv.n_win) return;
     const int tid = threadIdx.x, wave = tid >> 6;
     const WinDesc& wd = bv.win[w];
     WinState& st = bv.st[w];

@@ -153,6 +153,12 @@ enum SchedPhase { PH_IDLE = 0, PH_TRIM_SOLVE = 1, PH_RETRY = 2, PH_TRIM = 3, PH_
 // Worklists the device-side scheduler rebuilds every round (streaming solve).  List k lives at
 // sched_lists + sched_off[k]: element [0] = number of entries, entries from [1].
 enum SchedList { SL_LBLK = 0, SL_SPLAIN, SL_SFGP, SL_SGEN, SL_WIN, SL_TBLK, SL_TLBLK, SL_TWIN, SL_COUNT };
+// k_sched_scan is ONE workgroup of kSchedThreads lanes with kSchedSlotsPerLane slots each: what bounds the slots of a slot group
+constexpr int kSchedThreads = 1024;
+constexpr int kSchedSlotsPerLane = 4;
+constexpr int kSchedMaxSlots = kSchedThreads * kSchedSlotsPerLane;
+// doubles per window in CoopParams::red (k_solve_coop): nf_pad <= 64 for fast-class windows (<= 4 free keyframes: 40 slots + rhs)
+constexpr int kCoopRedStride = 64 * 64;
 
 struct SolveConsts {  // subset of limo_ba_options the kernels need
     double a_rep, a_dep;

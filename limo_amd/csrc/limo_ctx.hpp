@@ -52,9 +52,9 @@ struct limo_ctx {
     bool has_transport() const { return comm != nullptr || xfn != nullptr; }
     long long exchange_stats[3] = {0, 0, 0};  // last landmark-sharded solve: exchange steps, bytes per rank, LM iterations
     long long coop_fallbacks = 0;           // one-launch solves whose barrier timed out and that were redone as a launch sequence
-    static constexpr int kCoopRetryAfter = 64;  // solves through the launch sequence before a benched one-launch path is tried again
-    int coop_benched = 0;                   // ... counted here
     int coop_strikes = 0;                   // ... in a row: after three the context stops taking the one-launch path (something shares the GPU)
+    int coop_benched = 0;                   // solves kept off it since; the kCoopRetryAfter-th tries again (kba_batch_plan.hpp:choose_solve_path)
+    long long last_solve_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // limo_ctx_last_solve_info: which path the last limo_ba_batch_solve took
     // Device blocks released by finished batches, kept for the next one (size class = power of two): a single-window
     // call (limo_ba_solve, limo_ba_adjust_pose_only) would otherwise spend more time in hipMalloc / hipFree than in
     // its kernels.  At most kPoolPerClass blocks per class are kept; everything is freed with the context.

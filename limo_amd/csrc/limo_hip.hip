@@ -119,6 +119,9 @@ struct limo_ba_batch : Executor {
     hipEvent_t ev_total_a = nullptr, ev_total_b = nullptr;
     double total_ms_acc = 0.0;
     double last_solve_sec = 0.0;
+    // what limo_ctx_last_solve_info tells about the solve in progress beyond its path (reset by limo_ba_batch_solve)
+    int64_t n_rounds = 0, n_pair_launches = 0;
+    int lin_variant = 1;  // k_lin_lm<true> / <false> of the last launch; the one-launch kernels always linearise through LDS
 
     ~limo_ba_batch() override {
         // (the arrays of P that live in the context's pinned pack arena are not freed one by one - kba_pack.hpp:PackArena -, the arena
@@ -516,6 +519,7 @@ struct limo_ba_batch : Executor {
         const bool vlds = want_vlds != 0 && lin_lm_lds_bytes(P.Vmax, true) <= 48 * 1024;
         const void* fn = vlds ? (const void*)k_lin_lm<true> : (const void*)k_lin_lm<false>;
         const int lds = lin_lm_lds_bytes(P.Vmax, vlds);
+        lin_variant = vlds ? 1 : 0;
         if (lds > 48 * 1024 && lin_lds_set < lds) {  // (beyond the default dynamic-LDS limit: many views)
             note(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute(k_lin_lm)");
             lin_lds_set = lds;
@@ -594,7 +598,7 @@ struct limo_ba_batch : Executor {
         bvs.n_active = bv.n_active + 2 * slot;
         bvs.n_active_host = d_h_active + slot;
         const WorkLists& a = wl[0].cur;
-        if (a.n_win) hipLaunchKernelGGL(k_cam_assemble, dim3(a.n_win), dim3(kBlock), plan.asm_bytes, s, bvs, c, a.win);
+        launch_cam_assemble(bvs, a.win, a.n_win, s);
         LAUNCH_CHECK("k_cam_assemble");
         note(hipEventRecord(act_ev[slot], s), "record n_active");
     }
@@ -637,6 +641,7 @@ struct limo_ba_batch : Executor {
             void* args[] = {(void*)&v, (void*)&wl_plain, (void*)&n_plain, (void*)&wl_fgp, (void*)&span, (void*)&span_gp, (void*)&packed};
             note(hipLaunchKernel((const void*)k_schur_lean_pair<2, 3>, dim3(n_plain + n_fgp), dim3(64), args, std::max(plan.plain_lds, plan.leangp_lds), s),
                  "launch k_schur_lean_pair");
+            ++n_pair_launches;
         }
         if (!pair && n_plain) {
             void* args[] = {(void*)&v, (void*)&wl_plain, (void*)&span, (void*)&span_gp, (void*)&packed};
@@ -650,6 +655,35 @@ struct limo_ba_batch : Executor {
             void* args[] = {(void*)&v, (void*)&wl_gen, (void*)&span, (void*)&span_gp};
             note(hipLaunchKernel(schur_fn_gen, dim3(n_gen), dim3(64 * kWideWaves), args, plan.wide_lds, s), "launch k_schur_wide");
         }
+    }
+
+    // ---- the other kernels of the train, ONE launch site each: block size, dynamic LDS and argument order are fixed here; view,
+    // worklist, grid and stream are the caller's - the lock-step solve (linearize / assemble / step / trim) and the rounds of the
+    // streaming solve (enqueue_round).  A grid of 0 launches nothing.
+    void launch_cam_assemble(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_cam_assemble, dim3(grid), dim3(kBlock), plan.asm_bytes, s, v, c, list);
+    }
+    void launch_cam_solve(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_cam_solve, dim3(grid), dim3(kBlock), plan.solve_bytes, s, v, c, list);
+    }
+    void launch_backsub(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_backsub, dim3(grid), dim3(kBlock), 0, s, v, c, list);
+    }
+    void launch_step_decide(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_step_decide, dim3(grid), dim3(64), 0, s, v, c, list);
+    }
+    void launch_after_step(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {  // accepted landmarks, re-damping after a rejected step
+        if (grid) hipLaunchKernelGGL(k_after_step, dim3(grid), dim3(kBlock), 0, s, v, c, list);
+    }
+    void launch_trim_residual(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_trim_residual, dim3(grid), dim3(kBlock), 0, s, v, d_plane_rep, d_plane_dep, list);
+    }
+    // (grid: a lane per landmark of the batch in lock-step, a workgroup per counted landmark block in a streaming round)
+    void launch_trim_max(const BatchView& v, int shard, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_trim_max, dim3(grid), dim3(kBlock), 0, s, v, (const double*)d_plane_rep, (const double*)d_plane_dep, shard, shard_P);
+    }
+    void launch_trim_select(const BatchView& v, int grid, hipStream_t s) {
+        if (grid) hipLaunchKernelGGL(k_trim_select, dim3(grid), dim3(kBlock), plan.trim_bytes, s, v, c);
     }
 
     void step() override {
@@ -681,13 +715,11 @@ struct limo_ba_batch : Executor {
                 exchange(2);
             }
         }
-        if (a.n_win) hipLaunchKernelGGL(k_cam_solve, dim3(a.n_win), dim3(kBlock), plan.solve_bytes, s, bv, c, a.win);
+        launch_cam_solve(bv, a.win, a.n_win, s);
         LAUNCH_CHECK("k_cam_solve");
         for (size_t i = 0; i < pv.size(); ++i) {
-            if (wl[i].cur.n_lblk) {
-                hipLaunchKernelGGL(k_backsub, dim3(wl[i].cur.n_lblk), dim3(kBlock), 0, s, pv[i], c, wl[i].cur.lblk);
-                LAUNCH_CHECK("k_backsub");
-            }
+            launch_backsub(pv[i], wl[i].cur.lblk, wl[i].cur.n_lblk, s);
+            LAUNCH_CHECK("k_backsub");
         }
         if (shard_P > 1 && a.n_win)
             for (size_t i = 0; i < pv.size(); ++i) {
@@ -695,13 +727,12 @@ struct limo_ba_batch : Executor {
                 LAUNCH_CHECK("k_shard_reduce");
             }
         exchange(4);
-        if (a.n_win) hipLaunchKernelGGL(k_step_decide, dim3(a.n_win), dim3(64), 0, s, bv, c, a.win);
+        launch_step_decide(bv, a.win, a.n_win, s);
         LAUNCH_CHECK("k_step_decide");
-        for (size_t i = 0; i < pv.size(); ++i)  // a rejected step: its landmark blocks are damped again for the next iteration
-            if (wl[i].cur.n_lblk) {
-                hipLaunchKernelGGL(k_after_step, dim3(wl[i].cur.n_lblk), dim3(kBlock), 0, s, pv[i], c, wl[i].cur.lblk);
-                LAUNCH_CHECK("k_after_step");
-            }
+        for (size_t i = 0; i < pv.size(); ++i) {  // a rejected step: its landmark blocks are damped again for the next iteration
+            launch_after_step(pv[i], wl[i].cur.lblk, wl[i].cur.n_lblk, s);
+            LAUNCH_CHECK("k_after_step");
+        }
     }
 
     void trim() override {
@@ -710,20 +741,15 @@ struct limo_ba_batch : Executor {
         for (const WinDesc& d : P.win) any = any || d.do_trim;
         if (!any) return;
         for (size_t i = 0; i < pv.size(); ++i) {
-            if (wl[i].full.n_blk) {
-                hipLaunchKernelGGL(k_trim_residual, dim3(wl[i].full.n_blk), dim3(kBlock), 0, s, pv[i], d_plane_rep, d_plane_dep, wl[i].full.blk);
-                LAUNCH_CHECK("k_trim_residual");
-            }
+            launch_trim_residual(pv[i], wl[i].full.blk, wl[i].full.n_blk, s);
+            LAUNCH_CHECK("k_trim_residual");
         }
-        if (P.TL) {
-            for (size_t i = 0; i < pv.size(); ++i) {
-                hipLaunchKernelGGL(k_trim_max, dim3(cdiv(P.TL, 256)), dim3(256), 0, s, pv[i], (const double*)d_plane_rep,
-                                   (const double*)d_plane_dep, local_shards[i], shard_P);
-                LAUNCH_CHECK("k_trim_max");
-            }
+        for (size_t i = 0; i < pv.size(); ++i) {
+            launch_trim_max(pv[i], local_shards[i], cdiv(P.TL, kBlock), s);
+            LAUNCH_CHECK("k_trim_max");
         }
         exchange_trim();
-        hipLaunchKernelGGL(k_trim_select, dim3(P.n_win), dim3(kBlock), plan.trim_bytes, s, bv, c);
+        launch_trim_select(bv, P.n_win, s);
         LAUNCH_CHECK("k_trim_select");
     }
 
@@ -760,37 +786,25 @@ struct limo_ba_batch : Executor {
         start_ev = nullptr;
     }
 
-    int stream_slots() const { return std::min((int)P.n_win, std::max(1024, std::min(kSchedMaxSlots, (int)P.n_win / 4))); }
-    int stream_setup(int n_groups) {
+    // Streams, events, lists and scheduler state of the slot groups of `geo` (kba_batch_plan.hpp:stream_geometry), kept for the
+    // re-solves of the batch while the number of groups stays (the rest of the geometry is fixed by the batch).
+    int stream_setup(const StreamGeometry& geo) {
+        const int n_groups = geo.n_groups;
         if (stream_groups_built == n_groups) return LIMO_OK;
         (void)hipStreamSynchronize(ctx->stream);
         stream_teardown();  // (device blocks of an earlier layout stay with the batch until it is destroyed)
-        // windows in flight: a quarter of the batch (so that the ramp-down at the end of the batch is a small part of the
-        // solve), at least 1024 (a round of fewer windows is bound by the latency of its window-level kernels)
-        n_slots = stream_slots();
-        int mx[SL_COUNT] = {0};
-        for (const WinDesc& d : P.win) {
-            const int plg = (d.n_sblk_plain + c.schur_span - 1) / c.schur_span, gpg = (d.n_sblk - d.n_sblk_plain + c.schur_span_gp - 1) / c.schur_span_gp;
-            mx[SL_LBLK] = std::max(mx[SL_LBLK], (int)d.n_lblk);
-            mx[SL_TBLK] = std::max(mx[SL_TBLK], (int)d.n_blk);
-            mx[SL_SPLAIN] = std::max(mx[SL_SPLAIN], d.schur_fast ? plg : 0);
-            mx[SL_SFGP] = std::max(mx[SL_SFGP], d.schur_fast ? gpg : 0);
-            mx[SL_SGEN] = std::max(mx[SL_SGEN], d.schur_fast ? 0 : plg + gpg);
-        }
-        mx[SL_WIN] = 1;
-        mx[SL_TLBLK] = mx[SL_LBLK];
-        mx[SL_TWIN] = 1;
+        n_slots = geo.n_slots;
         if (!d_sched_ctl && dmalloc((void**)&d_sched_ctl, sizeof(int32_t) * 8)) return LIMO_ERR_RUNTIME;
         HIP_TRY(ctx, hipEventCreateWithFlags(&start_ev, hipEventDisableTiming));
         groups.resize(n_groups);
         for (int gi = 0; gi < n_groups; ++gi) {
             StreamGroup& g = groups[gi];
-            g.n_slots = n_slots / n_groups + (gi < n_slots % n_groups ? 1 : 0);
+            g.n_slots = geo.group_slots[gi];
             g.sv = bv;
             size_t total = 0;
             for (int k = 0; k < SL_COUNT; ++k) {
-                g.mx[k] = mx[k];
-                g.cap[k] = g.n_slots * mx[k];
+                g.mx[k] = geo.mx[k];
+                g.cap[k] = g.n_slots * g.mx[k];
                 g.sv.sched_off[k] = (int32_t)total;
                 total += 1 + (size_t)std::max(1, g.cap[k]);
             }
@@ -850,9 +864,9 @@ struct limo_ba_batch : Executor {
         //      trimmed ones join again in the next round (k_trim_select arms their next solve)
         note(hipEventRecord(g.sched_ev, s), "record sched");
         note(hipStreamWaitEvent(g.trim_stream, g.sched_ev, 0), "wait sched");
-        if (cap[SL_TBLK]) hipLaunchKernelGGL(k_trim_residual, dim3(cap[SL_TBLK]), dim3(kBlock), 0, g.trim_stream, sv, d_plane_rep, d_plane_dep, L(SL_TBLK));
-        if (cap[SL_TLBLK]) hipLaunchKernelGGL(k_trim_max, dim3(cap[SL_TLBLK]), dim3(kBlock), 0, g.trim_stream, sv, (const double*)d_plane_rep, (const double*)d_plane_dep, 0, 1);
-        hipLaunchKernelGGL(k_trim_select, dim3(cap[SL_TWIN]), dim3(kBlock), plan.trim_bytes, g.trim_stream, sv, c);
+        launch_trim_residual(sv, L(SL_TBLK), cap[SL_TBLK], g.trim_stream);
+        launch_trim_max(sv, 0, cap[SL_TLBLK], g.trim_stream);
+        launch_trim_select(sv, cap[SL_TWIN], g.trim_stream);
         LAUNCH_CHECK("trim kernels");
         note(hipEventRecord(g.trim_ev, g.trim_stream), "record trim");
         // ---- linearisation of the windows that need it (their per-view constants: k_sched_fill above)
@@ -861,7 +875,7 @@ struct limo_ba_batch : Executor {
             if (cap[SL_LBLK]) launch_lin_lm(cap[SL_LBLK], s, sv, L(SL_LBLK));
             if (ep) note(hipEventRecord(ep->b, s), "hipEventRecord");
         }
-        hipLaunchKernelGGL(k_cam_assemble, dim3(cap[SL_WIN]), dim3(kBlock), plan.asm_bytes, s, sv, c, L(SL_WIN));
+        launch_cam_assemble(sv, L(SL_WIN), cap[SL_WIN], s);
         LAUNCH_CHECK("linearisation kernels");
         // ---- trust-region step of the windows that iterate
         {
@@ -871,74 +885,30 @@ struct limo_ba_batch : Executor {
             launch_schur(sv, L(SL_SPLAIN), cap[SL_SPLAIN], L(SL_SFGP), cap[SL_SFGP], L(SL_SGEN), cap[SL_SGEN], pair, s);
             if (ep) note(hipEventRecord(ep->b, s), "hipEventRecord");
         }
-        hipLaunchKernelGGL(k_cam_solve, dim3(cap[SL_WIN]), dim3(kBlock), plan.solve_bytes, s, sv, c, L(SL_WIN));
-        if (cap[SL_LBLK]) hipLaunchKernelGGL(k_backsub, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
-        hipLaunchKernelGGL(k_step_decide, dim3(cap[SL_WIN]), dim3(64), 0, s, sv, c, L(SL_WIN));
-        if (cap[SL_LBLK])  // re-damping after a rejected step (kba_kernels.hip:k_after_step)
-            hipLaunchKernelGGL(k_after_step, dim3(cap[SL_LBLK]), dim3(kBlock), 0, s, sv, c, L(SL_LBLK));
+        launch_cam_solve(sv, L(SL_WIN), cap[SL_WIN], s);
+        launch_backsub(sv, L(SL_LBLK), cap[SL_LBLK], s);
+        launch_step_decide(sv, L(SL_WIN), cap[SL_WIN], s);
+        launch_after_step(sv, L(SL_LBLK), cap[SL_LBLK], s);
         LAUNCH_CHECK("step kernels");
         note(hipEventRecord(g.round_ev[round & 3], s), "record round");
     }
 
-    // ---- a whole solve in ONE launch (kba_kernels.hip:k_solve_wg): windows without free landmarks - adjustPoseOnly -
-    // whose landmark workgroups a single workgroup walks through in a few microseconds.  KBA_NO_WG_SOLVE=1 (read per
-    // call) keeps the lock-step launches: the tests compare the two paths bit by bit.
-    static constexpr int kWgMaxLblk = 8;  // <= 2048 landmarks per window
-    bool wg_solve_applies() const {
-        if (shard_P != 1 || P.evaluate_only || P.n_sblk != 0 || P.n_win < 1) return false;
-        if (const char* e = std::getenv("KBA_NO_WG_SOLVE"))
-            if (std::atoi(e) != 0) return false;
-        for (const WinDesc& d : P.win)
-            if (d.n_lblk > kWgMaxLblk) return false;
-        return wg_lds_bytes() <= kCamLdsCapBytes;
-    }
-    int wg_lds_bytes() const { return plan.onelaunch_lds; }
+    // ---- a whole solve in ONE launch: k_solve_wg (a workgroup per window) and k_solve_coop (G workgroups per window that meet at
+    // device-wide barriers).  Which solve takes them: kba_batch_plan.hpp:choose_solve_path.
     long long cap_ticks() const { return opts.max_solver_time_sec > 0.0 ? std::max(1ll, (long long)(opts.max_solver_time_sec * 1e8)) : 0ll; }
     void solve_wg() {
-        const int lds = wg_lds_bytes();
+        const int lds = plan.onelaunch_lds;
         note(hipFuncSetAttribute((const void*)k_solve_wg, hipFuncAttributeMaxDynamicSharedMemorySize, lds), "hipFuncSetAttribute(k_solve_wg)");
         hipLaunchKernelGGL(k_solve_wg, dim3(P.n_win), dim3(kBlock), lds, ctx->stream, bv, c, cap_ticks(), d_plane_rep, d_plane_dep);
         LAUNCH_CHECK("k_solve_wg");
     }
 
-    // ---- one window (a few windows), ONE cooperative launch (kba_kernels.hip:k_solve_coop): G workgroups per window that
-    // meet at device-wide barriers where the lock-step solve has launch boundaries.  KBA_NO_COOP_SOLVE=1 (read per call)
-    // keeps the lock-step launches (the tests compare the two paths bit by bit).
-    // At most 64 windows per launch (>= 4 workgroups per window): measured on C2 windows (scripts/gpu_small_batch.py), one launch
-    // vs streaming solve: 16 windows 10.8 / 19.1 ms, 64: 17.4 / 22.4 ms, 128: 25.0 / 24.0 ms, 256: 34.0 / 27.7 ms
-    // (KBA_COOP_MAX_WIN: timing aid, up to 256).
-    static constexpr int kCoopMaxWg = 256, kCoopMaxWin = 64;
     int32_t* d_coop_bar = nullptr;
     double* d_coop_red = nullptr;
     bool coop_launched = false;
-    int coop_G = 0, coop_xcd = 1;
-    int coop_lds_bytes() const { return std::max(plan.onelaunch_lds, (kBlock / 64) * plan.schur_wave_lds); }
-    bool coop_solve_applies() {
-        if (shard_P != 1 || P.evaluate_only || P.n_win < 1) return false;
-        if (const char* e = std::getenv("KBA_NO_COOP_SOLVE"))
-            if (std::atoi(e) != 0) return false;
-        int G = 1;
-        for (const WinDesc& d : P.win) {
-            if (!d.schur_fast || d.cam_scr_off >= 0 || d.nf_pad * d.nf_pad > kCoopRedStride) return false;
-            const int tasks = (d.n_sblk_plain + c.schur_span - 1) / c.schur_span + (d.n_sblk - d.n_sblk_plain + c.schur_span_gp - 1) / c.schur_span_gp;
-            // enough workgroups for one landmark workgroup each, and for one Schur group per wave next to workgroup 0
-            G = std::max(G, std::max((int)d.n_lblk, tasks ? 1 + (tasks + kBlock / 64 - 1) / (kBlock / 64) : 1));
-        }
-        G = std::min(G, 32);
-        // one workgroup per CU, all resident: a batch of up to kCoopMaxWin windows shares the chip with fewer workgroups per
-        // window (64 windows: 4 each) - still far ahead of ten launches per iteration over 64 slots
-        if (P.n_win > kCoopMaxWg || coop_lds_bytes() > kCamLdsCapBytes) return false;
-        // the workgroups of a window on one XCD (k_solve_coop): the grid is 8 G ceil(n_win / 8), of which n_win G blocks work
-        // (a batch too large for that grid takes the plain mapping)
-        const int per8 = ((int)P.n_win + 7) / 8;
-        coop_xcd = 8 * per8 > kCoopMaxWg ? 0 : 1;
-        G = std::max(1, std::min(G, coop_xcd ? kCoopMaxWg / (8 * per8) : kCoopMaxWg / (int)P.n_win));
-        coop_G = G;
-        return true;
-    }
     // false: the launch was refused (nothing ran) - the caller takes the lock-step path
-    bool solve_coop() {
-        const int lds = coop_lds_bytes();
+    bool solve_coop(const CoopGeometry& geo, const SolveSwitches& sw) {
+        const int lds = coop_lds_bytes(plan);
         if (!d_coop_bar && dmalloc((void**)&d_coop_bar, sizeof(int32_t) * 8 * P.n_win)) return false;
         if (!d_coop_red && dmalloc((void**)&d_coop_red, sizeof(double) * kCoopRedStride * P.n_win)) return false;
         if (hipFuncSetAttribute((const void*)k_solve_coop, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
@@ -952,19 +922,16 @@ struct limo_ba_batch : Executor {
         }
         h_active[8] = 0;
         CoopParams cp;
-        cp.G = coop_G;
-        cp.xcd_map = coop_xcd;
-        const int coop_grid = coop_xcd ? 8 * coop_G * (((int)P.n_win + 7) / 8) : (int)P.n_win * coop_G;
+        cp.G = geo.G;
         cp.vp = plan.plain_tm;
         cp.vg = plan.gp_tm;
         cp.schur_lds = plan.schur_wave_lds / (int)sizeof(double);
         cp.cap_ticks = cap_ticks();
-        // barrier timeout in ticks of the 100 MHz constant clock (read per call; KBA_COOP_TIMEOUT_MS=0: give up at the first wait -
-        // how the tests reach the recovery path of limo_ba_batch_solve)
+        // barrier timeout in ticks of the 100 MHz constant clock (KBA_COOP_TIMEOUT_MS=0: give up at the first wait - how the tests
+        // reach the recovery path of limo_ba_batch_solve)
         // default 50 ms (the whole call is ~5 ms; the longest phase between two barriers - the quantile trimming - well under 1 ms):
         // a barrier that is not met by then is lost, and the caller of a 10 Hz pipeline should not wait seconds to learn it
-        cp.timeout_ticks = 5000000ll;
-        if (const char* e = std::getenv("KBA_COOP_TIMEOUT_MS")) cp.timeout_ticks = std::max(0ll, (long long)(std::atof(e) * 1e5));
+        cp.timeout_ticks = std::max(0ll, (long long)(sw.coop_timeout_ms * 1e5));
         cp.bar = d_coop_bar;
         cp.abort_host = d_h_active + 8;
         cp.plane_rep = d_plane_rep;
@@ -980,11 +947,11 @@ struct limo_ba_batch : Executor {
         // profiles/r04_experiment_coop_api_vs_plain_launch.txt).
         int per_cu = 0, n_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_solve_coop, kBlock, (size_t)lds) != hipSuccess ||
-            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || per_cu * n_cu < coop_grid) {
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || per_cu * n_cu < geo.grid) {
             (void)hipGetLastError();
             return false;  // (not all workgroups resident at once: the launch sequence)
         }
-        if (hipLaunchKernel((const void*)k_solve_coop, dim3(coop_grid), dim3(kBlock), args, lds, ctx->stream) != hipSuccess) {
+        if (hipLaunchKernel((const void*)k_solve_coop, dim3(geo.grid), dim3(kBlock), args, lds, ctx->stream) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
@@ -994,14 +961,8 @@ struct limo_ba_batch : Executor {
 
     // The host only enqueues; it learns that all windows are done from a pinned word the scheduler writes, two rounds
     // late (so the streams never drain inside a solve).
-    int solve_streaming() {
-        // two slot groups from 512 windows on (A/B at 256 .. 1536 windows: 5-9 % on the re-solve at every size; the FIRST solve of a batch
-        // pays the second group's streams and events, which a one-shot batch of 256 windows does not earn back: 44 vs 36 ms)
-        // THREE groups once a group still holds ~1400 slots (4096 slots = batches of 16384 windows: 36.4 vs 35.8 k windows/s, alternating runs
-        // on one box; at 1024-2048 slots a third group costs 1-4 %, a fourth 7 % at 4096: profiles/r06_experiment_launch_train.txt)
-        int n_groups = stream_slots() >= 4096 ? 3 : P.n_win >= 512 ? 2 : 1;
-        if (const char* e = std::getenv("KBA_GROUPS")) n_groups = std::max(1, std::min(4, std::atoi(e)));
-        if (stream_setup(n_groups) != LIMO_OK) return LIMO_ERR_RUNTIME;
+    int solve_streaming(const SolveSwitches& sw) {
+        if (stream_setup(stream_geometry(P, {c.schur_span, c.schur_span_gp}, sw)) != LIMO_OK) return LIMO_ERR_RUNTIME;
         if (c.slab_packed) spart_has_packed = true;
         hipStream_t s0 = ctx->stream;
         groups[0].stream = s0;
@@ -1025,6 +986,7 @@ struct limo_ba_batch : Executor {
             const int in_flight_max = (int)P.n_win - done_seen;
             const auto t_enq0 = std::chrono::steady_clock::now();
             for (StreamGroup& g : groups) enqueue_round(g, round, time_kernels, in_flight_max);
+            ++n_rounds;
             if (sched_trace) enq_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enq0).count();
             if (rc != LIMO_OK) break;
             if (round >= kLag) {
@@ -1062,6 +1024,12 @@ struct limo_ba_batch : Executor {
             }
         }
         return rc;
+    }
+
+    // An evaluation of an evaluate-only batch: the per-view constants + the materialised pass, on the context's stream.
+    void launch_evaluate(int apply_loss, double* d_cost, uint8_t* d_valid) {
+        hipLaunchKernelGGL(k_view_consts_all, dim3(cdiv(P.TV, 256)), dim3(256), 0, ctx->stream, bv);
+        hipLaunchKernelGGL(k_evaluate, dim3(evaluate_grid(P.n_echunk)), dim3(kBlock), 0, ctx->stream, bv, c, apply_loss, d_cost, d_valid);
     }
 
     int collect_linearize_events() {
@@ -1268,36 +1236,45 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     b->rc = LIMO_OK;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(ctx, hipEventRecord(b->ev_total_a, ctx->stream));
-    // Windows of a batch converge after very different numbers of iterations: from a few windows on they stream through
-    // slots (k_sched) instead of advancing in lock-step.  Not for sharded solves (exchange steps between the kernels)
-    // and not with a wall-clock cap (a per-solve clock, run_schedule keeps it).
-    // ... and small batches (<= 256 windows of the common shape) run as ONE launch: a workgroup per window (no free
-    // landmark) or G workgroups per window that meet at device-wide barriers (k_solve_coop).  All paths give the same bits.
-    const bool env_stream = std::getenv("KBA_STREAM_MIN") != nullptr;  // (read per call: the tests switch paths)
-    const int stream_min = env_stream ? std::atoi(std::getenv("KBA_STREAM_MIN")) : 16;
-    const int coop_max = std::getenv("KBA_COOP_MAX_WIN") ? std::min(std::atoi(std::getenv("KBA_COOP_MAX_WIN")), (int)limo_ba_batch::kCoopMaxWg) : limo_ba_batch::kCoopMaxWin;
-    // A batch of SEVERAL adjustPoseOnly windows (limo_ba_batch_create_pose_only) takes k_solve_wg at any size - its workgroups never
-    // wait for each other, so the grid need not be resident at once - or else the lock-step sequence.  Never the slot scheduler
-    // (its Schur worklists have not seen windows without Schur blocks) and never device-wide barriers over several such windows.
-    const bool pose_multi = b->pose_batch && b->P.n_win > 1;
-    const bool can_stream = b->shard_P == 1 && b->opts.max_solver_time_sec <= 0.0 && b->P.n_win >= stream_min && !b->P.evaluate_only && !pose_multi;
-    const bool one_launch = pose_multi || (!(env_stream && can_stream) && b->P.n_win <= coop_max);  // (KBA_STREAM_MIN set: the caller asks for the streaming solve)
+    // Which path (kba_batch_plan.hpp:choose_solve_path; the KBA_* switches are read per call: the tests switch paths).  All paths
+    // give the same bits.
+    const SolveSwitches sw = read_solve_switches();
+    SolveFacts facts;
+    facts.max_solver_time_sec = b->opts.max_solver_time_sec;
+    facts.shard_P = b->shard_P;
+    facts.pose_batch = b->pose_batch;
+    facts.pristine = b->pristine;
+    facts.coop_strikes = ctx->coop_strikes;
+    facts.coop_benched = ctx->coop_benched;
+    const SolveChoice ch = choose_solve_path(b->P, b->plan, sw, facts);
+    if (ch.benched) ++ctx->coop_benched;
+    b->n_rounds = b->n_pair_launches = 0;
+    b->lin_variant = 1;
+    long long* info = ctx->last_solve_info;
+    std::fill(info, info + 8, 0ll);
     auto launch_sequence = [&]() {
-        if (can_stream)
-            b->solve_streaming();
+        info[0] = ch.fallback;
+        if (ch.fallback == PATH_STREAMING)
+            b->solve_streaming(sw);
         else
             run_schedule(*b, b->opts);
     };
-    if (one_launch && b->wg_solve_applies())
-        b->solve_wg();
-    // (the cooperative solve only from the pristine state - its timeout recovery restores THAT state, a warm re-solve would lose the
-    // first solve's result - and not any more in a context whose launches keep timing out: something shares the GPU)
-    // (three strikes switch the one-launch path off - but not for the life of the context: after kCoopRetryAfter solves through the launch
-    // sequence ONE more attempt is made (a profiler session or a neighbour process that has gone away); its success clears the strikes)
-    else if (one_launch && !pose_multi && b->pristine && b->coop_solve_applies() && (ctx->coop_strikes < 3 || ++ctx->coop_benched >= limo_ctx::kCoopRetryAfter) && b->solve_coop())
-        ctx->coop_benched = 0;
-    else
-        launch_sequence();
+    switch (ch.path) {
+        case PATH_WG:
+            info[0] = PATH_WG;
+            b->solve_wg();
+            break;
+        case PATH_COOP:
+            if (b->solve_coop(ch.coop, sw)) {
+                info[0] = PATH_COOP;
+                info[2] = ch.coop.G;
+                ctx->coop_benched = 0;
+                break;
+            }
+            [[fallthrough]];  // the launch was refused (nothing ran)
+        default:
+            launch_sequence();
+    }
     b->pristine = false;
     if (b->coop_launched) {
         // A device-wide barrier of k_solve_coop that was not met in time aborts the launch (kba_kernels.hip:coop_sync) and leaves
@@ -1308,6 +1285,7 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
         if (b->h_active[8] == 0) ctx->coop_strikes = 0;
         if (b->h_active[8] != 0) {
             b->h_active[8] = 0;
+            info[1] = 1;
             ++ctx->coop_fallbacks;
             ++ctx->coop_strikes;
             if (b->reset_state() != LIMO_OK) return LIMO_ERR_RUNTIME;
@@ -1330,6 +1308,13 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
         ++b->n_exchanges;
         b->exchange_bytes += (int64_t)sizeof(double) * 3 * b->P.TL;
     }
+    if (info[0] == PATH_STREAMING) {
+        info[3] = (long long)b->groups.size();
+        info[4] = b->n_slots;
+    }
+    info[5] = b->n_rounds;
+    info[6] = b->n_pair_launches;
+    info[7] = b->lin_variant;
     HIP_TRY(ctx, hipEventRecord(b->ev_total_b, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
@@ -1574,27 +1559,28 @@ int limo_ba_solve_sharded(limo_ctx* ctx, limo_ba_window* window, const limo_ba_o
     return rc;
 }
 
-// One window per call (limo_ba_solve, limo_ba_adjust_pose_only): create, solve, download, destroy.
-// KBA_HOST_TRACE=1 prints where the host time of the call goes.
-static int solve_one(limo_ctx* ctx, limo_ba_window* window, const limo_ba_options* opts, const PackOptions& po, limo_ba_report* report,
-                     const char* what) {
+// The calls that take windows and give results back (limo_ba_solve, limo_ba_adjust_pose_only, limo_ba_adjust_pose_only_batch): create,
+// solve, download, destroy over `n` windows.  KBA_HOST_TRACE=1 prints where the host time of the call goes.
+static int solve_n(limo_ctx* ctx, int32_t n, limo_ba_window* windows, const limo_ba_options* opts, const PackOptions& po, limo_ba_report* reports,
+                   const char* what) {
     using Clock = std::chrono::steady_clock;
     static const bool trace = std::getenv("KBA_HOST_TRACE") != nullptr;
     const auto t_a = Clock::now();
     limo_ba_batch* b = nullptr;
-    int rc = batch_create_impl(ctx, 1, window, opts, po, &b);
+    int rc = batch_create_impl(ctx, n, windows, opts, po, &b);
     if (rc != LIMO_OK) return rc;
     const auto t0 = Clock::now();
     rc = limo_ba_batch_solve(b, nullptr);
     const auto t1 = Clock::now();
-    if (rc == LIMO_OK) rc = limo_ba_batch_download(b, window, report);
+    if (rc == LIMO_OK) rc = limo_ba_batch_download(b, windows, reports);
     const auto t2 = Clock::now();
-    if (report) report->time_sec = std::chrono::duration<double>(t2 - t0).count();
+    if (reports)
+        for (int w = 0; w < n; ++w) reports[w].time_sec = std::chrono::duration<double>(t2 - t0).count();
     limo_ba_batch_destroy(b);
     if (trace) {
         auto us = [](Clock::time_point a, Clock::time_point c) { return std::chrono::duration<double, std::micro>(c - a).count(); };
-        std::fprintf(stderr, "[kba] %s: create %.0f us, solve %.0f us, download %.0f us, destroy %.0f us\n", what, us(t_a, t0), us(t0, t1), us(t1, t2),
-                     us(t2, Clock::now()));
+        std::fprintf(stderr, "[kba] %s (%d windows): create %.0f us, solve %.0f us, download %.0f us, destroy %.0f us\n", what, (int)n, us(t_a, t0), us(t0, t1),
+                     us(t1, t2), us(t2, Clock::now()));
     }
     return rc;
 }
@@ -1607,9 +1593,15 @@ int limo_ctx_exchange_stats(limo_ctx* ctx, int64_t* stats3) {
     return LIMO_OK;
 }
 
+int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]) {
+    if (!ctx || !info) return LIMO_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) info[i] = ctx->last_solve_info[i];
+    return LIMO_OK;
+}
+
 int limo_ba_solve(limo_ctx* ctx, limo_ba_window* window, const limo_ba_options* opts, limo_ba_report* report) {
     if (!ctx || !window) return LIMO_ERR_INVALID;
-    return solve_one(ctx, window, opts, PackOptions(), report, "limo_ba_solve");
+    return solve_n(ctx, 1, window, opts, PackOptions(), report, "limo_ba_solve");
 }
 
 int limo_ba_adjust_pose_only(limo_ctx* ctx, limo_ba_window* window, const limo_speed_prior* prior,
@@ -1618,7 +1610,7 @@ int limo_ba_adjust_pose_only(limo_ctx* ctx, limo_ba_window* window, const limo_s
     PackOptions po;
     po.pose_only = true;
     po.prior = prior;
-    return solve_one(ctx, window, opts, po, report, "limo_ba_adjust_pose_only");
+    return solve_n(ctx, 1, window, opts, po, report, "limo_ba_adjust_pose_only");
 }
 
 int limo_ba_batch_create_pose_only(limo_ctx* ctx, int32_t n_windows, const limo_ba_window* windows, const limo_speed_prior* priors,
@@ -1631,33 +1623,13 @@ int limo_ba_batch_create_pose_only(limo_ctx* ctx, int32_t n_windows, const limo_
     return batch_create_impl(ctx, n_windows, windows, nullptr, po, out);
 }
 
-// KBA_HOST_TRACE=1 prints where the host time of the call goes, as for the single call.
 int limo_ba_adjust_pose_only_batch(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
                                    const limo_ba_options* opts, limo_ba_report* reports) {
-    using Clock = std::chrono::steady_clock;
-    static const bool trace = std::getenv("KBA_HOST_TRACE") != nullptr;
-    const auto t_a = Clock::now();
     PackOptions po;
     po.pose_only = true;
     po.per_window_prior = true;
     po.window_priors = priors;
-    limo_ba_batch* b = nullptr;
-    int rc = batch_create_impl(ctx, n_windows, windows, opts, po, &b);
-    if (rc != LIMO_OK) return rc;
-    const auto t0 = Clock::now();
-    rc = limo_ba_batch_solve(b, nullptr);
-    const auto t1 = Clock::now();
-    if (rc == LIMO_OK) rc = limo_ba_batch_download(b, windows, reports);
-    const auto t2 = Clock::now();
-    if (reports && rc == LIMO_OK)
-        for (int w = 0; w < n_windows; ++w) reports[w].time_sec = std::chrono::duration<double>(t2 - t0).count();
-    limo_ba_batch_destroy(b);
-    if (trace) {
-        auto us = [](Clock::time_point a, Clock::time_point c) { return std::chrono::duration<double, std::micro>(c - a).count(); };
-        std::fprintf(stderr, "[kba] limo_ba_adjust_pose_only_batch (%d windows): create %.0f us, solve %.0f us, download %.0f us, destroy %.0f us\n", (int)n_windows,
-                     us(t_a, t0), us(t0, t1), us(t1, t2), us(t2, Clock::now()));
-    }
-    return rc;
+    return solve_n(ctx, n_windows, windows, opts, po, reports, "limo_ba_adjust_pose_only_batch");
 }
 
 int limo_ba_evaluate(limo_ctx* ctx, const limo_ba_window* window, const limo_ba_options* opts, int apply_loss,
@@ -1675,8 +1647,7 @@ int limo_ba_evaluate(limo_ctx* ctx, const limo_ba_window* window, const limo_ba_
     rc = b->dmalloc((void**)&d_cost, sizeof(double) * NB);
     if (rc == LIMO_OK) rc = b->dmalloc((void**)&d_valid, (size_t)std::max(1, M) + 2);
     if (rc == LIMO_OK && P.n_echunk) {
-        hipLaunchKernelGGL(k_view_consts_all, dim3(cdiv(P.TV, 256)), dim3(256), 0, ctx->stream, b->bv);
-        hipLaunchKernelGGL(k_evaluate, dim3(evaluate_grid(P.n_echunk)), dim3(kBlock), 0, ctx->stream, b->bv, b->c, apply_loss, d_cost, d_valid);
+        b->launch_evaluate(apply_loss, d_cost, d_valid);
         if (hipGetLastError() != hipSuccess) rc = LIMO_ERR_RUNTIME;
     }
     // device layout (kba_layout.hpp): rows u, v as planes over the observations, the depth row as compact planes over the depth observations
@@ -1784,14 +1755,10 @@ int limo_ba_evaluate_batch_time(limo_ctx* ctx, int32_t n, const limo_ba_window* 
     if (rc == LIMO_OK && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = LIMO_ERR_RUNTIME;
     if (rc == LIMO_OK && b->P.n_echunk) {
         hipStream_t s = ctx->stream;
-        // (an evaluation = the per-view constants + the materialised pass: both launches are inside the timed region)
-        auto eval = [&]() {
-            hipLaunchKernelGGL(k_view_consts_all, dim3(cdiv(b->P.TV, 256)), dim3(256), 0, s, b->bv);
-            hipLaunchKernelGGL(k_evaluate, dim3(evaluate_grid(b->P.n_echunk)), dim3(kBlock), 0, s, b->bv, b->c, 1, d_cost, d_valid);
-        };
-        eval();  // warm-up
+        // (both launches of an evaluation are inside the timed region)
+        b->launch_evaluate(1, d_cost, d_valid);  // warm-up
         (void)hipEventRecord(e0, s);
-        for (int r = 0; r < reps; ++r) eval();
+        for (int r = 0; r < reps; ++r) b->launch_evaluate(1, d_cost, d_valid);
         (void)hipEventRecord(e1, s);
         float ms = 0.f;
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {

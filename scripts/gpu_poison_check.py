@@ -23,6 +23,7 @@ def check(name, ws):
     nan = sum(not np.isfinite(b_.kf_pose).all() for b_ in outs)
     h = float(sum(np.abs(b_.kf_pose).sum() for b_ in outs))
     print("%-28s windows %4d unchanged %d nan %d terminations %s checksum %.12f" % (name, len(ws), same, nan, sorted(set(r["termination"] for r in reps)), h), flush=True)
+    print("%-28s solve info %s" % (name, " ".join("%s=%s" % kv for kv in ctx.last_solve_info().items())), flush=True)
 
 
 short = len(sys.argv) > 1 and sys.argv[1] == "short"  # (three cases: the streaming batch, a single window, the large window)

@@ -1,5 +1,5 @@
-// Host-only checks of limo_amd/csrc/kba_batch_plan.hpp (the per-batch kernel plan and the Schur worklist builder) and of the pack
-// arena's lend guard (kba_pack.hpp:PackArenaLend).  Stand-alone program, built with -fsanitize=address by tests/test_batch_plan_cpu.py
+// Host-only checks of limo_amd/csrc/kba_batch_plan.hpp (the per-batch kernel plan, the Schur worklist builder, the path of a solve
+// and the slot geometry of the streaming solve) and of the pack arena's lend guard (kba_pack.hpp:PackArenaLend).  Stand-alone program, built with -fsanitize=address by tests/test_batch_plan_cpu.py
 // together with kba_pack.cpp.  The expected values are written out here, not computed by the code under test.
 #include <cstdio>
 #include <cstdlib>
@@ -172,9 +172,252 @@ static void test_lend_guard() {
     std::free(block);
 }
 
+// ---- the path of a solve (choose_solve_path).  Expected values by hand from the rules: a batch streams from 16 windows on (not
+// sharded, not capped, not several pose-only windows); up to 64 windows it is one launch instead unless KBA_STREAM_MIN is set and it
+// can stream; k_solve_wg for windows without Schur blocks and <= 8 landmark workgroups, else k_solve_coop for fast-class windows
+// from the pristine state.
+static WinDesc fast_window(int n_lblk) {  // 5 plain + 2 ground-plane Schur blocks: 3 + 2 groups -> 1 + ceil(5 / 4) = 3 workgroups
+    WinDesc d = window(1, 5, 7);
+    d.n_lblk = n_lblk;
+    d.n_blk = 4;
+    return d;
+}
+static WinDesc pose_window(int n_lblk) {  // no free landmark: no Schur block
+    WinDesc d = window(1, 0, 0);
+    d.n_lblk = n_lblk;
+    d.n_blk = 1;
+    return d;
+}
+static SolveChoice choose(const std::vector<WinDesc>& ws, const SolveSwitches& sw, const SolveFacts& f, const PlanKernelSizes& ks = kSizes) {
+    const PackedBatch P = batch_of(ws);
+    return choose_solve_path(P, plan_batch(P, ks), sw, f);
+}
+static int lean_lds_huge(int) { return 40000; }  // four waves of it: 160000 > kCamLdsCapBytes
+
+static void test_solve_paths() {
+    const SolveSwitches def;
+    const SolveFacts fresh;
+    CHECK(def.stream_min == 16 && !def.stream_min_set && def.coop_max_win == 64 && !def.no_wg && !def.no_coop && def.coop_timeout_ms == 50.0 && !def.groups_set);
+    CHECK(fresh.shard_P == 1 && fresh.pristine && !fresh.pose_batch && fresh.max_solver_time_sec <= 0.0 && fresh.coop_strikes == 0);
+    SolveSwitches no_coop, no_wg, neither;
+    no_coop.no_coop = neither.no_coop = true;
+    no_wg.no_wg = neither.no_wg = true;
+    {   // one fast window
+        SolveChoice ch = choose({fast_window(2)}, def, fresh);
+        CHECK(ch.path == PATH_COOP && ch.fallback == PATH_LOCKSTEP && !ch.benched);
+        CHECK(ch.coop.G == 3 && ch.coop.grid == 24);  // the Schur groups ask for 3 workgroups
+        ch = choose({fast_window(6)}, def, fresh);
+        CHECK(ch.path == PATH_COOP && ch.coop.G == 6 && ch.coop.grid == 48);  // the landmark workgroups for 6
+        ch = choose({fast_window(40)}, def, fresh);
+        CHECK(ch.path == PATH_COOP && ch.coop.G == 32 && ch.coop.grid == 256);  // at most 32
+        ch = choose({fast_window(2)}, no_coop, fresh);
+        CHECK(ch.path == PATH_LOCKSTEP && ch.fallback == PATH_LOCKSTEP && !ch.benched);
+        ch = choose({fast_window(2)}, no_wg, fresh);
+        CHECK(ch.path == PATH_COOP);
+    }
+    {   // a window without Schur blocks
+        SolveChoice ch = choose({pose_window(1)}, def, fresh);
+        CHECK(ch.path == PATH_WG && ch.fallback == PATH_LOCKSTEP);
+        ch = choose({pose_window(8)}, def, fresh);
+        CHECK(ch.path == PATH_WG);
+        ch = choose({pose_window(9)}, def, fresh);  // too many landmark workgroups for one workgroup to walk
+        CHECK(ch.path == PATH_COOP && ch.coop.G == 9 && ch.coop.grid == 72);
+        ch = choose({pose_window(1)}, no_wg, fresh);
+        CHECK(ch.path == PATH_COOP && ch.coop.G == 1 && ch.coop.grid == 8);
+        ch = choose({pose_window(1)}, no_coop, fresh);
+        CHECK(ch.path == PATH_WG);
+        ch = choose({pose_window(1)}, neither, fresh);
+        CHECK(ch.path == PATH_LOCKSTEP);
+    }
+    {   // 24 fast windows
+        const std::vector<WinDesc> ws(24, fast_window(2));
+        SolveChoice ch = choose(ws, def, fresh);
+        CHECK(ch.path == PATH_COOP && ch.fallback == PATH_STREAMING && ch.coop.G == 3 && ch.coop.grid == 72);
+        SolveSwitches sm1, sm1000, sm1000_nc;
+        sm1.stream_min_set = sm1000.stream_min_set = sm1000_nc.stream_min_set = true;
+        sm1.stream_min = 1;
+        sm1000.stream_min = sm1000_nc.stream_min = 1000;
+        sm1000_nc.no_coop = true;
+        ch = choose(ws, sm1, fresh);
+        CHECK(ch.path == PATH_STREAMING && ch.fallback == PATH_STREAMING);
+        ch = choose(ws, sm1000, fresh);
+        CHECK(ch.path == PATH_COOP && ch.fallback == PATH_LOCKSTEP);
+        ch = choose(ws, sm1000_nc, fresh);
+        CHECK(ch.path == PATH_LOCKSTEP && ch.fallback == PATH_LOCKSTEP);
+        ch = choose({fast_window(2)}, sm1, fresh);  // a single window streams when it is asked to
+        CHECK(ch.path == PATH_STREAMING);
+        std::vector<WinDesc> mixed = ws;
+        mixed[7] = window(0, 3, 4);  // one generic-class window
+        ch = choose(mixed, def, fresh);
+        CHECK(ch.path == PATH_STREAMING && ch.fallback == PATH_STREAMING && !ch.benched);
+        mixed[7] = fast_window(2);
+        mixed[7].cam_scr_off = 0;  // camera system in global scratch
+        CHECK(choose(mixed, def, fresh).path == PATH_STREAMING);
+        mixed[7].cam_scr_off = -1;
+        mixed[7].nf_pad = 80;  // 6400 > kCoopRedStride
+        CHECK(choose(mixed, def, fresh).path == PATH_STREAMING);
+        SolveFacts capped;
+        capped.max_solver_time_sec = 5.0;
+        ch = choose(ws, def, capped);
+        CHECK(ch.path == PATH_COOP && ch.fallback == PATH_LOCKSTEP);
+        ch = choose(ws, no_coop, capped);
+        CHECK(ch.path == PATH_LOCKSTEP);
+        CHECK(choose({fast_window(2)}, no_coop, capped).path == PATH_LOCKSTEP);
+        SolveFacts warm;
+        warm.pristine = false;
+        CHECK(choose(ws, def, warm).path == PATH_STREAMING);
+        CHECK(choose({fast_window(2)}, def, warm).path == PATH_LOCKSTEP);
+        CHECK(choose({pose_window(1)}, def, warm).path == PATH_WG);  // (k_solve_wg has no barrier to time out: any state)
+        SolveFacts sharded;
+        sharded.shard_P = 2;
+        CHECK(choose({fast_window(2)}, def, sharded).path == PATH_LOCKSTEP);
+        CHECK(choose({pose_window(1)}, def, sharded).path == PATH_LOCKSTEP);
+        CHECK(choose(ws, def, sharded).path == PATH_LOCKSTEP && choose(ws, def, sharded).fallback == PATH_LOCKSTEP);
+    }
+    {   // how many windows are one launch
+        CHECK(choose(std::vector<WinDesc>(64, fast_window(2)), def, fresh).path == PATH_COOP);
+        CHECK(choose(std::vector<WinDesc>(65, fast_window(2)), def, fresh).path == PATH_STREAMING);
+        SolveSwitches wide;
+        wide.coop_max_win = 256;
+        SolveChoice ch = choose(std::vector<WinDesc>(200, fast_window(2)), wide, fresh);
+        CHECK(ch.path == PATH_COOP && ch.fallback == PATH_STREAMING && ch.coop.G == 1 && ch.coop.grid == 200);
+        CHECK(choose(std::vector<WinDesc>(257, fast_window(2)), wide, fresh).path == PATH_STREAMING);
+        // cooperative grids: windows that ask for 32 workgroups each share 256
+        const int n_of[] = {1, 40, 64, 200, 256}, g_of[] = {32, 6, 4, 1, 1}, grid_of[] = {256, 240, 256, 200, 256};
+        for (int k = 0; k < 5; ++k) {
+            ch = choose(std::vector<WinDesc>(n_of[k], fast_window(40)), wide, fresh);
+            CHECK(ch.path == PATH_COOP && ch.coop.G == g_of[k] && ch.coop.grid == grid_of[k]);
+            CHECK(ch.coop.grid <= 256 && ch.coop.grid == 8 * ch.coop.G * ((n_of[k] + 7) / 8));
+        }
+    }
+    {   // three strikes bench the cooperative path; the 64th benched solve tries again
+        SolveFacts f;
+        f.coop_strikes = 2;
+        SolveChoice ch = choose({fast_window(2)}, def, f);
+        CHECK(ch.path == PATH_COOP && !ch.benched);
+        f.coop_strikes = 3;
+        const int benched_of[] = {0, 62, 63, 64};
+        const SolvePath path_of[] = {PATH_LOCKSTEP, PATH_LOCKSTEP, PATH_COOP, PATH_COOP};
+        for (int k = 0; k < 4; ++k) {
+            f.coop_benched = benched_of[k];
+            ch = choose({fast_window(2)}, def, f);
+            CHECK(ch.path == path_of[k] && ch.benched && ch.fallback == PATH_LOCKSTEP);
+        }
+        f.coop_benched = 0;
+        ch = choose(std::vector<WinDesc>(24, fast_window(2)), def, f);
+        CHECK(ch.path == PATH_STREAMING && ch.benched);
+        // a solve the cooperative path would not have taken anyway is not counted
+        CHECK(!choose({fast_window(2)}, no_coop, f).benched);
+        CHECK(!choose({pose_window(1)}, def, f).benched && choose({pose_window(1)}, def, f).path == PATH_WG);
+        CHECK(!choose(std::vector<WinDesc>(65, fast_window(2)), def, f).benched);
+        f.pristine = false;
+        CHECK(!choose({fast_window(2)}, def, f).benched);
+    }
+    {   // several pose-only windows: k_solve_wg at any size, else lock-step
+        SolveFacts pb;
+        pb.pose_batch = true;
+        std::vector<WinDesc> ws(300, pose_window(1));
+        SolveChoice ch = choose(ws, def, pb);
+        CHECK(ch.path == PATH_WG && ch.fallback == PATH_LOCKSTEP);
+        ws[100].n_lblk = 9;
+        SolveSwitches sm1;
+        sm1.stream_min_set = true;
+        sm1.stream_min = 1;
+        ch = choose(ws, def, pb);
+        CHECK(ch.path == PATH_LOCKSTEP && ch.fallback == PATH_LOCKSTEP && !ch.benched);
+        ch = choose(ws, sm1, pb);
+        CHECK(ch.path == PATH_LOCKSTEP && ch.fallback == PATH_LOCKSTEP);
+        ws.resize(24);  // (24 windows without the large one)
+        CHECK(choose(ws, no_wg, pb).path == PATH_LOCKSTEP);  // never barriers over several such windows
+        CHECK(choose({pose_window(1)}, no_wg, pb).path == PATH_COOP);  // one window of a pose batch: as limo_ba_adjust_pose_only
+    }
+    {   // LDS beyond kCamLdsCapBytes refuses the one-launch kernels
+        PlanKernelSizes big_lin = kSizes, big_wave = kSizes;
+        big_lin.lin_lds = 200000;  // the window-level phases: both kernels
+        big_wave.lean_lds = lean_lds_huge;  // the Schur waves: k_solve_coop only
+        CHECK(choose({pose_window(1)}, def, fresh, big_lin).path == PATH_LOCKSTEP);
+        CHECK(choose({fast_window(2)}, def, fresh, big_lin).path == PATH_LOCKSTEP);
+        CHECK(choose(std::vector<WinDesc>(24, fast_window(2)), def, fresh, big_lin).path == PATH_STREAMING);
+        CHECK(choose({pose_window(1)}, def, fresh, big_wave).path == PATH_WG);
+        CHECK(choose({fast_window(2)}, def, fresh, big_wave).path == PATH_LOCKSTEP);
+    }
+}
+
+static void test_stream_geometry() {
+    const SolveSwitches def;
+    const SchurSpans spans;
+    CHECK(spans.plain == 2 && spans.gp == 1 && kSchedMaxSlots == 4096);
+    struct Row {
+        int n_win, slots, groups, per_group[4];
+    };
+    const Row rows[] = {{16, 16, 1, {16, 0, 0, 0}},          {512, 512, 2, {256, 256, 0, 0}},          {4096, 1024, 2, {512, 512, 0, 0}},
+                        {8192, 2048, 2, {1024, 1024, 0, 0}}, {16384, 4096, 3, {1366, 1365, 1365, 0}}, {20000, 4096, 3, {1366, 1365, 1365, 0}},
+                        {511, 511, 1, {511, 0, 0, 0}},       {1, 1, 1, {1, 0, 0, 0}},                  {5000, 1250, 2, {625, 625, 0, 0}}};
+    for (const Row& r : rows) {
+        const StreamGeometry g = stream_geometry(batch_of(std::vector<WinDesc>(r.n_win, fast_window(2))), spans, def);
+        CHECK(g.n_slots == r.slots && g.n_groups == r.groups);
+        for (int k = 0; k < 4; ++k) CHECK(g.group_slots[k] == r.per_group[k] && g.group_slots[k] <= kSchedMaxSlots);
+    }
+    {   // KBA_GROUPS: 1 .. 4
+        SolveSwitches sw;
+        sw.groups_set = true;
+        const PackedBatch P = batch_of(std::vector<WinDesc>(512, fast_window(2)));
+        sw.groups = 0;
+        StreamGeometry g = stream_geometry(P, spans, sw);
+        CHECK(g.n_groups == 1 && g.n_slots == 512 && g.group_slots[0] == 512 && g.group_slots[1] == 0);
+        sw.groups = 9;
+        g = stream_geometry(P, spans, sw);
+        CHECK(g.n_groups == 4 && g.group_slots[0] == 128 && g.group_slots[1] == 128 && g.group_slots[2] == 128 && g.group_slots[3] == 128);
+        sw.groups = 3;
+        g = stream_geometry(P, spans, sw);
+        CHECK(g.n_groups == 3 && g.group_slots[0] == 171 && g.group_slots[1] == 171 && g.group_slots[2] == 170 && g.group_slots[3] == 0);
+        sw.groups = 1;
+        g = stream_geometry(batch_of(std::vector<WinDesc>(20000, fast_window(2))), spans, sw);
+        CHECK(g.n_groups == 1 && g.group_slots[0] == 4096 && g.group_slots[0] <= kSchedMaxSlots);
+    }
+    {   // entries a single window can have per list: a fast window (5 + 2 Schur blocks, 3 landmark and 4 observation workgroups) and a
+        // generic one (3 + 1 blocks, 5 and 2)
+        WinDesc gen = window(0, 3, 4);
+        gen.n_lblk = 5;
+        gen.n_blk = 2;
+        const PackedBatch P = batch_of({fast_window(3), gen});
+        StreamGeometry g = stream_geometry(P, spans, def);
+        CHECK(g.n_slots == 2 && g.n_groups == 1);
+        CHECK(g.mx[SL_LBLK] == 5 && g.mx[SL_TBLK] == 4 && g.mx[SL_TLBLK] == 5 && g.mx[SL_WIN] == 1 && g.mx[SL_TWIN] == 1);
+        CHECK(g.mx[SL_SPLAIN] == 3 && g.mx[SL_SFGP] == 2 && g.mx[SL_SGEN] == 2 + 1);
+        SchurSpans one;
+        one.plain = 1;
+        g = stream_geometry(P, one, def);
+        CHECK(g.mx[SL_SPLAIN] == 5 && g.mx[SL_SFGP] == 2 && g.mx[SL_SGEN] == 3 + 1);
+    }
+}
+
+static void test_switch_reader() {
+    for (const char* k : {"KBA_STREAM_MIN", "KBA_COOP_MAX_WIN", "KBA_NO_WG_SOLVE", "KBA_NO_COOP_SOLVE", "KBA_COOP_TIMEOUT_MS", "KBA_GROUPS"}) unsetenv(k);
+    SolveSwitches s = read_solve_switches();
+    CHECK(!s.stream_min_set && s.stream_min == 16 && s.coop_max_win == 64 && !s.no_wg && !s.no_coop && s.coop_timeout_ms == 50.0 && !s.groups_set);
+    setenv("KBA_STREAM_MIN", "5", 1);
+    setenv("KBA_COOP_MAX_WIN", "1000", 1);
+    setenv("KBA_NO_WG_SOLVE", "0", 1);
+    setenv("KBA_NO_COOP_SOLVE", "1", 1);
+    setenv("KBA_COOP_TIMEOUT_MS", "0", 1);
+    setenv("KBA_GROUPS", "9", 1);
+    s = read_solve_switches();
+    CHECK(s.stream_min_set && s.stream_min == 5 && s.coop_max_win == 256 && !s.no_wg && s.no_coop && s.coop_timeout_ms == 0.0 && s.groups_set && s.groups == 9);
+    setenv("KBA_COOP_MAX_WIN", "8", 1);
+    setenv("KBA_NO_WG_SOLVE", "1", 1);
+    setenv("KBA_COOP_TIMEOUT_MS", "2.5", 1);
+    s = read_solve_switches();
+    CHECK(s.coop_max_win == 8 && s.no_wg && s.coop_timeout_ms == 2.5);
+    for (const char* k : {"KBA_STREAM_MIN", "KBA_COOP_MAX_WIN", "KBA_NO_WG_SOLVE", "KBA_NO_COOP_SOLVE", "KBA_COOP_TIMEOUT_MS", "KBA_GROUPS"}) unsetenv(k);
+}
+
 int main() {
     test_plan_table();
     test_worklists();
+    test_solve_paths();
+    test_stream_geometry();
+    test_switch_reader();
     test_lend_guard();
     std::printf("%d checks, %d failed checks\n", g_checks, g_failed);
     return g_failed ? 1 : 0;

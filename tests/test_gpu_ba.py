@@ -128,10 +128,11 @@ def test_streaming_and_lock_step_schedules_give_the_same_bits(ctx, monkeypatch):
     results = []
     for k in ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE"):  # (the one-launch paths have their own tests below)
         monkeypatch.setenv(k, "1")
-    for stream_min in ("1", "1000"):
+    for stream_min, path in (("1", "STREAMING"), ("1000", "LOCKSTEP")):
         monkeypatch.setenv("KBA_STREAM_MIN", stream_min)
         b = ba.Batch(ctx, [w.copy() for w in ws])
         b.solve(o)
+        assert ctx.last_solve_info()["path"] == path
         reps = b.download()
         results.append((reps, [(w.kf_pose.copy(), w.kf_plane_dir.copy(), w.kf_plane_dist.copy(), w.lm_pos.copy()) for w in b.windows], [b.trimmed(i) for i in range(len(ws))]))
         b.close()
@@ -160,6 +161,7 @@ def test_one_batch_through_every_launch_sequence_gives_the_same_bits(ctx, monkey
         if i:
             b.reset()
         b.solve(o)
+        assert ctx.last_solve_info()["path"] == ("STREAMING" if stream_min == "1" else "LOCKSTEP")
         reps = b.download()
         results.append((reps, [(w.kf_pose.copy(), w.kf_plane_dir.copy(), w.kf_plane_dist.copy(), w.lm_pos.copy()) for w in b.windows], [b.trimmed(i) for i in range(len(ws))]))
     b.close()
@@ -239,15 +241,18 @@ def test_pose_only_one_launch_equals_lock_step(ctx, seed, cap, monkeypatch):
     pw, prior, _ = make_pose_only_case(seed)
     o = default_options(min_landmarks_for_trimming=30, max_solver_time_sec=cap)
     for pr in (None, prior):
-        # three paths: one workgroup (k_solve_wg), the cooperative kernel with G = 1 (KBA_NO_WG_SOLVE=1), the lock-step launches
+        # three paths: one workgroup (k_solve_wg), the cooperative kernel with a workgroup per landmark workgroup - G = 1 or 2 for these
+        # ~300-landmark windows - (KBA_NO_WG_SOLVE=1), the lock-step launches
         runs = []
-        for env in ({}, {"KBA_NO_WG_SOLVE": "1"}, {"KBA_NO_WG_SOLVE": "1", "KBA_NO_COOP_SOLVE": "1"}):
+        for env, path in (({}, "WG"), ({"KBA_NO_WG_SOLVE": "1"}, "COOP"), ({"KBA_NO_WG_SOLVE": "1", "KBA_NO_COOP_SOLVE": "1"}, "LOCKSTEP")):
             for k in ("KBA_NO_WG_SOLVE", "KBA_NO_COOP_SOLVE"):
                 monkeypatch.delenv(k, raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
             x = pw.copy()
             runs.append((x, ctx.adjust_pose_only(x, pr, o)))
+            info = ctx.last_solve_info()
+            assert info["path"] == path and info["recovered"] == 0 and (1 <= info["coop_G"] <= 2 if path == "COOP" else info["coop_G"] == 0), info
         for k in ("KBA_NO_WG_SOLVE", "KBA_NO_COOP_SOLVE"):
             monkeypatch.delenv(k, raising=False)
         (a, ra) = runs[0]
@@ -260,16 +265,19 @@ def test_pose_only_one_launch_equals_lock_step(ctx, seed, cap, monkeypatch):
 
 
 def _solve_both_paths(ctx, w, o, monkeypatch):
+    """The window on the default path and on the lock-step sequence; the third result is the path the default run took."""
     a, b = w.copy(), w.copy()
     for k in ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE"):
         monkeypatch.delenv(k, raising=False)
     ra = ctx.solve(a, o)
+    path = ctx.last_solve_info()["path"]
     for k in ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE"):
         monkeypatch.setenv(k, "1")
     rb = ctx.solve(b, o)
+    assert ctx.last_solve_info()["path"] == "LOCKSTEP"
     for k in ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE"):
         monkeypatch.delenv(k, raising=False)
-    return a, ra, b, rb
+    return (a, ra, path), (b, rb)
 
 
 @pytest.mark.parametrize("cap", [-1.0, 30.0])
@@ -287,14 +295,14 @@ def test_single_window_one_launch_equals_lock_step(ctx, cap, monkeypatch):
     ws += [w for kw, w in random_windows(40, 2024) if kw["n_kf"] <= 5][:12]
     n_coop = 0
     for w in ws:
-        a, ra, b, rb = _solve_both_paths(ctx, w, o, monkeypatch)
+        (a, ra, path), (b, rb) = _solve_both_paths(ctx, w, o, monkeypatch)
         assert a.kf_pose.tobytes() == b.kf_pose.tobytes()
         assert a.lm_pos.tobytes() == b.lm_pos.tobytes()
         assert a.kf_plane_dir.tobytes() == b.kf_plane_dir.tobytes() and a.kf_plane_dist.tobytes() == b.kf_plane_dist.tobytes()
         for k in ("final_cost", "initial_cost", "iterations_total", "iterations_final", "num_solves", "n_trimmed_landmarks", "termination",
                   "successful_steps", "num_linearizations"):
             assert ra[k] == rb[k], (k, ra[k], rb[k])
-        n_coop += 1
+        n_coop += path == "COOP"
     assert n_coop >= 10
 
 
@@ -310,6 +318,7 @@ def test_barrier_timeout_of_the_one_launch_solve_is_recovered(ctx, monkeypatch):
         ref = w.copy()
         monkeypatch.setenv("KBA_NO_COOP_SOLVE", "1")
         r_ref = ctx.solve(ref, o)
+        assert ctx.last_solve_info()["path"] == "LOCKSTEP"
         monkeypatch.delenv("KBA_NO_COOP_SOLVE")
         before = ctx.coop_fallbacks()
         monkeypatch.setenv("KBA_COOP_TIMEOUT_MS", "0")
@@ -317,12 +326,16 @@ def test_barrier_timeout_of_the_one_launch_solve_is_recovered(ctx, monkeypatch):
         r = ctx.solve(x, o)
         monkeypatch.delenv("KBA_COOP_TIMEOUT_MS")
         assert ctx.coop_fallbacks() == before + 1            # the launch did give up ...
+        info = ctx.last_solve_info()
+        assert info["recovered"] == 1 and info["path"] == "LOCKSTEP" and info["coop_G"] > 1, info  # ... and the launch sequence gave the result
         assert x.kf_pose.tobytes() == ref.kf_pose.tobytes() and x.lm_pos.tobytes() == ref.lm_pos.tobytes()  # ... and nothing of it is left
         for k in ("final_cost", "initial_cost", "iterations_total", "num_solves", "n_trimmed_landmarks", "termination", "num_linearizations"):
             assert r[k] == r_ref[k], (k, r[k], r_ref[k])
         y = w.copy()
         ctx.solve(y, o)                                        # the next call on the context takes the one-launch path again
         assert ctx.coop_fallbacks() == before + 1 and y.kf_pose.tobytes() == ref.kf_pose.tobytes()
+        info = ctx.last_solve_info()
+        assert info["recovered"] == 0 and info["path"] == "COOP", info
 
 
 @pytest.mark.parametrize("n", [24, 64, 200])
@@ -340,6 +353,11 @@ def test_small_batch_one_launch_equals_streaming(ctx, n, monkeypatch):
             monkeypatch.setenv("KBA_STREAM_MIN", "1")
         b = ba.Batch(ctx, [w.copy() for w in ws])
         b.solve(o)
+        info = ctx.last_solve_info()
+        if streaming:
+            assert info["path"] == "STREAMING" and info["slots"] == n and info["groups"] == 1 and info["rounds"] > 0, info
+        else:  # the 2000-landmark windows ask for 8 workgroups (their landmark workgroups); 8 G ceil(n / 8) <= 256 allows 10, 4, 1
+            assert info["path"] == "COOP" and info["recovered"] == 0 and info["coop_G"] == {24: 8, 64: 4, 200: 1}[n], info
         reps = b.download()
         results.append((reps, [(w.kf_pose.copy(), w.kf_plane_dir.copy(), w.kf_plane_dist.copy(), w.lm_pos.copy()) for w in b.windows], [b.trimmed(i) for i in range(len(ws))]))
         b.close()
@@ -350,6 +368,36 @@ def test_small_batch_one_launch_equals_streaming(ctx, n, monkeypatch):
             assert ra[i][key] == rb[i][key], (i, key)
         assert all(np.array_equal(x, y) for x, y in zip(pa[i], pb[i])), i
         assert np.array_equal(ta[i], tb[i])
+
+
+def test_solve_info_reports_each_path(ctx, monkeypatch):
+    """limo_ctx_last_solve_info names the launch path of the last solve on the context, through the single-call wrappers (which
+    destroy their batch) as well as for a resident batch: the smallest shapes at which the way from the plan (kba_batch_plan.hpp:
+    choose_solve_path, stream_geometry) to the launches can go wrong."""
+    for k in ("KBA_NO_COOP_SOLVE", "KBA_NO_WG_SOLVE", "KBA_STREAM_MIN", "KBA_COOP_MAX_WIN", "KBA_GROUPS", "KBA_COOP_TIMEOUT_MS"):
+        monkeypatch.delenv(k, raising=False)
+    o = default_options()
+    w = synth.make_window(300, n_kf=3, n_lm=60)
+    ctx.solve(w.copy(), o)
+    info = ctx.last_solve_info()
+    assert info["path"] == "COOP" and info["recovered"] == 0 and info["coop_G"] >= 1 and info["groups"] == info["slots"] == info["rounds"] == 0, info
+    assert info["lin_variant"] == 1 and info["pair_launches"] == 0, info
+    monkeypatch.setenv("KBA_NO_COOP_SOLVE", "1")
+    ctx.solve(w.copy(), o)
+    info = ctx.last_solve_info()
+    assert info["path"] == "LOCKSTEP" and info["recovered"] == 0 and info["coop_G"] == 0 and info["groups"] == info["slots"] == info["rounds"] == 0, info
+    monkeypatch.delenv("KBA_NO_COOP_SOLVE")
+    monkeypatch.setenv("KBA_STREAM_MIN", "1")
+    b = ba.Batch(ctx, [w.copy(), w.copy()])
+    b.solve(o)
+    info = ctx.last_solve_info()
+    b.close()
+    monkeypatch.delenv("KBA_STREAM_MIN")
+    assert info["path"] == "STREAMING" and info["groups"] == 1 and info["slots"] == 2 and info["rounds"] >= 3 and info["coop_G"] == 0, info
+    pw, prior, _ = synth.make_pose_only_case(71)
+    ctx.adjust_pose_only(pw.copy(), prior, default_options(min_landmarks_for_trimming=30))
+    info = ctx.last_solve_info()
+    assert info["path"] == "WG" and info["recovered"] == 0 and info["coop_G"] == 0 and info["rounds"] == 0, info
 
 
 def test_committed_golden_fixtures(ctx):

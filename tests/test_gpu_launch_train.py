@@ -44,10 +44,11 @@ def test_window_without_landmarks_whose_pose_moves(ctx, oracle, monkeypatch):
     po = bare.copy()
     oracle.adjust_pose_only(po, prior, o)
     runs = []
-    for env in ({}, {"KBA_NO_WG_SOLVE": "1"}, {"KBA_NO_WG_SOLVE": "1", "KBA_NO_COOP_SOLVE": "1"}):
+    for env, path in (({}, "WG"), ({"KBA_NO_WG_SOLVE": "1"}, "COOP"), ({"KBA_NO_WG_SOLVE": "1", "KBA_NO_COOP_SOLVE": "1"}, "LOCKSTEP")):
         _set_env(monkeypatch, env)
         x = bare.copy()
         runs.append((x, ctx.adjust_pose_only(x, prior, o)))
+        assert ctx.last_solve_info()["path"] == path
     _set_env(monkeypatch, {})
     a, ra = runs[0]
     for b, rb in runs[1:]:
@@ -68,6 +69,7 @@ def test_window_without_landmarks_whose_pose_moves(ctx, oracle, monkeypatch):
     _set_env(monkeypatch, {"KBA_NO_WG_SOLVE": "1"})
     bt = ba.Batch(ctx, wins, pose_only=True, priors=priors)
     bt.solve(o)
+    assert ctx.last_solve_info()["path"] == "LOCKSTEP"
     reps = bt.download()
     launches = bt.kernel_stats()["linearize_launches"]
     bt.close()
@@ -89,11 +91,13 @@ def test_rejected_steps_on_every_launch_path(ctx, monkeypatch):
     w = window_io.load_npz(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "window_drive_frame1674.npz"))
     o = default_options()
     results = []  # (what, window, report, trimmed set)
-    for what, env, n in (("one launch", {}, 1), ("lock-step", {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"}, 1),
-                         ("streaming", {"KBA_STREAM_MIN": "1"}, 2)):
+    for what, env, n, path in (("one launch", {}, 1, "COOP"), ("lock-step", {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"}, 1, "LOCKSTEP"),
+                               ("streaming", {"KBA_STREAM_MIN": "1"}, 2, "STREAMING")):
         _set_env(monkeypatch, env)
         b = ba.Batch(ctx, [w.copy() for _ in range(n)])
         b.solve(o)
+        info = ctx.last_solve_info()
+        assert info["path"] == path and info["recovered"] == 0, (what, info)
         reps = b.download()
         for i in range(n):
             results.append(("%s, window %d" % (what, i), b.windows[i], reps[i], b.trimmed(i)))

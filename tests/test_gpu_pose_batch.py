@@ -82,6 +82,7 @@ def test_batch_equals_single_calls(ctx, n, cap, monkeypatch):
     _clear_env(monkeypatch)
     wins, priors = _batch_inputs(n)
     reps = ctx.adjust_pose_only_batch(wins, priors, _opts(cap))
+    assert ctx.last_solve_info()["path"] == "WG"  # one launch at every size, with and without the cap
     assert len(reps) == n
     _check_against_singles(ctx, monkeypatch, wins, reps, cap)
     assert len({r["time_sec"] for r in reps}) == 1  # the batch's time
@@ -100,8 +101,10 @@ def test_both_launch_paths(ctx, n, monkeypatch):
             monkeypatch.setenv(k, v)
         wins, priors = _batch_inputs(n)
         reps = ctx.adjust_pose_only_batch(wins, priors, _opts())
+        assert ctx.last_solve_info()["path"] == ("LOCKSTEP" if env else "WG")
         b = ba.Batch(ctx, _batch_inputs(n)[0], pose_only=True, priors=priors)
         b.solve(_opts())
+        assert ctx.last_solve_info()["path"] == ("LOCKSTEP" if env else "WG")
         launches = b.kernel_stats()["linearize_launches"]
         b.close()
         _clear_env(monkeypatch)
@@ -154,6 +157,7 @@ def test_ragged_batch_takes_the_lock_step_sequence(ctx, monkeypatch):
         singles.append((x.kf_pose.tobytes(), rep))
     wins = [w.copy() for w in wins0]
     reps = ctx.adjust_pose_only_batch(wins, priors, o)
+    assert ctx.last_solve_info()["path"] == "LOCKSTEP"
     for i in range(3):
         _assert_same(wins[i].kf_pose.tobytes(), reps[i], singles[i], "window %d" % i)
         assert np.array_equal(wins[i].lm_pos, wins0[i].lm_pos)
@@ -162,6 +166,7 @@ def test_ragged_batch_takes_the_lock_step_sequence(ctx, monkeypatch):
     assert reps[2]["num_solves"] >= 2
     b = ba.Batch(ctx, [w.copy() for w in wins0], pose_only=True, priors=priors)
     b.solve(o)
+    assert ctx.last_solve_info()["path"] == "LOCKSTEP"
     assert b.kernel_stats()["linearize_launches"] > 0  # launches of k_lin_lm: the lock-step sequence, not k_solve_wg
     reps2 = b.download()
     for i in range(3):
@@ -178,10 +183,12 @@ def test_resident_form(ctx, monkeypatch):
     b = ba.Batch(ctx, wins, pose_only=True, priors=priors)
     b.solve(o)
     assert b.kernel_stats()["linearize_launches"] == 0  # one k_solve_wg launch
+    assert ctx.last_solve_info()["path"] == "WG"
     r1 = b.download()
     p1 = [w.kf_pose.tobytes() for w in b.windows]
     b.reset()
     b.solve(o)
+    assert ctx.last_solve_info()["path"] == "WG"
     r2 = b.download()
     p2 = [w.kf_pose.tobytes() for w in b.windows]
     one_shot_w, _ = _batch_inputs(n)

@@ -16,6 +16,16 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _solve_infos(stdout):
+    """The 'solve info' lines of scripts/gpu_poison_check.py (one per case, next to its checksum line) as dicts."""
+    out = []
+    for l in stdout.splitlines():
+        if " solve info " in l:
+            d = dict(kv.split("=") for kv in l.split(" solve info ")[1].split())
+            out.append({k: (v if k == "path" else int(v)) for k, v in d.items()})
+    return out
+
+
 def test_repeated_calls_give_the_same_bits(ctx):
     o = default_options()
     rng = np.random.default_rng(5)
@@ -66,7 +76,7 @@ def test_linearisation_variants_give_the_same_bits():
     scalar loads of the view constants - also what batches with many views per window take).  The same statements in the same order:
     every checksum of the poison script must be the same to the last bit whichever one runs."""
     out = []
-    for extra in ({}, {"KBA_LIN_VLDS": "0"}):
+    for extra, variant in (({}, 1), ({"KBA_LIN_VLDS": "0"}, 0)):
         env = dict(os.environ, **extra)
         env.pop("KBA_POISON", None)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "gpu_poison_check.py"), "short"], capture_output=True, text=True, timeout=600,
@@ -75,6 +85,12 @@ def test_linearisation_variants_give_the_same_bits():
         lines = [l for l in r.stdout.splitlines() if "checksum" in l]
         assert len(lines) >= 3
         out.append(lines)
+        # k_lin_lm is launched by the launch sequences; the one-launch kernels contain the LDS form whatever the switch says
+        infos = _solve_infos(r.stdout)
+        assert len(infos) == len(lines)
+        launched = [i for i in infos if i["path"] in ("STREAMING", "LOCKSTEP")]
+        assert launched and all(i["lin_variant"] == variant for i in launched), infos
+        assert all(i["lin_variant"] == 1 for i in infos if i["path"] in ("WG", "COOP")), infos
     assert out[0] == out[1]
 
 
@@ -91,4 +107,9 @@ def test_schur_pair_launch_gives_the_same_bits():
         lines = [l for l in r.stdout.splitlines() if "checksum" in l]
         assert len(lines) == 6
         out.append(lines)
+        infos = _solve_infos(r.stdout)
+        assert len(infos) == 6
+        pairs = sum(i["pair_launches"] for i in infos if i["path"] == "STREAMING")
+        assert sum(i["pair_launches"] for i in infos) == pairs  # (only the streaming solve launches the pair kernel)
+        assert (pairs == 0) if extra else (pairs > 0), infos
     assert out[0] == out[1]

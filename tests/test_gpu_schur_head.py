@@ -95,12 +95,16 @@ def _solve_batch(ctx, windows):
     return out
 
 
-def _solve(ctx, windows, monkeypatch, env):
+def _solve(ctx, windows, monkeypatch, env, path):
+    """... under `env`; `path`: the launch path the solve has to report (limo_ctx_last_solve_info)."""
     for k in _ENV:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     out = _solve_batch(ctx, windows)
+    info = ctx.last_solve_info()
+    assert info["path"] == path and info["recovered"] == 0, (env, info)
+    _cache["info"] = info
     for k in _ENV:
         monkeypatch.delenv(k, raising=False)
     return out
@@ -111,13 +115,14 @@ _cache = {}  # results computed once, shared, never changed
 
 def _one_launch(ctx, i, monkeypatch):
     if ("one", i) not in _cache:
-        _cache["one", i] = _solve(ctx, [_window(CASES[i])], monkeypatch, {})[0]
+        _cache["one", i] = _solve(ctx, [_window(CASES[i])], monkeypatch, {}, "COOP")[0]
     return _cache["one", i]
 
 
 def _streaming(ctx, monkeypatch):
     if "stream" not in _cache:
-        _cache["stream"] = _solve(ctx, [_window(c) for c in CASES], monkeypatch, STREAMING)
+        _cache["stream"] = _solve(ctx, [_window(c) for c in CASES], monkeypatch, STREAMING, "STREAMING")
+        assert _cache["info"]["pair_launches"] > 0, _cache["info"]  # nine windows in flight: every round is a draining round
     return _cache["stream"]
 
 
@@ -145,7 +150,7 @@ def test_shapes_are_what_the_cases_are_for():
 
 @pytest.mark.parametrize("i", range(len(CASES)))
 def test_lock_step_equals_one_launch(ctx, i, monkeypatch):
-    got = _solve(ctx, [_window(CASES[i])], monkeypatch, LOCK_STEP)[0]
+    got = _solve(ctx, [_window(CASES[i])], monkeypatch, LOCK_STEP, "LOCKSTEP")[0]
     _same(_one_launch(ctx, i, monkeypatch), got, CASES[i])
 
 
@@ -156,14 +161,15 @@ def test_streaming_equals_one_launch(ctx, monkeypatch):
 
 
 def test_streaming_without_the_pair_kernel_equals_streaming(ctx, monkeypatch):
-    got = _solve(ctx, [_window(c) for c in CASES], monkeypatch, dict(STREAMING, KBA_NO_SCHUR_PAIR="1"))
+    got = _solve(ctx, [_window(c) for c in CASES], monkeypatch, dict(STREAMING, KBA_NO_SCHUR_PAIR="1"), "STREAMING")
+    assert _cache["info"]["pair_launches"] == 0, _cache["info"]
     ref = _streaming(ctx, monkeypatch)
     for i in range(len(CASES)):
         _same(ref[i], got[i], CASES[i])
 
 
 def test_lock_step_batch_with_finished_windows(ctx, monkeypatch):
-    got = _solve(ctx, [_window(CASES[i]) for i in LOCK_STEP_BATCH], monkeypatch, LOCK_STEP)
+    got = _solve(ctx, [_window(CASES[i]) for i in LOCK_STEP_BATCH], monkeypatch, LOCK_STEP, "LOCKSTEP")
     iters = [g[0][REPORT_KEYS.index("iterations_total")] for g in got]
     assert len(set(iters)) > 1, iters  # some windows finish while others iterate: their waves take the `active` exit
     for k, i in enumerate(LOCK_STEP_BATCH):
@@ -177,8 +183,11 @@ def test_streaming_under_poison_equals_streaming(ctx, monkeypatch):
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l.split()[1] for l in r.stdout.splitlines() if l.startswith("digest ")]
     assert lines == [_digest(x) for x in _streaming(ctx, monkeypatch)]
+    assert [l.split()[1] for l in r.stdout.splitlines() if l.startswith("path ")] == ["STREAMING"]
 
 
 if __name__ == "__main__":  # the streaming solve of all cases in a process of its own (KBA_POISON is read once per process)
-    for res in _solve_batch(ba.Context(0), [_window(c) for c in CASES]):
+    _ctx = ba.Context(0)
+    for res in _solve_batch(_ctx, [_window(c) for c in CASES]):
         print("digest", _digest(res))
+    print("path", _ctx.last_solve_info()["path"])

@@ -50,8 +50,9 @@ def _plain_slabs(w):
     return ((n_plain + 63) // 64 + 1) // 2
 
 
-def _solve(ctx, windows, monkeypatch, env, prepare=None):
-    """Results of one ba.Batch of copies of `windows`: per window (report fields, parameter bytes, trimmed set)."""
+def _solve(ctx, windows, monkeypatch, env, path, prepare=None):
+    """Results of one ba.Batch of copies of `windows`: per window (report fields, parameter bytes, trimmed set).  `path`: the launch
+    path the solve has to report (limo_ctx_last_solve_info)."""
     for k in _ENV:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -60,6 +61,8 @@ def _solve(ctx, windows, monkeypatch, env, prepare=None):
     if prepare is not None:
         prepare(b, monkeypatch)
     b.solve(default_options())
+    info = ctx.last_solve_info()
+    assert info["path"] == path and info["recovered"] == 0, (env, info)
     reps = b.download()
     out = []
     for i, w in enumerate(b.windows):
@@ -76,7 +79,7 @@ _tile = {}  # case index -> result of the one-launch solve (tile layout): comput
 
 def _tile_result(ctx, i, monkeypatch):
     if i not in _tile:
-        _tile[i] = _solve(ctx, [_window(CASES[i])], monkeypatch, {})[0]
+        _tile[i] = _solve(ctx, [_window(CASES[i])], monkeypatch, {}, "COOP")[0]
     return _tile[i]
 
 
@@ -100,7 +103,7 @@ def test_shapes_are_what_the_cases_are_for():
 
 @pytest.mark.parametrize("i", range(len(CASES)))
 def test_lock_step_packed_equals_one_launch_tiles(ctx, i, monkeypatch):
-    got = _solve(ctx, [_window(CASES[i])], monkeypatch, {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"})[0]
+    got = _solve(ctx, [_window(CASES[i])], monkeypatch, {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"}, "LOCKSTEP")[0]
     _same(_tile_result(ctx, i, monkeypatch), got, CASES[i])
     if CASES[i]["n_lm"] > 100:
         assert got[0][REPORT_KEYS.index("num_solves")] >= 2  # the trimming solves ran
@@ -110,7 +113,7 @@ def test_lock_step_packed_equals_one_launch_tiles(ctx, i, monkeypatch):
 
 def test_streaming_batch_packed_equals_one_launch_tiles(ctx, monkeypatch):
     ws = [_window(c) for c in CASES]
-    got = _solve(ctx, ws, monkeypatch, {"KBA_STREAM_MIN": "1"})
+    got = _solve(ctx, ws, monkeypatch, {"KBA_STREAM_MIN": "1"}, "STREAMING")
     for i in range(len(CASES)):
         _same(_tile_result(ctx, i, monkeypatch), got[i], CASES[i])
 
@@ -121,9 +124,10 @@ def test_one_launch_solve_after_a_packed_solve_of_the_same_batch(ctx, i, monkeyp
     the SAME batch lie across them.  Lock-step solve, reset, one-launch solve: the bits of a fresh batch's one-launch solve."""
     def prepare(b, mp):
         b.solve(default_options())  # (KBA_NO_COOP_SOLVE is set: packed)
+        assert ctx.last_solve_info()["path"] == "LOCKSTEP"
         b.reset()
         mp.delenv("KBA_NO_COOP_SOLVE")
         mp.delenv("KBA_NO_WG_SOLVE")
 
-    got = _solve(ctx, [_window(CASES[i])], monkeypatch, {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"}, prepare)[0]
+    got = _solve(ctx, [_window(CASES[i])], monkeypatch, {"KBA_NO_COOP_SOLVE": "1", "KBA_NO_WG_SOLVE": "1"}, "COOP", prepare)[0]
     _same(_tile_result(ctx, i, monkeypatch), got, CASES[i])
