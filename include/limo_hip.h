@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch and with limo_ctx_last_solve_info: more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
+#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch, with limo_ctx_last_solve_info and with limo_ba_solve_fixed_landmarks / limo_ba_batch_create_fixed_landmarks: more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
 
 /* Keyframe::FixationStatus, keyframe.hpp:30 */
 enum limo_fixation { LIMO_FIX_POSE = 0, LIMO_FIX_SCALE = 1, LIMO_FIX_NONE = 2 };
@@ -324,6 +324,39 @@ int limo_ba_batch_create_pose_only(limo_ctx* ctx, int32_t n_windows, const limo_
 /* create + solve + download + destroy; poses optimised in place, reports[n] may be NULL. */
 int limo_ba_adjust_pose_only_batch(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
                                    const limo_ba_options* opts, limo_ba_report* reports);
+
+/*
+ * limo_ba_solve with per-landmark constness: the window is solved against landmarks the caller trusts (a map, LiDAR, an older part
+ * of the trajectory) - motion-only bundle adjustment over several keyframes, relocalising a short sequence.  What the reference
+ * does with BundleAdjusterKeyframes::deactivateLandmarks (bundle_adjuster_keyframes.cpp:221-280; INTEGRATION.md maps its
+ * keyframe_fraction onto the flags).
+ * lm_fixed: NULL (= limo_ba_solve) or n_lm flags in the caller's landmark order; != 0: the landmark is a constant parameter block
+ * (:262-269).
+ *   - Problem build.  Everything else is solve()'s: ground rows, scale and ground-plane regularisers, constness of keyframes, the
+ *     trimming schedule.  The block counts of the report do not depend on the flags: a constant landmark keeps its residual
+ *     blocks, takes part in trimming like any other (limo_ba_batch_trimmed reports it if trimmed) and comes back bit for bit as it
+ *     went in.
+ *   - Fixed cost.  A residual block without a variable parameter block - a reprojection / depth block, or a ground-height block,
+ *     of a LIMO_FIX_POSE keyframe (its plane is fixed with it, :208-216) and a constant landmark - belongs to the fixed cost of
+ *     each Ceres-style solve of the schedule: evaluated with its loss at the start of that solve, after the trimming rounds before
+ *     it.  initial_cost and final_cost include it; the cost the step acceptance, the function tolerance and every other relative
+ *     test see does not (Ceres' reduced program).  This holds for any kf_fixation pattern: the LIMO_FIX_POSE keyframes need not
+ *     lead the window.
+ *   - Nothing to optimise.  A window whose parameter blocks are all constant returns LIMO_CONVERGENCE with zero iterations and
+ *     initial_cost == final_cost == that fixed cost.
+ *   - No change without flags.  lm_fixed == NULL, a NULL entry or all-zero flags give the result of limo_ba_solve /
+ *     limo_ba_batch_create bit for bit.
+ *   - Launch paths.  Window i of a batch gets its single call's result bit for bit, on every launch path
+ *     (limo_ctx_last_solve_info).  A window without a variable landmark has no Schur blocks: no Schur kernel runs for it.
+ *   - Not offered: limo_ba_solve_sharded takes no flags, and the C++ shim (limo_amd/kba) does not call these two.
+ */
+int limo_ba_solve_fixed_landmarks(limo_ctx* ctx, limo_ba_window* window, const uint8_t* lm_fixed, const limo_ba_options* opts,
+                                  limo_ba_report* report);
+/* lm_fixed: NULL, or n_windows entries, each NULL or that window's n_lm flags.  The batch is used with limo_ba_batch_solve / _reset /
+ * _download / _trimmed / _destroy like any other; n_windows <= 0 and NULL arguments: as limo_ba_batch_create.  The flags are read
+ * during the call only. */
+int limo_ba_batch_create_fixed_landmarks(limo_ctx* ctx, int32_t n_windows, const limo_ba_window* windows, const uint8_t* const* lm_fixed,
+                                         limo_ba_batch** out);
 
 /*
  * The residual rows of a window that are NOT reprojection / depth blocks, linearised at the window's current parameters the

@@ -56,9 +56,15 @@ class Context:
             pass
 
     # ---- single window
-    def solve(self, window, opts):
+    def solve(self, window, opts, lm_fixed=None):
+        """limo_ba_solve; lm_fixed (one flag per landmark, non-zero = constant parameter block): limo_ba_solve_fixed_landmarks."""
         s = window.as_struct()
         rep = _ffi.BaReport()
+        if lm_fixed is not None:
+            flags = fixed_flags(lm_fixed, window.n_lm)
+            rc = self.lib.limo_ba_solve_fixed_landmarks(self.ptr, C.byref(s), flags.ctypes.data_as(_ffi.c_uint8_p), C.byref(opts), C.byref(rep))
+            _check(rc, self.ptr, "limo_ba_solve_fixed_landmarks")
+            return rep.as_dict()
         _check(self.lib.limo_ba_solve(self.ptr, C.byref(s), C.byref(opts), C.byref(rep)), self.ptr, "limo_ba_solve")
         return rep.as_dict()
 
@@ -168,6 +174,14 @@ class Context:
         return _ffi.rows_as_dicts(rows, n.value)
 
 
+def fixed_flags(lm_fixed, n_lm):
+    """One uint8 flag per landmark of a window (non-zero: constant), contiguous, at least one byte long."""
+    flags = np.ascontiguousarray(lm_fixed).astype(bool).astype(np.uint8).ravel()
+    if flags.size != n_lm:
+        raise ValueError("lm_fixed: %d flags for %d landmarks" % (flags.size, n_lm))
+    return flags if n_lm else np.zeros(1, np.uint8)
+
+
 def prior_array(priors, n):
     """limo_speed_prior[n] for a list of _ffi.SpeedPrior / None (None: speed_weight 0, no prior for that window); None for priors=None."""
     if priors is None:
@@ -185,22 +199,35 @@ def prior_array(priors, n):
 class Batch:
     """Many independent windows resident in HBM (limo_ba_batch_*)."""
 
-    def __init__(self, ctx, windows, arr=None, pose_only=False, priors=None):
+    def __init__(self, ctx, windows, arr=None, pose_only=False, priors=None, lm_fixed=None):
         """arr: struct_array(windows) made earlier (the array of limo_ba_window a C / C++ caller holds anyway: building it from
         numpy windows is ~20 us of Python per window and not part of the library call).
         pose_only=True: every window is an adjustPoseOnly problem (limo_ba_batch_create_pose_only), priors = None or one
-        _ffi.SpeedPrior / None per window."""
+        _ffi.SpeedPrior / None per window.
+        lm_fixed: None, or one entry per window, each None or that window's per-landmark flags (non-zero: the landmark is a constant
+        parameter block) - limo_ba_batch_create_fixed_landmarks."""
         self.ctx = ctx
         self.lib = ctx.lib
         self.windows = list(windows)
         self._arr = struct_array(self.windows) if arr is None else arr
         self.ptr = C.c_void_p()
         if pose_only:
+            if lm_fixed is not None:
+                raise ValueError("lm_fixed belongs to a solve batch: the landmarks of a pose_only batch are all constant")
             rc = self.lib.limo_ba_batch_create_pose_only(ctx.ptr, len(self.windows), self._arr, prior_array(priors, len(self.windows)), C.byref(self.ptr))
             _check(rc, ctx.ptr, "limo_ba_batch_create_pose_only")
             return
         if priors is not None:
             raise ValueError("priors belong to a pose_only batch")
+        if lm_fixed is not None:
+            lm_fixed = list(lm_fixed)
+            if len(lm_fixed) != len(self.windows):
+                raise ValueError("lm_fixed: %d entries for %d windows" % (len(lm_fixed), len(self.windows)))
+            keep = [None if f is None else fixed_flags(f, w.n_lm) for f, w in zip(lm_fixed, self.windows)]
+            ptrs = (_ffi.c_uint8_p * max(1, len(keep)))(*[None if f is None else f.ctypes.data_as(_ffi.c_uint8_p) for f in keep])
+            rc = self.lib.limo_ba_batch_create_fixed_landmarks(ctx.ptr, len(self.windows), self._arr, ptrs, C.byref(self.ptr))
+            _check(rc, ctx.ptr, "limo_ba_batch_create_fixed_landmarks")
+            return
         _check(self.lib.limo_ba_batch_create(ctx.ptr, len(self.windows), self._arr, C.byref(self.ptr)), ctx.ptr, "limo_ba_batch_create")
 
     def solve(self, opts):

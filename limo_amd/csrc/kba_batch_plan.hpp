@@ -179,8 +179,9 @@ struct SolveChoice {
 inline int plain_groups(const WinDesc& d, int span) { return (d.n_sblk_plain + span - 1) / span; }
 inline int gp_groups(const WinDesc& d, int span_gp) { return (d.n_sblk - d.n_sblk_plain + span_gp - 1) / span_gp; }
 
-// k_solve_wg (a whole solve in ONE launch, a workgroup per window): windows without free landmarks - adjustPoseOnly - whose
-// landmark workgroups a single workgroup walks through in a few microseconds.
+// k_solve_wg (a whole solve in ONE launch, a workgroup per window): batches without a Schur block - adjustPoseOnly windows, and solve
+// windows of any number of keyframes whose landmarks are all constant (PackOptions::lm_fixed) - whose landmark workgroups a single
+// workgroup walks through in a few microseconds.
 inline bool wg_solve_applies(const PackedBatch& P, const BatchPlan& plan, const SolveSwitches& sw, int shard_P) {
     if (shard_P != 1 || P.evaluate_only || P.n_sblk != 0 || P.n_win < 1 || sw.no_wg) return false;
     for (const WinDesc& d : P.win)
@@ -218,8 +219,10 @@ inline bool coop_solve_applies(const PackedBatch& P, const BatchPlan& plan, cons
 // not with a wall-clock cap (a per-solve clock, run_schedule keeps it).  Small batches (<= coop_max_win windows of the common shape)
 // run as ONE launch: a workgroup per window (no free landmark) or G workgroups per window.  All paths give the same bits.
 // A batch of SEVERAL adjustPoseOnly windows takes k_solve_wg at any size - its workgroups never wait for each other, so the grid
-// need not be resident at once - or else the lock-step sequence.  Never the slot scheduler (its Schur worklists have not seen
-// windows without Schur blocks) and never device-wide barriers over several such windows.
+// need not be resident at once - or else the lock-step sequence.  Never the slot scheduler and never device-wide barriers over several
+// such windows: no test holds those paths for a pose-only batch.  (Windows without Schur blocks as such are no obstacle to either: a
+// solve batch with constant landmarks may hold them - every landmark of a window flagged - and takes the paths of any solve batch;
+// their Schur list counts are zero, tests/test_gpu_fixed_landmarks.py.)
 // The cooperative solve starts only from the pristine state - its timeout recovery restores THAT state, a warm re-solve would lose
 // the first solve's result - and not in a context whose launches keep timing out (something shares the GPU): three strikes switch
 // it off, but not for the life of the context: the kCoopRetryAfter-th benched solve makes ONE more attempt (a profiler session or

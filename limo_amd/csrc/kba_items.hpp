@@ -455,6 +455,10 @@ KBA_HD int lin_lm_lane(const BatchView& bv, const SolveConsts& c, int w, int gl,
         double r3[3], c4[4];
         if (j < wd.n_view_fixed0) {  // keyframe without a free pose block: cost and residual only (nobody reads its planes)
             if (!lin_obs<false>(vl, c, in, want_cost, r3, c4, cam[j])) fail = 1;
+            if (state == 2) {  // neither block is variable: the pair's cost is fixed cost, not part of x_cost (kLinFixedCost)
+                cam[j].e[kLinFixedCost] = cam[j].e[0];
+                cam[j].e[0] = 0.0;
+            }
         } else {
             if (!lin_obs<true>(vl, c, in, want_cost, r3, c4, cam[j])) fail = 1;
             bv.obs_c[s] = c4[0];  // (au, sd: the residual stays in the lane, xn / yn are rebuilt from the landmark: view_xy)
@@ -495,11 +499,17 @@ KBA_HD void trim_residual_lane(const BatchView& bv, int b, int t, double* plane_
 }
 
 // ======================================================================================= ground plane
+// A ground-height row whose keyframe is pose-fixed (its plane is fixed with it, bundle_adjuster_keyframes.cpp:208-216) and whose
+// landmark is constant has no variable parameter block: its cost belongs to the fixed cost of a solve.
+KBA_HD bool gp_row_fixed(const BatchView& bv, int g) {
+    return bv.lm_state[bv.gp_lm[g]] == 2 && !bv.cmask[(int64_t)bv.gp_kf[g] * kCamSlots];
+}
 KBA_HD void gp_lane(const BatchView& bv, int g, bool candidate, double* cost_out) {
     const int gl = bv.gp_lm[g];
     const int gk = bv.gp_kf[g];
     GpOut o;
-    if (!bv.lm_state[gl]) {
+    const int state = bv.lm_state[gl];
+    if (!state) {
         if (!candidate) {
             bv.gp_r[g] = 0.0;
             for (int i = 0; i < 10; ++i) bv.gp_F[i * bv.SG + g] = 0.0;
@@ -509,6 +519,10 @@ KBA_HD void gp_lane(const BatchView& bv, int g, bool candidate, double* cost_out
         return;
     }
     if (candidate) {
+        if (state == 2 && !bv.cmask[(int64_t)gk * kCamSlots]) {  // gp_row_fixed: fixed cost, not part of the candidate cost
+            cost_out[g] = 0.0;
+            return;
+        }
         gp_residual_jacobian(bv.pose_c + 7 * (int64_t)gk, bv.pdir_c + 3 * (int64_t)gk, bv.pdist_c[gk],
                              bv.lm_c + 3 * (int64_t)gl, bv.gp_w[g], true, false, &o);
         cost_out[g] = o.cost;
@@ -906,6 +920,8 @@ KBA_HD void backsub_lane(const BatchView& bv, const SolveConsts& c, int w, int g
     const double c_rep = 1.0 / (c.a_rep * c.a_rep), c_dep = 1.0 / (c.a_dep * c.a_dep);
     LogProd lp_rep = {1.0, 0}, lp_dep = {1.0, 0};
     int fail = 0;
+    // (a constant landmark's pairs with the leading views of keyframes without a free pose block are fixed cost: not evaluated here)
+    const int j_prog = state == 2 ? wd.n_view_fixed0 : 0;
     {
         int s_cur = slot[0];
         int s_nxt = n_view > 1 ? slot[bv.SL] : -1;
@@ -917,7 +933,7 @@ KBA_HD void backsub_lane(const BatchView& bv, const SolveConsts& c, int w, int g
             dn = bv.obs_d[o];
         }
         for (int j = 0; j < n_view; ++j) {
-            const bool have = s_cur >= 0;
+            const bool have = s_cur >= 0 && j >= j_prog;
             const float u = un, v = vn, d = dn;
             s_cur = s_nxt;
             s_nxt = j + 2 < n_view ? slot[(int64_t)(j + 2) * bv.SL] : -1;
@@ -1515,7 +1531,19 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     for (int i = tid; i < wd.n_lblk * wd.n_view; i += nt) cost += bv.lv_part[wd.lvpart_off + (int64_t)i * kLinPartial];
     for (int b = wd.lblk0 + tid; b < wd.lblk0 + wd.n_lblk; b += nt)
         if (bv.lblk_linfail[b] != 0.0) failf = 1.0;
-    for (int g = wd.gp0 + tid; g < wd.gp0 + wd.n_gp; g += nt) cost += bv.gp_cost[g];
+    if (wd.n_lm_const) {  // (uniform) constant landmarks: blocks without a variable parameter are fixed cost - the pairs of a constant
+                          // landmark with a view without a free pose block (kLinFixedCost), ground rows of such a keyframe and landmark
+        for (int i = tid; i < wd.n_lblk * wd.n_view_fixed0; i += nt)
+            reg_fixed += bv.lv_part[wd.lvpart_off + ((int64_t)(i / wd.n_view_fixed0) * wd.n_view + i % wd.n_view_fixed0) * kLinPartial + kLinFixedCost];
+        for (int g = wd.gp0 + tid; g < wd.gp0 + wd.n_gp; g += nt) {
+            const double v = bv.gp_cost[g];
+            const bool fixed = gp_row_fixed(bv, g);
+            cost += fixed ? 0.0 : v;
+            reg_fixed += fixed ? v : 0.0;
+        }
+    } else {
+        for (int g = wd.gp0 + tid; g < wd.gp0 + wd.n_gp; g += nt) cost += bv.gp_cost[g];
+    }
     for (int i = tid; i < nrows; i += nt) {
         if (rows[i].n < 0)
             reg_fixed += 0.5 * rows[i].r * rows[i].r;
@@ -1559,6 +1587,7 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         r.lin_fail = failf != 0.0;
         r.gmax = gmax;
         r.xnorm2 = xn2;
+        r.no_variable = wd.nf == 0 && wd.n_lm_const > 0 && wd.n_lm_const == wd.n_lm;
         bv.reg_cost[2 * w] = reg_free;
         bv.reg_cost[2 * w + 1] = reg_fixed;
     }

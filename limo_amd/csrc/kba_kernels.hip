@@ -467,7 +467,11 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     //      a sliding window): same pipeline, same landmark-block terms, but no planes stored, no pose Jacobian, no U / g, and only the
     //      cost leaves the wave (the slice's other 27 entries are zeros).  A loop of its own: the general loop below stays one
     //      straight-line body (a uniform branch inside it cost more than the skipped third of the arithmetic gave back).
+    //      Where the cost goes: entry 0 (x_cost), or - the workgroups of a window's constant run (WinDesc::n_lm_const; no workgroup
+    //      straddles its start, kba_pack.cpp) - entry kLinFixedCost: a pair of a constant landmark and a pose-fixed keyframe has no
+    //      variable parameter block, its cost is fixed cost.  Uniform over the workgroup: a select of the slot, no second reduction.
     const int j_cam0 = wd.n_view_fixed0;
+    const int cost_slot = bv.lblk_lm0[b] - wd.lm0 >= wd.n_lm - wd.n_lm_const ? kLinFixedCost : 0;
     for (int j = 0; j < j_cam0; ++j) {
         // (the constants are read where they are used - scalar loads the compiler places next to their instructions; a local
         // copy of all 55 would not fit the scalar register file)
@@ -492,7 +496,7 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         // (no planes stored: the Schur fills load them for keyframes with a free pose block only, k_backsub starts behind these views)
         accum(vl, r3, c4);
         const double tot = wave_sum_all(l.e[0]);
-        if (lane < kLinPartial) lv_lds[(j * kLinWaves + wave) * kLinPartial + lane] = lane == 0 ? tot : 0.0;
+        if (lane < kLinPartial) lv_lds[(j * kLinWaves + wave) * kLinPartial + lane] = lane == cost_slot ? tot : 0.0;
     }
     for (int j = j_cam0; j < n_view; ++j) {
         VT vl = vc + (int64_t)j * kVStride;

@@ -37,6 +37,9 @@ constexpr int kMaxRegRows = 1 + (kMaxKf - 1) * 5 + 3 * kMaxKf;  // scale + per p
 // number of doubles in a block partial of the linearize kernel: cost, 21 (U upper) + 6 (g)
 constexpr int kGpRed = 65;  // per keyframe: upper triangle of F^T F (10 x 10: 55) + F^T r (10) of ground-plane rows (BatchView::x_gp)
 constexpr int kLinPartial = 28;
+constexpr int kLinFixedCost = 26;  // entry of a view's partial the camera assembly never reads (lin_cam_half1: 26 sums of 28): of a view
+                                   // WITHOUT a free pose block it holds the cost of the pairs whose landmark is constant as well - blocks
+                                   // without a variable parameter, the fixed cost of a solve (fixed-landmark windows)
 constexpr int kLinWaves = 4;      // waves of a landmark workgroup: each keeps its own camera-side partial sums (no barrier per view)
 
 // One wave of k_evaluate (evaluate-only batches): the ALIGNED range of 64 observations [base, base + 64) of the observation block
@@ -66,7 +69,8 @@ struct WinDesc {
     int32_t nf, nf_pad;       // free camera slots (compact Schur system); nf + 1 (rhs column) rounded up to 16
     int32_t nfq;              // free POSE slots: compact indices [0,nfq) are pose slots, [nfq,nf) plane slots.  In the
                               // Schur tile / slab column nfq holds the rhs, so compact index i sits in column i + (i >= nfq)
-    int32_t lm_gp0;           // first (global) landmark of the window that carries a ground-plane row (they are packed last)
+    int32_t lm_gp0;           // first (global) VARIABLE landmark of the window that carries a ground-plane row (they are packed behind the
+                              // plain ones; a constant run, n_lm_const, follows them)
     int32_t cam0;             // first global camera-slot index = kf0*10
     int32_t reg0;             // first row in the regulariser row buffers
     int32_t has_scale_reg, has_gp_reg;
@@ -75,8 +79,12 @@ struct WinDesc {
     int32_t pose_only;        // adjustPoseOnly problem (landmarks constant)
     int32_t n_view_fixed0;    // the window's first n_view_fixed0 views belong to keyframes WITHOUT a free pose block (the Pose-fixed
                               // oldest keyframe of a sliding window): k_lin_lm forms no camera-side sums for them, k_backsub no
-                              // camera-step term - their own short loops in front of the general ones (view order unchanged)
-    int32_t pad_view;
+                              // camera-step term - their own short loops in front of the general ones (view order unchanged).
+                              // In a window with constant landmarks the views of EVERY pose-fixed keyframe are packed first
+                              // (kba_pack.cpp, pass 1), so this counts all views without a free pose block
+    int32_t n_lm_const;       // a solve window with per-landmark constness (PackOptions::lm_fixed): its LAST n_lm_const packed landmarks are
+                              // the constant run (lm_state 2 or 0) - landmark workgroups of their own, no Schur block; 0 everywhere else
+                              // (the constant landmarks of a pose-only window are not counted: no fixed cost, no Schur blocks at all)
     double scale_w, scale_s0; // PoseRegularization weight and target
     double speed_w, speed_dt, speed_vel[3], speed_Rb[9], speed_tb[3];  // SpeedRegularizationVector2 (pose-only)
     int64_t hcc_off;          // offset (doubles) of this window's nc x nc matrix in the Hcc buffer
@@ -142,7 +150,8 @@ struct WinRed {
     double step2;       // |x - x_candidate|^2
     double cand2;       // |x_candidate|^2
     double cand_cost;   // cost at the candidate (free blocks)
-    int32_t lin_fail, chol_fail, cand_fail, pad;
+    int32_t lin_fail, chol_fail, cand_fail;
+    int32_t no_variable;  // the window has no variable parameter block at all: the solve ends before its first iteration (lm_decide_lin)
 };
 
 // Phases of one window in the solveTrimmed schedule (robust_solving.cpp:160-248) when every window advances on its own
@@ -204,7 +213,7 @@ struct BatchView {
     const int32_t* lm_win;      // [TL]
     const int32_t* lm_id;       // [TL] index of the landmark in the caller's window (ties in trimming resolve by id)
     const double* lm_weight;    // [TL]
-    uint8_t* lm_state;          // [TL] 1 = in problem, 0 = removed by trimming / not constrained
+    uint8_t* lm_state;          // [TL] 1 = in problem, 2 = in problem as a constant block, 0 = removed by trimming / not constrained
     const int32_t* lm_gp;       // [TL] ground-plane residual index or -1
     const int32_t* lm_slot;     // [Vmax*SL] observation index per (view-in-window, landmark) or -1
     const int32_t* view_kf;     // [TV] global keyframe index
@@ -283,7 +292,8 @@ struct BatchView {
     double *S_part;             // Schur partial slabs
     double *S_red;              // landmark-sharded solve: one slab per (window, shard) = sum of the shard's partial slabs
     double* cam_scratch;        // scratch of the window-level kernels for windows too large for LDS (WinDesc::cam_scr_off)
-    double* reg_cost;           // [n_win*2]: free / fixed regulariser cost at the linearisation point
+    double* reg_cost;           // [n_win*2]: free regulariser cost / fixed cost (regulariser rows and residual blocks without a variable
+                                // parameter block) at the linearisation point
     // --- trimming
     double *trim_rep, *trim_dep;   // [TL] max un-robustified residual norm per landmark, <0 = no block
     int32_t* n_active;          // [2] {windows still iterating, workgroups of k_cam_assemble done} of this iteration

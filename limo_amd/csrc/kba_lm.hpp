@@ -136,6 +136,19 @@ KBA_HD void lm_decide_lin(WinState& s, const WinRed& r, double fixed_cost, const
         s.first = 0;
         return;
     }
+    if (s.first && r.no_variable) {  // Solve(): "No non-constant parameter blocks found." - CONVERGENCE before the first iteration,
+                                     // initial cost = final cost = the fixed cost; not a linearisation of the report
+        s.first = 0;
+        s.x_cost = 0.0;
+        s.x_norm = 0.0;
+        s.gmax = 0.0;
+        s.n_success = 0;
+        s.fixed_cost = fixed_cost;
+        s.solve_initial_cost = fixed_cost;
+        if (s.acc_solves == 1) s.first_initial_cost = fixed_cost;
+        lm_terminate(s, LIMO_CONVERGENCE);
+        return;
+    }
     // the cost at an accepted candidate is already known (HandleSuccessfulStep: x_cost = candidate_cost); only the
     // first linearisation of a solve evaluates it (kernels skip the cost value otherwise)
     s.x_cost = s.first ? r.lin_cost : s.cost_pending;

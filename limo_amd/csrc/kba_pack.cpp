@@ -276,13 +276,24 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
                 return fail(LIMO_ERR_INVALID, "observation index out of range");
             vid[(size_t)k * W.n_cam + c] = 0;
         }
+        // View order: by keyframe, then camera.  A window with constant landmarks (PackOptions::lm_fixed, a flag set) takes the views
+        // of ALL its LIMO_FIX_POSE keyframes first, wherever they stand in the window (each group by keyframe, then camera): they are
+        // the views without a free pose block, WinDesc::n_view_fixed0 then counts every one of them, and the fixed-cost rule for
+        // (pose-fixed keyframe, constant landmark) blocks holds for any kf_fixation pattern.  Windows without a flag set keep the
+        // plain order (their bits depend on it).
+        bool fixed_first = false;
+        if (po.lm_fixed && po.lm_fixed[w] && !po.pose_only && !po.evaluate_only)
+            for (int l = 0; l < W.n_lm && !fixed_first; ++l) fixed_first = po.lm_fixed[w][l] != 0;
         int nv = 0;
-        for (int k = 0; k < W.n_kf; ++k)
-            for (int c = 0; c < W.n_cam; ++c)
-                if (vid[(size_t)k * W.n_cam + c] == 0) {
-                    vid[(size_t)k * W.n_cam + c] = nv++;
-                    views[w].push_back({k, c});
-                }
+        for (int pass = fixed_first ? 0 : 1; pass < 2; ++pass)
+            for (int k = 0; k < W.n_kf; ++k) {
+                if (fixed_first && (W.kf_fixation[k] == LIMO_FIX_POSE) != (pass == 0)) continue;
+                for (int c = 0; c < W.n_cam; ++c)
+                    if (vid[(size_t)k * W.n_cam + c] == 0) {
+                        vid[(size_t)k * W.n_cam + c] = nv++;
+                        views[w].push_back({k, c});
+                    }
+            }
         if (nv > kMaxViews) return fail(LIMO_ERR_INVALID, "window has more than kMaxViews (64) (keyframe, camera) views with observations");
         obs_view[w].resize(W.n_obs);
         for (int i = 0; i < W.n_obs; ++i) obs_view[w][i] = vid[(size_t)W.obs_kf[i] * W.n_cam + W.obs_cam[i]];
@@ -424,7 +435,22 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
         // packed landmark order: plain landmarks, then ground-plane landmarks; inside each class by owning shard
         // (landmark id mod n_shards), then input order.  seg[] = start of every run of one (class, shard):
         // with n_shards > 1 no workgroup straddles a run, so every workgroup has exactly one owner.
+        // Constant landmarks (PackOptions::lm_fixed) come behind all of them, in input order, as one more run: a landmark workgroup
+        // is variable or constant as a whole (kba_kernels.hip:lin_lm_block), and the Schur blocks end where the run starts.
         const int NS = std::max(1, po.shards);
+        const uint8_t* fixed_in = (po.lm_fixed && !po.pose_only && !po.evaluate_only) ? po.lm_fixed[w] : nullptr;
+        std::vector<uint8_t> cst(W.n_lm, 0);
+        int n_const = 0;
+        if (fixed_in)
+            for (int l = 0; l < W.n_lm; ++l) n_const += cst[l] = fixed_in[l] != 0;
+        if (n_const && NS > 1) {  // (a guard: no entry point of the library sets both - limo_ba_solve_sharded takes no flags)
+            L.err = "constant landmarks in a landmark-sharded batch";
+            L.rc = LIMO_ERR_INVALID;
+            return;
+        }
+        const int n_var = W.n_lm - n_const;
+        int n_gp_var = 0;
+        for (const GpTmp& g : gp_tmp) n_gp_var += !cst[g.lm];
         std::vector<int> perm(W.n_lm), seg;
         {
             int nxt = 0;
@@ -432,12 +458,16 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
                 for (int r = 0; r < NS; ++r) {
                     const int before = nxt;
                     for (int l = 0; l < W.n_lm; ++l)
-                        if (has_gp[l] == pass && l % NS == r) perm[l] = nxt++;
+                        if (!cst[l] && has_gp[l] == pass && l % NS == r) perm[l] = nxt++;
                     if (NS > 1 && nxt > before) seg.push_back(before);
                 }
+            for (int l = 0; l < W.n_lm && n_const; ++l)
+                if (cst[l]) perm[l] = nxt++;
             if (seg.empty()) seg.push_back(0);
+            if (n_const && n_var > 0) seg.push_back(n_var);
             seg.push_back(W.n_lm);
-            d.lm_gp0 = d.lm0 + W.n_lm - (int)gp_tmp.size();
+            d.lm_gp0 = d.lm0 + n_var - n_gp_var;
+            d.n_lm_const = n_const;
         }
         std::vector<int> seg_of(W.n_lm, 0);  // run index of a packed landmark
         for (size_t si = 0; si + 1 < seg.size(); ++si)
@@ -554,6 +584,10 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
         {
             for (const GpTmp& g : gp_tmp)
                 if (P.lm_state[d.lm0 + perm[g.lm]] == 0) P.lm_state[d.lm0 + perm[g.lm]] = 1;  // constrained by its gp block only
+            // constant landmarks (deactivateLandmarks, bundle_adjuster_keyframes.cpp:262-269): in the problem with every residual block
+            // they have, as constant parameter blocks
+            for (int l = n_var; l < W.n_lm; ++l)
+                if (P.lm_state[d.lm0 + l] == 1) P.lm_state[d.lm0 + l] = 2;
             // rows sorted by keyframe (stable in landmark order) so each keyframe owns a contiguous range
             std::stable_sort(gp_tmp.begin(), gp_tmp.end(), [](const GpTmp& a, const GpTmp& b) { return a.kf < b.kf; });
             for (const GpTmp& g : gp_tmp) {
@@ -646,10 +680,13 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
         d.n_sblk_plain = 0;
         if (!po.pose_only && !po.evaluate_only && d.nf > 0) {
             const int per = kSchurLmPerBlock;
-            // no Schur block straddles a shard run or the plain / ground-plane boundary
-            const int n_plain = W.n_lm - (int)gp_tmp.size();
-            std::vector<int> cuts(seg);
+            // no Schur block straddles a shard run or the plain / ground-plane boundary, and none reaches into the constant run
+            const int n_plain = n_var - n_gp_var;
+            std::vector<int> cuts;
+            for (int v : seg)
+                if (v < n_var) cuts.push_back(v);
             cuts.push_back(n_plain);
+            cuts.push_back(n_var);
             std::sort(cuts.begin(), cuts.end());
             cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
             for (size_t si = 0; si + 1 < cuts.size(); ++si)

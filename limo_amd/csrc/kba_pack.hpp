@@ -117,6 +117,11 @@ struct PackOptions {
     // in the error text.
     bool per_window_prior = false;
     const limo_speed_prior* window_priors = nullptr;
+    // Solve windows with per-landmark constness (limo_ba_solve_fixed_landmarks): null, or one entry per window, each null or that
+    // window's n_lm flags in the caller's landmark order - != 0: the landmark is a constant parameter block (lm_state 2).  The
+    // flagged landmarks of a window form their own run of the packed order behind the variable ones (WinDesc::n_lm_const): landmark
+    // workgroups of their own, no Schur block.  A window without a flag set packs exactly as it does without the array.
+    const uint8_t* const* lm_fixed = nullptr;
 };
 
 // Returns LIMO_OK or a negative limo_status; err receives a message.

@@ -691,7 +691,10 @@ struct limo_ba_batch : Executor {
         if (c.slab_packed) spart_has_packed = true;
         const WorkLists& a = wl[0].cur;  // (the window list is the same for every view)
         {
-            EventPair* ep = timed(LIMO_KERNEL_SCHUR);
+            // (a step without Schur blocks - no window with a variable landmark - launches nothing and counts no launch)
+            int n_schur = 0;
+            for (size_t i = 0; i < pv.size(); ++i) n_schur += wl[i].cur.n_sblk;
+            EventPair* ep = n_schur ? timed(LIMO_KERNEL_SCHUR) : nullptr;
             for (size_t i = 0; i < pv.size(); ++i) {
                 const WorkLists& l = wl[i].cur;
                 launch_schur(pv[i], l.sblk, l.n_sblk_plain, l.sblk + l.n_sblk_plain, l.n_sblk_fgp, l.sblk + l.n_sblk_plain + l.n_sblk_fgp,
@@ -879,7 +882,7 @@ struct limo_ba_batch : Executor {
         LAUNCH_CHECK("linearisation kernels");
         // ---- trust-region step of the windows that iterate
         {
-            EventPair* ep = time_kernels ? timed(LIMO_KERNEL_SCHUR, s) : nullptr;
+            EventPair* ep = time_kernels && (cap[SL_SPLAIN] || cap[SL_SFGP] || cap[SL_SGEN]) ? timed(LIMO_KERNEL_SCHUR, s) : nullptr;
             // few windows in flight (the batch drains): both fast-class lists in one launch (kba_kernels.hip:k_schur_lean_pair)
             const bool pair = schur_pair_ok && bound <= kSchurPairBound && cap[SL_SPLAIN] && cap[SL_SFGP];
             launch_schur(sv, L(SL_SPLAIN), cap[SL_SPLAIN], L(SL_SFGP), cap[SL_SFGP], L(SL_SGEN), cap[SL_SGEN], pair, s);
@@ -1602,6 +1605,22 @@ int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]) {
 int limo_ba_solve(limo_ctx* ctx, limo_ba_window* window, const limo_ba_options* opts, limo_ba_report* report) {
     if (!ctx || !window) return LIMO_ERR_INVALID;
     return solve_n(ctx, 1, window, opts, PackOptions(), report, "limo_ba_solve");
+}
+
+int limo_ba_solve_fixed_landmarks(limo_ctx* ctx, limo_ba_window* window, const uint8_t* lm_fixed, const limo_ba_options* opts,
+                                  limo_ba_report* report) {
+    if (!ctx || !window) return LIMO_ERR_INVALID;
+    PackOptions po;
+    po.lm_fixed = lm_fixed ? &lm_fixed : nullptr;
+    return solve_n(ctx, 1, window, opts, po, report, "limo_ba_solve_fixed_landmarks");
+}
+
+int limo_ba_batch_create_fixed_landmarks(limo_ctx* ctx, int32_t n_windows, const limo_ba_window* windows, const uint8_t* const* lm_fixed,
+                                         limo_ba_batch** out) {
+    // (do_trim from the default options here, refreshed by limo_ba_batch_solve(opts): as limo_ba_batch_create)
+    PackOptions po;
+    po.lm_fixed = lm_fixed;
+    return batch_create_impl(ctx, n_windows, windows, nullptr, po, out);
 }
 
 int limo_ba_adjust_pose_only(limo_ctx* ctx, limo_ba_window* window, const limo_speed_prior* prior,
