@@ -89,7 +89,7 @@ void for_each_buffer(const PackedBatch& P, BatchView& bv, F f) {
     KBA_BUF(gp_cost_c, TG * D, nullptr);
     // evaluate-only batches (limo_ba_evaluate): rows u, v over the observations + the depth row over the depth observations
     KBA_BUF(obs_r, (size_t)(P.evaluate_only ? P.SO * 2 + P.SD : 1) * D, nullptr);
-    KBA_BUF(obs_c, (size_t)(P.evaluate_only ? 1 : P.SO * 2) * D, nullptr);
+    KBA_BUF(obs_c, (P.evaluate_only ? 1 : P.lm_slot.size() * 2) * D, nullptr);  // two planes over lm_slot's entries (kba_layout.hpp:obs_c_stride)
     KBA_BUF(obs_Jp, (size_t)(P.evaluate_only ? P.SO * 12 + P.SD * 6 : 1) * D, nullptr);
     KBA_BUF(obs_Jl, (size_t)(P.evaluate_only ? P.SO * 6 + P.SD * 3 : 1) * D, nullptr);
     if (P.evaluate_only) KBA_BUF(echunk, (size_t)std::max(1, P.n_echunk) * sizeof(EvalChunk), P.echunk.empty() ? nullptr : P.echunk.data());

@@ -441,6 +441,10 @@ KBA_HD int lin_lm_lane(const BatchView& bv, const SolveConsts& c, int w, int gl,
         for (int i = 0; i < kLinPartial; ++i) cam[j].e[i] = 0.0;
     }
     const int state = bv.lm_state[gl];
+    // the planes of the pair (view j, landmark): written for EVERY view with a free pose block, +0.0 where the pair does not exist
+    // (kba_layout.hpp:BatchView::obs_c)
+    const int64_t PS = obs_c_stride(bv);
+    for (int j = wd.n_view_fixed0; j < wd.n_view; ++j) bv.obs_c[(int64_t)j * bv.SL + gl] = bv.obs_c[PS + (int64_t)j * bv.SL + gl] = 0.0;
     if (state == 0) return 0;
     LmAcc acc;
     for (int i = 0; i < 6; ++i) acc.V[i] = 0.0;
@@ -461,8 +465,8 @@ KBA_HD int lin_lm_lane(const BatchView& bv, const SolveConsts& c, int w, int gl,
             }
         } else {
             if (!lin_obs<true>(vl, c, in, want_cost, r3, c4, cam[j])) fail = 1;
-            bv.obs_c[s] = c4[0];  // (au, sd: the residual stays in the lane, xn / yn are rebuilt from the landmark: view_xy)
-            bv.obs_c[bv.SO + s] = c4[3];
+            bv.obs_c[(int64_t)j * bv.SL + gl] = c4[0];  // (au, sd: the residual stays in the lane, xn / yn are rebuilt from the landmark: view_xy)
+            bv.obs_c[PS + (int64_t)j * bv.SL + gl] = c4[3];
         }
         lin_lm_accum(vl, r3, c4, acc);
     }
@@ -667,8 +671,8 @@ KBA_HD void schur_pair_block(const BatchView& bv, const WinDesc& wd, int gl, int
                 have = true;
             }
             double Ft[9], c4[4];
-            c4[0] = bv.obs_c[s];
-            c4[3] = bv.obs_c[bv.SO + s];
+            c4[0] = bv.obs_c[(int64_t)j * bv.SL + gl];  // the pair's planes (kba_layout.hpp:BatchView::obs_c)
+            c4[3] = bv.obs_c[obs_c_stride(bv) + (int64_t)j * bv.SL + gl];
             view_xy(bv.view_lin + (int64_t)kViewLin * (wd.view0 + j), bv.lm + 3 * (int64_t)gl, &c4[1], &c4[2]);
             ft_build(c4, bv.view_cam + 16 * (int64_t)(wd.view0 + j) + 4, Ft);
             schur_pose_block(Ft, R, M, lmk, sc + row0, Y);
@@ -843,27 +847,28 @@ KBA_HD void backsub_lane(const BatchView& bv, const SolveConsts& c, int w, int g
         double a[3] = {0, 0, 0};
         // (the leading views of keyframes without a free pose block have a zero camera step: their terms of `a` are exact
         // zeros - the loop starts behind them and their planes are never loaded)
+        // The planes sit at the pair's own index (kba_layout.hpp:BatchView::obs_c): slot and planes of a view are three coalesced
+        // loads whose addresses the lane knows at its start, all one view ahead - the slot only says whether the pair exists.
         const int j0 = wd.n_view_fixed0;
-        int s_cur = j0 < n_view ? slot[(int64_t)j0 * bv.SL] : -1;
-        int s_nxt = j0 + 1 < n_view ? slot[(int64_t)(j0 + 1) * bv.SL] : -1;
-        double aun, sdn;
-        {
-            const int64_t o = s_cur >= 0 ? s_cur : 0;
-            aun = bv.obs_c[o];
-            sdn = bv.obs_c[bv.SO + o];
+        const double* au_p = bv.obs_c;
+        const double* sd_p = au_p + obs_c_stride(bv);
+        int64_t r = (int64_t)j0 * bv.SL + gl;  // the pair's index, one view ahead of the loop
+        int s_cur = -1;
+        double aun = 0.0, sdn = 0.0;
+        if (j0 < n_view) {
+            s_cur = bv.lm_slot[r];
+            aun = au_p[r];
+            sdn = sd_p[r];
         }
         for (int j = j0; j < n_view; ++j) {
             const bool have = s_cur >= 0;
             double c4[4];
             c4[0] = have ? aun : 0.0;
             c4[3] = have ? sdn : 0.0;
-            s_cur = s_nxt;
-            s_nxt = j + 2 < n_view ? slot[(int64_t)(j + 2) * bv.SL] : -1;
-            {
-                const int64_t o = s_cur >= 0 ? s_cur : 0;
-                aun = bv.obs_c[o];
-                sdn = bv.obs_c[bv.SO + o];
-            }
+            r += j + 1 < n_view ? bv.SL : 0;  // (the last view reloads itself: nobody reads it)
+            s_cur = bv.lm_slot[r];
+            aun = au_p[r];
+            sdn = sd_p[r];
             // E^T (F dc) of the pair, with F dc = c^T Rc (dR x + d_trans) = c^T (K x + k0) and E = c^T H: the view's
             // K = Rc dR, k0 = Rc d_trans (cam_solve) and H (view_consts_item) are wave-uniform, c^T is spanned by the four
             // scalars (kba_math.hpp:ft_build) - no 3 x 3 Ft / E per observation

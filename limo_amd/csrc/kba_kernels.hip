@@ -366,10 +366,11 @@ __global__ void k_view_consts(BatchView bv) {
 //     constant address space (written by k_sched_fill or k_view_consts, the launch before: scalar loads although plane stores precede them);
 //   * the observation of the pair (slot table -> index s -> u, v, d: 12 B) is fetched one view ahead, the slot two ahead;
 //   * branch-free: a landmark that does not see the view (or is out of the problem) runs the same arithmetic on a valid
-//     dummy observation, contributes zeros and stores into the dump area behind the planes;
+//     dummy observation, contributes zeros and stores +0.0 into the pair's place of the planes (kba_layout.hpp:BatchView::obs_c);
 //   * the 28 camera-side sums of the view leave each WAVE through one reduce-scatter into the wave's LDS slice (no
 //     barrier in the loop); after the last view one barrier, then lane (view, entry) adds the four slices.
-// Bytes per pair: 4 (slot) + 12 (u, v, d) read, 16 (planes au, sd) written; per landmark 32 read + 72 (V, g) + 48 (Bt) written -
+// Bytes per pair: 4 (slot) + 12 (u, v, d) read, 16 (planes au, sd) written - also for a pair the landmark does not have, in the views
+// with a free pose block (+0.0: the planes are indexed by the pair); per landmark 32 read + 72 (V, g) + 48 (Bt) written -
 // 79 B per observation under counters (round 5); the separate view-major linearise + landmark-major accumulate pair of round 1
 // moved 101 + 93.
 typedef const double __attribute__((address_space(4))) cdouble;
@@ -431,7 +432,8 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     } else {
         vc = (VT)(bv.view_lin + (int64_t)kViewLin * wd.view0);
     }
-    const int64_t dump = bv.SO - kObsBlock + threadIdx.x;
+    double* const plane = bv.obs_c + gl;
+    const int64_t plane_stride = obs_c_stride(bv);
 #pragma unroll
     for (int i = 0; i < 9; ++i) accl[i * kBlock] = 0.0;
     // the tail's per-landmark inputs wait in LDS as well (fetched up here, in front of the loop's stores: LmTailIn)
@@ -520,9 +522,12 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         {   // of the four scalars of the factored Jacobian the Schur / back-substitution kernels read au and sd (16 B per pair) and
             // rebuild xn, yn from the landmark and the view (kba_math.hpp:view_xy: the same statements as here); the residual
             // r3 has done its work inside this lane (g += E^T r, camera-side g) - nobody reads it from memory in a solve
-            const int64_t o = have ? s : dump;
-            bv.obs_c[o] = c4[0];
-            bv.obs_c[bv.SO + o] = c4[3];
+            // They go to the PAIR's place (kba_layout.hpp:BatchView::obs_c), +0.0 where the landmark has no observation in the view:
+            // every word a reader may load is written by this linearisation.  Lanes past the block's end store nothing.
+            if (in_block) {
+                plane[(int64_t)j * bv.SL] = have ? c4[0] : 0.0;
+                plane[plane_stride + (int64_t)j * bv.SL] = c4[3];  // (lin_obs_core: exactly +0.0 without the pair; au may be -0.0)
+            }
         }
         accum(vl, r3, c4);  // zeros where the pair does not exist
         static_assert(kLinPartial == 28 && kLinWaves * 64 == kBlock, "wave_reduce_scatter14 x 2");
@@ -784,8 +789,8 @@ __global__ __launch_bounds__(64 * kWideWaves) void k_schur_wide(BatchView bv, co
 //   * No padding columns: a panel read past the last column runs into the next row - finite values that only reach
 //     output entries nobody reads (masked to zero at the store).
 //   * Keyframe constants (R, Rc, q, scales, columns) sit in LDS; the landmark-side inputs of ONE tile in registers: the
-//     loads of the next tile are issued right after the fill and complete under the MFMAs of the current one; the
-//     indices (slot, state, ground-plane row) are fetched two tiles ahead.
+//     loads of the next tile are issued right after the fill and complete under the MFMAs of the current one, the
+//     indices (slot, state) with them; a ground-plane wave fetches its indices (ground-plane row too) two tiles ahead.
 // One wave per workgroup, no cross-wave synchronisation; `span` consecutive blocks of one class per wave.
 constexpr int kSpBatch = 4;  // k-steps whose panel reads are in flight together
 constexpr int kSpKf = 41;    // doubles per free keyframe in LDS: R (9) | Rc (9) | scale of its 10 slots | |q|^2 - 1 | H (9), h0 (3) of its view
@@ -817,9 +822,9 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     // ---- the head: everything a wave waits for before its first tile.  What describes the group is ONE record right behind the
     //      worklist entry (kba_layout.hpp:SchurGroup, scalar loads; with other spans than the record's - the landmark-sharded solve -
     //      the wave builds it from the window's descriptor and the block tables as the waves of rounds 3-6 did); then the index
-    //      loads of the first two tiles, the keyframe constants and the data loads of the first tile are ISSUED in this order before
-    //      anything is waited for: the constants arrive under the landmark-side loads, and the wave reaches its first fill behind
-    //      one wait.
+    //      loads, the keyframe constants and the data loads of the first tile are ISSUED in this order before anything is waited
+    //      for - no address among them is a loaded value - and the wave reaches its first fill behind one wait: worklist -> record
+    //      -> {indices, constants, data} -> fill.  (A ground-plane wave has one trip more: the row planes behind lm_gp.)
     // (Two routes to ONE description: schur_group_make writes the record at pack time and is what the other route calls on the
     // device, so the two cannot drift apart field by field; the launch-path tests run the record, the sharded tests the device route.)
     SchurGroup g;
@@ -867,11 +872,14 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     for (int i = 0; i < NT; ++i) acc[i] = (v4f64){0.0, 0.0, 0.0, 0.0};
 
     // ---- software pipeline
-    // stage 1 (two tiles ahead): landmark state, observation slot in this lane's keyframe, ground-plane row attached to it.
+    // The landmark-side inputs of a tile are addressed by the landmark, the two plane scalars of a pair by (view, landmark)
+    // (kba_layout.hpp:BatchView::obs_c): NO data load of a plain wave depends on a loaded value - the indices (state, slot) only
+    // decide, at the fill, what of the loaded data counts.  So the indices and the data of a tile are issued together, one tile
+    // ahead.  A ground-plane wave also loads the landmark's ground-plane row, whose address is a loaded value (lm_gp): its
+    // indices stay two tiles ahead, the row's planes are loaded one tile ahead by the lanes the row hangs on.
     // index_issue only ISSUES the loads (branch-free: a lane past the group's end reads the last landmark's entries, a lane without
     // a view row 0 of the slot table - a use of a loaded value inside a divergent section would wait for it at the section's end);
-    // index_kf issues the one load that depends on another (the row's keyframe); index_mask turns the raw values into what the
-    // data stage consumes, when it consumes them.
+    // index_kf issues the one load that depends on another (the row's keyframe).
     auto index_issue = [&](int l0, int& st, int& slot, int& gr) {
         const int i = l0 + li < n_lm_blk ? l0 + li : n_lm_blk - 1;
         const int gl = lm_first + i;
@@ -884,39 +892,36 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         if constexpr (GP) return bv.gp_kf[gr >= 0 ? gr : 0];
         return 0;
     };
-    auto index_mask = [&](int l0, int& st, int& slot, int& gg, int kf) {  // gg: in the raw row, out the row if it hangs on this keyframe
-        const bool in = l0 + li < n_lm_blk;
-        st = in ? st : 0;
-        slot = in && have && my_view >= 0 ? slot : -1;
-        gg = GP && in && have && st == 1 && gg >= 0 && kf - g.kf0 == my_kl ? gg : -1;
-    };
-    // stage 2 (one tile ahead): the landmark-side inputs
+    // stage 2 (one tile ahead): the landmark-side inputs.
+    // data_issue: what the RECORD alone says this lane can need (lane in range - clamped -, a free pose block, a view, a share of
+    // the rhs) - no loaded value decides a load or an address here.  gp_issue: the planes of ground-plane row gg where `on`.
     // (g3 is written by loads only: with a variable that the fill also overwrites - t = Bt g in place - the compiler copied the loaded
     // values into it right behind the loads, and that wait exposed the whole prefetch of a tile before its MFMAs)
     double c4[4], p[3], Bt[6], g3[3], gE[3], gF[kCamSlots];
-    bool live = false, seen = false, att = false;
-    auto fetch_data = [&](int l0, int st, int slot, int gg) {
-        const int gl = lm_first + l0 + li;
-        live = st == 1;
-        seen = live && slot >= 0;
-        att = GP && live && gg >= 0;
-        if (seen) {
-            c4[0] = bv.obs_c[slot];
-            c4[3] = bv.obs_c[bv.SO + slot];
+    const bool has_pair = have && my_view >= 0;  // pairs of this lane's keyframe can exist: free pose block, a view
+    const bool want_g = kq == 0 || two_tile;     // this lane supplies (its share of) the rhs column: t = Bt g
+    const double* my_au = bv.obs_c + (int64_t)(my_view >= 0 ? my_view - g.view0 : 0) * bv.SL;  // the view's row of the two planes
+    const double* my_sd = my_au + obs_c_stride(bv);
+    auto data_issue = [&](int l0) {
+        const int gl = lm_first + (l0 + li < n_lm_blk ? l0 + li : n_lm_blk - 1);
+        if (has_pair) {
+            c4[0] = my_au[gl];
+            c4[3] = my_sd[gl];
 #pragma unroll
             for (int i = 0; i < 3; ++i) p[i] = bv.lm[3 * (int64_t)gl + i];
         }
-        const bool want_t = live && (kq == 0 || two_tile);  // this lane supplies (its share of) the rhs column: t = Bt g
-        if (seen || att || want_t) {
+        if (has_pair || want_g || (GP && have)) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) Bt[i] = bv.lm_Li[i * bv.SL + gl];
         }
-        if (want_t) {
+        if (want_g) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) g3[i] = bv.lm_g[i * bv.SL + gl];  // (turned into t = Bt g at the fill)
         }
+    };
+    auto gp_issue = [&](bool on, int gg) {
         if constexpr (GP) {
-            if (att) {
+            if (on) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) gE[i] = bv.gp_E[i * bv.SG + gg];
 #pragma unroll
@@ -924,11 +929,19 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
             }
         }
     };
-    int n_st, n_slot, n_gg, n_kf;  // raw index values of the tile after the next
+    // What of a tile's data counts, formed where the fill consumes it: st / slot / gg / kf = the tile's raw index values
+    bool live = false, seen = false, att = false;
+    auto predicates = [&](int l0, int st, int slot, int gg, int kf) {
+        const bool in = l0 + li < n_lm_blk;
+        live = in && st == 1;
+        seen = live && has_pair && slot >= 0;
+        att = GP && live && have && gg >= 0 && kf - g.kf0 == my_kl;  // the landmark's row hangs on this lane's keyframe
+    };
+    int c_st, c_slot, c_gg, c_kf = 0;                 // raw index values of the tile whose data is in flight
+    int n_st = 0, n_slot = -1, n_gg = -1, n_kf = 0;   // ground-plane waves: of the tile after it
     {
-        int st0, sl0, gg0;
-        index_issue(0, st0, sl0, gg0);
-        index_issue(kSchurLm, n_st, n_slot, n_gg);
+        index_issue(0, c_st, c_slot, c_gg);
+        if constexpr (GP) index_issue(kSchurLm, n_st, n_slot, n_gg);
         // keyframe constants: the 16 lanes of a keyframe copy its view's record (kba_items.hpp:view_consts_item - H, h0, Rc at
         // [0..20], R, |q|^2 - 1 at [37..46]) with three coalesced loads, ten of them the scales and the columns of its slots.
         // A free keyframe without a view has no observation (no `seen` lane): its R, Rc, H are never read and stay zero.
@@ -938,10 +951,14 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         const int my_slot = slot0 + (li < kCamSlots ? li : 0);
         const double sc = bv.scale_c[my_slot];
         const int ci = bv.cslot[my_slot];
-        const int kf_0 = index_kf(gg0);
-        n_kf = index_kf(n_gg);
-        index_mask(0, st0, sl0, gg0, kf_0);
-        fetch_data(0, st0, sl0, gg0);
+        data_issue(0);
+        if constexpr (GP) {
+            // the one dependent trip of a ground-plane wave: the row's keyframe and the row's planes, both behind lm_gp and side by
+            // side - every lane with a free pose block loads the planes of its landmark's row, `att` picks the keyframe's at the fill
+            c_kf = index_kf(c_gg);
+            n_kf = index_kf(n_gg);
+            gp_issue(have && li < n_lm_blk && c_gg >= 0, c_gg);
+        }
         if (!active) return;
         if (kq < n_fk) {
             double* mine_w = kc + kq * kSpKf;
@@ -963,6 +980,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     const int mq = li < 8 ? li : li + 8;            // two-tile path: column of lane li in the second operand {0..7, 16..23}
     for (int l0 = 0; l0 < n_lm_blk; l0 += kSchurLm) {
         // ---- fill: this lane's 3 x NS block of Y' (zeros where the landmark has no row with the keyframe)
+        predicates(l0, c_st, c_slot, c_gg, c_kf);
         double t3[3] = {0.0, 0.0, 0.0};
         if (live && (kq == 0 || two_tile)) lm_t_of(Bt, g3, t3);
         if (kq == 0 && !two_tile) {
@@ -1015,13 +1033,20 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
                 }
             }
         }
-        // ---- loads of the next tile (they complete under the MFMAs below), indices of the one after
-        {
-            int st = n_st, slot = n_slot, gg = n_gg;
-            index_mask(l0 + kSchurLm, st, slot, gg, n_kf);
-            index_issue(l0 + 2 * kSchurLm, n_st, n_slot, n_gg);
-            n_kf = index_kf(n_gg);
-            fetch_data(l0 + kSchurLm, st, slot, gg);
+        // ---- loads of the next tile (they complete under the MFMAs below): its indices with them, or - ground-plane waves, whose
+        //      row planes sit behind the index - the indices of the tile after it and the planes of the row that hangs on this lane
+        if (l0 + kSchurLm < n_lm_blk) {  // (wave-uniform)
+            const int l1 = l0 + kSchurLm;
+            if constexpr (GP) {
+                c_st = n_st, c_slot = n_slot, c_gg = n_gg, c_kf = n_kf;
+                index_issue(l1 + kSchurLm, n_st, n_slot, n_gg);
+                n_kf = index_kf(n_gg);
+                data_issue(l1);
+                gp_issue(have && l1 + li < n_lm_blk && c_st == 1 && c_gg >= 0 && c_kf - g.kf0 == my_kl, c_gg);
+            } else {
+                index_issue(l1, c_st, c_slot, c_gg);
+                data_issue(l1);
+            }
         }
         schur_wave_sync<COOP>();
         // ---- Z^T Z over the 48 rows (rows of absent landmarks are zero): 12 k-steps, upper tiles

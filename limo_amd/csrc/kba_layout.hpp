@@ -274,7 +274,12 @@ struct BatchView {
     //     obs_r  = [2][SO] r_u, r_v             | [1][SD] r_d
     //     obs_Jp = [12][SO] rows u, v (2 x 6)   | [6][SD] row d
     //     obs_Jl = [6][SO] rows u, v (2 x 3)    | [3][SD] row d
-    double *obs_r, *obs_c;            // obs_c = [2][SO] (au, sd), solver batches; obs_r exists in evaluate-only batches only (the solve keeps residuals in registers)
+    // Solver batches: obs_c holds the two plane scalars (au, sd) of a pair, indexed by the PAIR, not by its observation: plane k of
+    // (view j of its window, packed landmark gl) sits at  k * obs_c_stride(bv) + j * SL + gl  - the index of the pair's entry in
+    // lm_slot, [2][Vmax][SL].  A reader knows the address from the window's record and the lane alone (no load behind the slot);
+    // k_lin_lm writes every pair of the views j >= n_view_fixed0 of its landmarks on every linearisation, +0.0 where the landmark
+    // has no observation in the view; the rows of the leading views without a free pose block are never written and never read.
+    double *obs_r, *obs_c;            // obs_r exists in evaluate-only batches only (the solve keeps residuals in registers)
     double *obs_Jp, *obs_Jl;          // evaluate-only batches
     const EvalChunk* echunk;          // [n_echunk] evaluate-only batches: the wave-sized work items of k_evaluate
     int64_t SD;                       // stride of the compact depth-row planes
@@ -308,6 +313,12 @@ struct BatchView {
     int32_t sched_off[SL_COUNT];  // offset of list k's count word inside sched_lists
     int32_t* sched_done_host;   // pinned ring (4 words): windows finished as of round r at [r & 3]
 };
+
+// doubles between the two planes of BatchView::obs_c (solver batches): the rows of lm_slot
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int64_t obs_c_stride(const BatchView& bv) { return (int64_t)(bv.Vmax > 0 ? bv.Vmax : 1) * bv.SL; }
 
 // Sizes and offsets of a landmark-sharded solve's exchange (kba_buffers.hpp:exchange_layout builds it and explains it).
 struct ExchangeLayout {
