@@ -7,7 +7,9 @@
 //
 //   limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--poses out.txt] [--gt-poses gt.txt]
 //               [--dump-velodyne DIR] [--velodyne DIR] [--no-depth] [--depth-ahead thread|stream|none] [--quiet]
-//               [--depth-params FILE]
+//               [--depth-params FILE] [--progress]
+// --progress prints Ceres' per-iteration table for every adjustPoseOnly and solve to stdout, as the reference's node does
+// (BundleAdjusterKeyframes::minimizer_progress_to_stdout_); the pose rows do not change.
 // --depth-params reads the depth estimator's settings from a mono_lidar_fusion_parameters.yaml (the file the reference
 // application loads; limo_amd/kba/depth_params_yaml.hpp) instead of using the built-in defaults, which are that file's values.
 // --dump-velodyne writes every synthetic sweep as a KITTI velodyne scan (DIR/NNNNNN.bin); --velodyne replays scans from
@@ -39,7 +41,7 @@ int main(int argc, char** argv) {
     int n_frames = 200, n_feat = 1500, n_az = 2000, window = 5, misannounce_every = 0;
     uint64_t seed = 7;
     std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path;
-    bool use_depth = true, quiet = false, five_point_prior = false;
+    bool use_depth = true, quiet = false, five_point_prior = false, progress = false;
     StreamParams::DepthAhead depth_ahead = StreamParams::DepthAhead::Thread;
     double min_flow = -1., time_between_keyframes = -1.;
     for (int i = 1; i < argc; ++i) {
@@ -68,9 +70,10 @@ int main(int argc, char** argv) {
             depth_ahead = m == "thread" ? StreamParams::DepthAhead::Thread : m == "stream" ? StreamParams::DepthAhead::Stream : StreamParams::DepthAhead::None;
         }
         else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
+        else if (!std::strcmp(argv[i], "--progress")) progress = true;
         else if (!std::strcmp(argv[i], "--five-point-prior")) five_point_prior = true;  // the node's prior without tf (mono_lidar.cpp:157-186)
         else {
-            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--quiet]\n");
+            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--quiet] [--progress]\n");
             return 2;
         }
     }
@@ -90,6 +93,7 @@ int main(int argc, char** argv) {
     sp.image_height = (int)world.H;
     sp.height_over_ground = synth_world::World::kHeightOverGround;
     StreamDriver driver(sp, cam, world.cam_lidar);
+    driver.adjuster().minimizer_progress_to_stdout_ = progress;
     if (!depth_params_path.empty()) {
         std::string err;
         if (!depth_params_yaml::load(depth_params_path, &driver.depthParams(), &err)) {

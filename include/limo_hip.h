@@ -143,7 +143,10 @@ typedef struct limo_ba_options {
 typedef struct limo_ba_report {
     int32_t termination;         /* enum limo_termination of the FINAL solve                    */
     int32_t num_solves;          /* ceres-style solves executed (trim rounds [+retries] + final) */
-    int32_t iterations_total;    /* LM iterations over all solves (iteration 0 not counted)      */
+    int32_t iterations_total;    /* LM iterations over all solves (iteration 0 not counted).  An iteration that ENDS its solve
+                                    inside the step decision - parameter tolerance, function tolerance, the last of
+                                    max_num_consecutive_invalid_steps invalid steps - IS counted here; Ceres' own count and the
+                                    iteration log (limo_ba_iteration below) have no entry for it: at most one per solve */
     int32_t iterations_final;    /* LM iterations of the final solve                             */
     int32_t successful_steps;    /* accepted steps over all solves                               */
     int32_t n_depth_blocks;      /* residual blocks built (before trimming)                      */
@@ -265,6 +268,52 @@ int64_t limo_ctx_coop_fallbacks(const limo_ctx* ctx);
  *   info[7]  the linearisation that ran: 1 k_lin_lm<true> (LDS; also what the one-launch kernels contain), 0 k_lin_lm<false>
  *            (scalar loads: KBA_LIN_VLDS=0, windows with many views) */
 int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]);
+
+/*
+ * Per-iteration solver log: what the reference prints for every solve (minimizer_progress_to_stdout = true,
+ * robust_optimization/robust_solving.hpp:105) - Ceres' iteration table, as numbers.  One entry per iteration of every
+ * Ceres-style solve of the schedule, recorded on the device by the lane that takes the LM decisions; the same bytes on every
+ * launch path (limo_ctx_last_solve_info).  Off by default; switching it on changes no result.
+ * An entry exists exactly when Ceres' TrustRegionMinimizer appends an IterationSummary:
+ *   - iteration 0 after the first linearisation of a solve: step fields zero, both flags 1, radius = initial_trust_region_radius.
+ *     A solve whose first evaluation fails, and a window without a variable parameter block, have no entries;
+ *   - an invalid step: cost = the current cost, gradient_max_norm = the previous entry's, step fields zero, the radius after the
+ *     division;
+ *   - a rejected step: cost = the candidate's cost (+ fixed cost), gradient_max_norm = the previous entry's, the radius after the
+ *     division;
+ *   - an accepted step: cost and gradient_max_norm of the relinearisation that follows, the radius after the update; no entry
+ *     when that relinearisation fails;
+ *   - NO entry for an iteration that ends the solve inside the step decision (parameter tolerance, function tolerance, the last
+ *     of max_num_consecutive_invalid_steps invalid steps).  limo_ba_report::iterations_total counts such an iteration, the log -
+ *     like Ceres' own iteration count - does not: per solve, entries with iteration >= 1 number iterations or iterations - 1;
+ *   - a solve ended by the wall-clock cap ends its log where it stood.
+ */
+typedef struct limo_ba_iteration { /* 64 bytes; ceres::IterationSummary restated */
+    int32_t solve;      /* index of the Ceres-style solve inside this call, 0-based, in execution order; a discarded first
+                           attempt (robust_solving.cpp:172-181) counts */
+    int32_t solve_kind; /* 0 trimming solve, 1 its retry with 3x the iterations, 2 final solve */
+    int32_t iteration;  /* 0 = IterationZero */
+    uint8_t step_is_valid, step_is_successful, pad[2];
+    double cost;        /* incl. the fixed cost, as Ceres reports it */
+    double cost_change, gradient_max_norm, step_norm, relative_decrease, trust_region_radius;
+} limo_ba_iteration;
+/* The switch belongs to the context and is read by limo_ba_batch_solve: when it is on, the solve allocates the log of its batch
+ * from the context's pool, with the exact bound of the schedule as the capacity per window:
+ *   num_trim_rounds * ((trim_solver_iterations + 1) + (3 * trim_solver_iterations + 1)) + (max_num_iterations + 1)  entries
+ * - 111 entries with the default options, about 7 KB per window: 116 MB for a batch of 16384 windows.  Every limo_ba_batch_solve
+ * starts the log of its windows at zero entries, limo_ba_batch_reset clears it, and a one-launch solve that gave up at a barrier
+ * and was redone (limo_ctx_coop_fallbacks) leaves nothing of the abandoned launch in it. */
+int limo_ctx_set_iteration_log(limo_ctx* ctx, int32_t on);
+/* The log of window `window` of a resident batch, read on demand: *n = the entries the window has, at most `cap` of them are
+ * written to `out` (out == NULL with cap == 0 asks for the count).  With the switch off at the batch's last solve: LIMO_OK, *n = 0. */
+int limo_ba_batch_iteration_log(limo_ba_batch* batch, int32_t window, int32_t cap, limo_ba_iteration* out, int32_t* n);
+/* The same for the calls that make and destroy their own batch - limo_ba_solve, limo_ba_adjust_pose_only,
+ * limo_ba_adjust_pose_only_batch, limo_ba_solve_fixed_landmarks: they copy their windows' logs into a host buffer of the context
+ * before they destroy the batch, and this reads window `window` of the last such call.  Switch off: LIMO_OK, *n = 0.
+ * Not offered: limo_ba_solve_sharded records no log - after it *n = 0 for every window.
+ * Both readers return LIMO_ERR_INVALID (limo_last_error names the argument) for a NULL ctx / batch / n, a window out of range,
+ * cap < 0, or out == NULL with cap > 0. */
+int limo_ctx_last_iteration_log(limo_ctx* ctx, int32_t window, int32_t cap, limo_ba_iteration* out, int32_t* n);
 
 /*
  * Evaluate the reprojection / depth residual blocks of a window at its current parameters

@@ -113,6 +113,38 @@ class BaRow(C.Structure):  # struct limo_ba_row
     ]
 
 
+class BaIteration(C.Structure):  # struct limo_ba_iteration
+    _fields_ = [
+        ("solve", C.c_int32),
+        ("solve_kind", C.c_int32),
+        ("iteration", C.c_int32),
+        ("step_is_valid", C.c_uint8),
+        ("step_is_successful", C.c_uint8),
+        ("pad", C.c_uint8 * 2),
+        ("cost", C.c_double),
+        ("cost_change", C.c_double),
+        ("gradient_max_norm", C.c_double),
+        ("step_norm", C.c_double),
+        ("relative_decrease", C.c_double),
+        ("trust_region_radius", C.c_double),
+    ]
+
+
+def iteration_dtype():
+    """struct limo_ba_iteration as a numpy structured dtype (64 bytes)."""
+    import numpy as np
+
+    return np.dtype(
+        {
+            "names": ["solve", "solve_kind", "iteration", "step_is_valid", "step_is_successful", "pad", "cost", "cost_change", "gradient_max_norm",
+                      "step_norm", "relative_decrease", "trust_region_radius"],
+            "formats": ["<i4", "<i4", "<i4", "u1", "u1", ("u1", 2), "<f8", "<f8", "<f8", "<f8", "<f8", "<f8"],
+            "offsets": [0, 4, 8, 12, 13, 14, 16, 24, 32, 40, 48, 56],
+            "itemsize": 64,
+        }
+    )
+
+
 ROW_GROUND_HEIGHT, ROW_SCALE, ROW_NORMAL_DIFF, ROW_DIST_DIFF, ROW_PLANE_MOTION, ROW_GLOBAL_NORMAL, ROW_SPEED = range(7)
 
 
@@ -258,6 +290,9 @@ ABI_SYMBOLS = [
     "limo_ctx_exchange_stats",
     "limo_ctx_coop_fallbacks",
     "limo_ctx_last_solve_info",
+    "limo_ctx_set_iteration_log",
+    "limo_ba_batch_iteration_log",
+    "limo_ctx_last_iteration_log",
     "limo_ba_evaluate",
     "limo_ba_evaluate_batch_time",
     "limo_ba_evaluate_rows",
@@ -387,6 +422,10 @@ def load():
     lib.limo_ctx_coop_fallbacks.restype = C.c_int64
     if hasattr(lib, "limo_ctx_last_solve_info"):  # (added without an ABI bump, as the two above)
         lib.limo_ctx_last_solve_info.argtypes = [vp, c_int64_p]
+    if hasattr(lib, "limo_ctx_set_iteration_log"):  # (added without an ABI bump, as the ones above)
+        lib.limo_ctx_set_iteration_log.argtypes = [vp, C.c_int32]
+        lib.limo_ba_batch_iteration_log.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(BaIteration), c_int32_p]
+        lib.limo_ctx_last_iteration_log.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(BaIteration), c_int32_p]
     lib.limo_depth_set_timing.argtypes = [vp, C.c_int32]
     lib.limo_depth_last_kernel_ms.argtypes = [vp, c_double_p]
     lib.limo_depth_last_ground_plane.argtypes = [vp, C.c_int32, c_double_p, c_int32_p]

@@ -96,6 +96,16 @@ class Context:
         keys = ("recovered", "coop_G", "groups", "slots", "rounds", "pair_launches", "lin_variant")
         return dict({"path": self.SOLVE_PATHS.get(int(v[0]), "NONE")}, **{k: int(v[1 + i]) for i, k in enumerate(keys)})
 
+    def set_iteration_log(self, on):
+        """limo_ctx_set_iteration_log: the solves on this context record Ceres' per-iteration table (off by default)."""
+        _check(self.lib.limo_ctx_set_iteration_log(self.ptr, int(bool(on))), self.ptr, "limo_ctx_set_iteration_log")
+
+    def last_iteration_log(self, window=0):
+        """limo_ctx_last_iteration_log: the entries of window `window` of the last solve / adjust_pose_only[_batch] call on this
+        context, as a numpy array of _ffi.iteration_dtype() (empty with the switch off)."""
+        return _read_iteration_log(lambda cap, out, n: self.lib.limo_ctx_last_iteration_log(self.ptr, int(window), cap, out, n), self.ptr,
+                                   "limo_ctx_last_iteration_log")
+
     def comm_init(self, unique_id, rank, world):
         _check(self.lib.limo_ctx_comm_init(self.ptr, unique_id, int(rank), int(world)), self.ptr, "limo_ctx_comm_init")
 
@@ -174,6 +184,17 @@ class Context:
         return _ffi.rows_as_dicts(rows, n.value)
 
 
+def _read_iteration_log(call, ctx_ptr, what):
+    """Both readers of the iteration log: ask for the count, then for the entries."""
+    n = C.c_int32(0)
+    _check(call(0, None, C.byref(n)), ctx_ptr, what)
+    out = np.zeros(n.value, _ffi.iteration_dtype())
+    if n.value:
+        _check(call(n.value, out.ctypes.data_as(C.POINTER(_ffi.BaIteration)), C.byref(n)), ctx_ptr, what)
+        assert n.value == out.size
+    return out
+
+
 def fixed_flags(lm_fixed, n_lm):
     """One uint8 flag per landmark of a window (non-zero: constant), contiguous, at least one byte long."""
     flags = np.ascontiguousarray(lm_fixed).astype(bool).astype(np.uint8).ravel()
@@ -247,6 +268,12 @@ class Batch:
         flags = np.zeros(max(1, self.windows[w].n_lm), np.uint8)
         _check(self.lib.limo_ba_batch_trimmed(self.ptr, int(w), flags.ctypes.data_as(_ffi.c_uint8_p)), self.ctx.ptr, "limo_ba_batch_trimmed")
         return np.nonzero(flags[: self.windows[w].n_lm])[0].astype(np.int32)
+
+    def iteration_log(self, w=0):
+        """limo_ba_batch_iteration_log: the entries window w recorded in the last solve of this batch, as a numpy array of
+        _ffi.iteration_dtype() (empty when the context's switch was off)."""
+        return _read_iteration_log(lambda cap, out, n: self.lib.limo_ba_batch_iteration_log(self.ptr, int(w), cap, out, n), self.ctx.ptr,
+                                   "limo_ba_batch_iteration_log")
 
     def kernel_stats(self, reset=False):
         ms = C.c_double()

@@ -193,6 +193,19 @@ __global__ void k_expire(BatchView bv) {
     if (bv.st[w].active) lm_terminate(bv.st[w], LIMO_NO_CONVERGENCE);
 }
 
+// Iteration log (kba_lm.hpp:lm_log_push): at the start of a limo_ba_batch_solve that records one, window w gets its `cap` entries
+// at base + w * cap and starts at zero entries; base == null switches the recording of the batch off again.
+__global__ void k_log_bind(BatchView bv, limo_ba_iteration* base, int cap) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= bv.n_win) return;
+    WinState& s = bv.st[w];
+    s.log = base ? base + (int64_t)w * cap : nullptr;
+    s.log_cap = base ? cap : 0;
+    s.log_n = 0;
+    s.log_solve = 0;
+    s.log_si = 0;
+}
+
 // ------------------------------------------------------------------------------------------ streaming solve: scheduler
 // At the start of every round (<= 4096 windows in flight):
 //   1. a window whose solve ended moves on in its schedule (kba_lm.hpp:sched_advance); finished windows leave their

@@ -131,14 +131,22 @@ struct WinState {
     int32_t acc_solves, acc_iters, acc_success, last_iters;
     int32_t n_trimmed, acc_lin;
     int32_t phase, trim_round;  // streaming solve (kba_lm.hpp:sched_advance): where the window is in the solveTrimmed schedule
-    int32_t redamp, pad_i;      // the last step was rejected: the landmark blocks must be damped again with the new radius
+    int32_t redamp;             // the last step was rejected: the landmark blocks must be damped again with the new radius
                                 // (after a linearisation the landmark pass has already done it)
+    int32_t log_kind;           // iteration log: limo_ba_iteration::solve_kind of the solve in progress
     double radius, decrease_factor;
     double x_cost, x_norm, fixed_cost;
     double solve_initial_cost, solve_final_cost;
     double first_initial_cost;
     double rho_pending, xnorm_pending, cost_pending;
     double gmax;
+    // ---- iteration log (limo_hip.h:limo_ba_iteration; kba_lm.hpp:lm_log_push).  log == null: off, nothing below is touched.
+    double step_pending, dcost_pending;  // step norm and cost change of an accepted step: its entry is completed by lm_decide_lin
+    limo_ba_iteration* log;     // the window's entries (log_cap of them)
+    int32_t log_n, log_cap;     // entries written; never more than log_cap
+    int32_t log_solve;          // solves of this call the window has started (the entry's `solve` is this minus one)
+    int32_t log_si;             // lock-step and one-launch schedules: calls of lm_solve_init so far = the next solve number of
+                                // kba_lm.hpp:sched_solve (the streaming schedule reads the kind from `phase`)
 };
 
 // Reduction inputs the LM decisions read (one entry per window).

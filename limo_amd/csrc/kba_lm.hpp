@@ -15,6 +15,28 @@
 
 namespace kba {
 
+// Iteration log (limo_hip.h:limo_ba_iteration): one entry where Ceres' FinalizeIterationAndCheckIfMinimizerCanContinue appends an
+// IterationSummary, written by the lane that takes the decision - 64 bytes of plain stores.  s.log == null: off.
+KBA_HD void lm_log_push(WinState& s, bool valid, bool successful, double cost, double cost_change, double gmax, double step_norm, double rho) {
+    limo_ba_iteration* const log = s.log;
+    if (!log || s.log_n >= s.log_cap) return;
+    limo_ba_iteration e;
+    e.solve = s.log_solve - 1;
+    e.solve_kind = s.log_kind;
+    e.iteration = s.iter;
+    e.step_is_valid = valid ? 1 : 0;
+    e.step_is_successful = successful ? 1 : 0;
+    e.pad[0] = e.pad[1] = 0;
+    e.cost = cost;
+    e.cost_change = cost_change;
+    e.gradient_max_norm = gmax;
+    e.step_norm = step_norm;
+    e.relative_decrease = rho;
+    e.trust_region_radius = s.radius;
+    log[s.log_n] = e;
+    s.log_n += 1;
+}
+
 // Start a ceres-style solve for window w (if selected by `selected`).
 KBA_HD void lm_solve_init(WinState& s, bool selected, int max_iter, const SolveConsts& c) {
     s.in_phase = selected ? 1 : 0;
@@ -33,6 +55,21 @@ KBA_HD void lm_solve_init(WinState& s, bool selected, int max_iter, const SolveC
     s.radius = c.initial_radius;
     s.decrease_factor = 2.0;
     if (selected) s.acc_solves += 1;
+    if (s.log) {
+        // which solve of the schedule this is: the streaming schedule has set the window's phase (sched_advance, sched_after_trim);
+        // the lock-step and one-launch schedules call this for EVERY window with the solves of sched_solve in order
+        int kind;
+        if (s.phase == PH_TRIM_SOLVE || s.phase == PH_RETRY || s.phase == PH_FINAL) {
+            kind = s.phase == PH_TRIM_SOLVE ? 0 : s.phase == PH_RETRY ? 1 : 2;
+        } else {
+            kind = s.log_si == 2 * c.num_trim_rounds ? 2 : (s.log_si & 1);
+            s.log_si += 1;
+        }
+        if (selected) {
+            s.log_kind = kind;
+            s.log_solve += 1;
+        }
+    }
 }
 
 KBA_HD void lm_terminate(WinState& s, int term) {
@@ -165,6 +202,10 @@ KBA_HD void lm_decide_lin(WinState& s, const WinRed& r, double fixed_cost, const
         s.x_norm = s.xnorm_pending;  // (radius and decrease factor of the successful step: set in lm_decide_step already)
         s.n_success += 1;
     }
+    if (s.n_success == 1)  // IterationZero
+        lm_log_push(s, true, true, s.x_cost + s.fixed_cost, 0.0, s.gmax, 0.0, 0.0);
+    else  // the accepted step of lm_decide_step, completed by its relinearisation
+        lm_log_push(s, true, true, s.x_cost + s.fixed_cost, s.dcost_pending, s.gmax, s.step_pending, s.rho_pending);
     if (s.iter >= s.max_iter) {
         lm_terminate(s, LIMO_NO_CONVERGENCE);
     } else if (s.gmax <= c.gradient_tolerance) {
@@ -189,6 +230,7 @@ KBA_HD void lm_decide_step(WinState& s, const WinRed& r, const SolveConsts& c) {
         s.radius = s.radius / s.decrease_factor;  // StepIsInvalid
         s.decrease_factor *= 2.0;
         s.redamp = 1;
+        lm_log_push(s, false, false, s.x_cost + s.fixed_cost, 0.0, s.gmax, 0.0, 0.0);
         lm_finalize_unsuccessful(s, c);
         return;
     }
@@ -220,10 +262,13 @@ KBA_HD void lm_decide_step(WinState& s, const WinRed& r, const SolveConsts& c) {
         s.rho_pending = rho;
         s.xnorm_pending = sqrt(r.cand2);
         s.cost_pending = cand_cost;
+        s.step_pending = step_norm;
+        s.dcost_pending = cost_change;
     } else {  // HandleUnsuccessfulStep
         s.radius = s.radius / s.decrease_factor;
         s.decrease_factor *= 2.0;
         s.redamp = 1;
+        lm_log_push(s, true, false, cand_cost + s.fixed_cost, cost_change, s.gmax, step_norm, rho);
         lm_finalize_unsuccessful(s, c);
     }
 }

@@ -55,6 +55,12 @@ struct limo_ctx {
     int coop_strikes = 0;                   // ... in a row: after three the context stops taking the one-launch path (something shares the GPU)
     int coop_benched = 0;                   // solves kept off it since; the kCoopRetryAfter-th tries again (kba_batch_plan.hpp:choose_solve_path)
     long long last_solve_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // limo_ctx_last_solve_info: which path the last limo_ba_batch_solve took
+    // iteration log (limo_ctx_set_iteration_log): the switch limo_ba_batch_solve reads, and the logs of the windows of the last call
+    // that made and destroyed its own batch (limo_ctx_last_iteration_log): window w has last_log_n[w] entries from last_log_off[w]
+    bool iteration_log = false;
+    std::vector<limo_ba_iteration> last_log;
+    std::vector<int32_t> last_log_n;
+    std::vector<size_t> last_log_off;
     // Device blocks released by finished batches, kept for the next one (size class = power of two): a single-window
     // call (limo_ba_solve, limo_ba_adjust_pose_only) would otherwise spend more time in hipMalloc / hipFree than in
     // its kernels.  At most kPoolPerClass blocks per class are kept; everything is freed with the context.

@@ -359,6 +359,75 @@ struct limo_ba_batch : Executor {
         return LIMO_OK;
     }
 
+    // ---- iteration log (limo_hip.h:limo_ba_iteration; kba_lm.hpp:lm_log_push).  limo_ba_batch_solve binds it when the context's
+    // switch is on: every window gets the exact bound of the schedule as its capacity, the reset image carries the pointers (so
+    // limo_ba_batch_reset and a recovered barrier timeout start the log again at zero entries), k_log_bind puts them into the live state.
+    limo_ba_iteration* d_log = nullptr;
+    int log_cap = 0;    // entries per window of the binding in force; 0: no log
+    int log_alloc = 0;  // entries per window d_log has room for
+    static int log_bound(const limo_ba_options& o) {
+        const int64_t t = std::max(0, o.trim_solver_iterations), r = std::max(0, o.num_trim_rounds), m = std::max(0, o.max_num_iterations);
+        return (int)std::min<int64_t>(r * ((t + 1) + (3 * t + 1)) + (m + 1), 1 << 24);
+    }
+    int bind_log(bool on) {
+        const int cap = on ? log_bound(opts) : 0;
+        if (!on && !log_cap) return LIMO_OK;  // (never bound, or unbound already: the state holds no pointer)
+        if (cap > log_alloc) {
+            if (dmalloc((void**)&d_log, sizeof(limo_ba_iteration) * (size_t)cap * (size_t)std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+            log_alloc = cap;
+        }
+        if (cap != log_cap) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier reset may still read the image)
+            for (int w = 0; w < P.n_win; ++w) {
+                st0[w].log = on ? d_log + (size_t)w * cap : nullptr;
+                st0[w].log_cap = cap;
+            }
+            log_cap = cap;
+        }
+        hipLaunchKernelGGL(k_log_bind, dim3(cdiv(P.n_win, 256)), dim3(256), 0, ctx->stream, bv, on ? d_log : (limo_ba_iteration*)nullptr, cap);
+        HIP_TRY(ctx, hipGetLastError());
+        return LIMO_OK;
+    }
+    // entries of window w -> host: *n = what the window has, at most `cap` written
+    int read_log(int w, int cap, limo_ba_iteration* out, int32_t* n) {
+        *n = 0;
+        if (!log_cap) return LIMO_OK;
+        WinState s;
+        HIP_TRY(ctx, hipMemcpyAsync(&s, bv.st + w, sizeof(WinState), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const int have = std::max(0, std::min(s.log_n, log_cap)), m = std::min(have, cap);
+        *n = have;
+        if (m > 0) {
+            HIP_TRY(ctx, hipMemcpyAsync(out, d_log + (size_t)w * log_cap, sizeof(limo_ba_iteration) * m, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return LIMO_OK;
+    }
+    // every window's entries into the context's buffer (limo_ctx_last_iteration_log), for the calls that destroy their batch
+    int export_log() {
+        ctx->last_log.clear();
+        ctx->last_log_n.clear();
+        ctx->last_log_off.clear();
+        if (!log_cap) return LIMO_OK;
+        std::vector<WinState> sv(P.n_win);
+        HIP_TRY(ctx, hipMemcpyAsync(sv.data(), bv.st, sizeof(WinState) * sv.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        size_t total = 0;
+        for (int w = 0; w < P.n_win; ++w) {
+            const int have = std::max(0, std::min(sv[w].log_n, log_cap));
+            ctx->last_log_n.push_back(have);
+            ctx->last_log_off.push_back(total);
+            total += (size_t)have;
+        }
+        ctx->last_log.resize(total);
+        for (int w = 0; w < P.n_win; ++w)
+            if (ctx->last_log_n[w])
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->last_log.data() + ctx->last_log_off[w], d_log + (size_t)w * log_cap,
+                                            sizeof(limo_ba_iteration) * ctx->last_log_n[w], hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return LIMO_OK;
+    }
+
     void note(hipError_t e, const char* what) {
         if (e != hipSuccess && rc == LIMO_OK) {
             rc = LIMO_ERR_RUNTIME;
@@ -1237,6 +1306,8 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
         b->c = b->consts_for(*opts);
     }
     b->rc = LIMO_OK;
+    // iteration log: every solve starts its windows' logs at zero entries (not offered for a landmark-sharded batch)
+    if (b->bind_log(ctx->iteration_log && b->shard_P == 1) != LIMO_OK) return LIMO_ERR_RUNTIME;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(ctx, hipEventRecord(b->ev_total_a, ctx->stream));
     // Which path (kba_batch_plan.hpp:choose_solve_path; the KBA_* switches are read per call: the tests switch paths).  All paths
@@ -1549,6 +1620,9 @@ int limo_ba_solve_sharded(limo_ctx* ctx, limo_ba_window* window, const limo_ba_o
     PackOptions po;
     po.shards = n_shards;
     limo_ba_batch* b = nullptr;
+    ctx->last_log.clear();  // (no iteration log on this path: limo_ctx_last_iteration_log reports zero entries after it)
+    ctx->last_log_n.clear();
+    ctx->last_log_off.clear();
     int rc = batch_create_impl(ctx, 1, window, opts, po, &b, ranks);
     if (rc != LIMO_OK) return rc;
     rc = limo_ba_batch_solve(b, opts);
@@ -1576,6 +1650,10 @@ static int solve_n(limo_ctx* ctx, int32_t n, limo_ba_window* windows, const limo
     rc = limo_ba_batch_solve(b, nullptr);
     const auto t1 = Clock::now();
     if (rc == LIMO_OK) rc = limo_ba_batch_download(b, windows, reports);
+    {   // the windows' iteration logs outlive the batch in the context's buffer (empty with the switch off)
+        const int lrc = b->export_log();
+        if (rc == LIMO_OK) rc = lrc;
+    }
     const auto t2 = Clock::now();
     if (reports)
         for (int w = 0; w < n; ++w) reports[w].time_sec = std::chrono::duration<double>(t2 - t0).count();
@@ -1599,6 +1677,48 @@ int limo_ctx_exchange_stats(limo_ctx* ctx, int64_t* stats3) {
 int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]) {
     if (!ctx || !info) return LIMO_ERR_INVALID;
     for (int i = 0; i < 8; ++i) info[i] = ctx->last_solve_info[i];
+    return LIMO_OK;
+}
+
+int limo_ctx_set_iteration_log(limo_ctx* ctx, int32_t on) {
+    if (!ctx) return LIMO_ERR_INVALID;
+    ctx->iteration_log = on != 0;
+    return LIMO_OK;
+}
+
+// the argument checks the two readers share; null: the arguments are fine
+static const char* iteration_log_args(int32_t window, int32_t n_win, int32_t cap, const limo_ba_iteration* out, const int32_t* n) {
+    if (!n) return "n is NULL";
+    if (cap < 0) return "cap < 0";
+    if (cap > 0 && !out) return "out is NULL with cap > 0";
+    if (window < 0 || (n_win >= 0 && window >= n_win)) return "window out of range";
+    return nullptr;
+}
+
+int limo_ba_batch_iteration_log(limo_ba_batch* b, int32_t window, int32_t cap, limo_ba_iteration* out, int32_t* n) {
+    if (!b) return LIMO_ERR_INVALID;
+    limo_ctx* ctx = b->ctx;
+    if (const char* bad = iteration_log_args(window, b->P.n_win, cap, out, n)) {
+        ctx->err = std::string("limo_ba_batch_iteration_log: ") + bad;
+        return LIMO_ERR_INVALID;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return LIMO_ERR_NO_DEVICE;
+    return b->read_log(window, cap, out, n);
+}
+
+int limo_ctx_last_iteration_log(limo_ctx* ctx, int32_t window, int32_t cap, limo_ba_iteration* out, int32_t* n) {
+    if (!ctx) return LIMO_ERR_INVALID;
+    // (no log held - switch off, or limo_ba_solve_sharded: zero entries for any window)
+    const int32_t n_win = ctx->last_log_n.empty() ? -1 : (int32_t)ctx->last_log_n.size();
+    if (const char* bad = iteration_log_args(window, n_win, cap, out, n)) {
+        ctx->err = std::string("limo_ctx_last_iteration_log: ") + bad;
+        return LIMO_ERR_INVALID;
+    }
+    *n = 0;
+    if (n_win < 0) return LIMO_OK;
+    *n = ctx->last_log_n[window];
+    const int m = std::min(*n, cap);
+    if (m > 0) std::memcpy(out, ctx->last_log.data() + ctx->last_log_off[window], sizeof(limo_ba_iteration) * m);
     return LIMO_OK;
 }
 

@@ -199,6 +199,33 @@ limo_ctx* BundleAdjusterKeyframes::context() {
     return ctx_;
 }
 
+// The iteration-log entry points are weak references: the shim also links against backends that serve the C-ABI without them (the
+// test backends tests/cpp/oracle_abi.cpp and emu_pipeline.cpp) - there the addresses are null and the shim behaves as "no log".
+#pragma weak limo_ctx_set_iteration_log
+#pragma weak limo_ctx_last_iteration_log
+
+void BundleAdjusterKeyframes::setIterationLog(limo_ctx* ctx) {
+    last_iterations_.clear();
+    if (&limo_ctx_set_iteration_log != nullptr) (void)limo_ctx_set_iteration_log(ctx, minimizer_progress_to_stdout_ ? 1 : 0);
+}
+
+// The columns of Ceres' trust-region table the device has (no ls_iter, iter_time, total_time); cost as %.6e, the rest as %.2e.
+void BundleAdjusterKeyframes::collectIterations(limo_ctx* ctx, const char* what) {
+    if (!minimizer_progress_to_stdout_ || &limo_ctx_last_iteration_log == nullptr) return;
+    int32_t n = 0;
+    if (limo_ctx_last_iteration_log(ctx, 0, 0, nullptr, &n) != LIMO_OK) return;
+    last_iterations_.resize((size_t)std::max(0, n));
+    if (n > 0 && limo_ctx_last_iteration_log(ctx, 0, n, last_iterations_.data(), &n) != LIMO_OK) last_iterations_.clear();
+    std::printf("%s: %zu solver iterations logged\n", what, last_iterations_.size());
+    for (size_t i = 0; i < last_iterations_.size(); ++i) {
+        const limo_ba_iteration& e = last_iterations_[i];
+        if (i == 0 || last_iterations_[i - 1].solve != e.solve) std::printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n");
+        std::printf("%4d % .6e % .2e % .2e % .2e % .2e % .2e\n", e.iteration, e.cost, e.cost_change, e.gradient_max_norm, e.step_norm, e.relative_decrease,
+                    e.trust_region_radius);
+    }
+    std::fflush(stdout);
+}
+
 void BundleAdjusterKeyframes::set_solver_time(double s) {
     this->solver_time_sec = s;
 }
@@ -693,11 +720,13 @@ std::string BundleAdjusterKeyframes::solve() {
     limo_ba_report rep;
     limo_ctx* ctx = context();
     dump_window_if_asked(F.w);
+    setIterationLog(ctx);
     const auto t_s2 = clk::now();
     const int rc = limo_ba_solve(ctx, &F.w, &o, &rep);
     const auto t_s3 = clk::now();
     if (rc == LIMO_ERR_NOT_ENOUGH_KF) throw NotEnoughKeyframesException(F.kfs.size(), 3);
     if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_solve: ") + limo_last_error(ctx));
+    collectIterations(ctx, "solve");
     F.write_back(true);
     last_report_ = {rep.termination, rep.num_solves, rep.iterations_total, rep.n_trimmed_landmarks, rep.n_depth_blocks,
                     rep.n_repr_blocks, rep.n_gp_blocks, rep.initial_cost, rep.final_cost, rep.time_sec};
@@ -764,10 +793,12 @@ std::string BundleAdjusterKeyframes::adjustPoseOnly(Keyframe& kf) {
     o.max_solver_time_sec = solver_time_sec;
     limo_ba_report rep;
     limo_ctx* ctx = context();
+    setIterationLog(ctx);
     const auto t_p2 = clk::now();
     const int rc = limo_ba_adjust_pose_only(ctx, &F.w, prior.speed_weight > 0.0 ? &prior : nullptr, &o, &rep);
     const auto t_p3 = clk::now();
     if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_adjust_pose_only: ") + limo_last_error(ctx));
+    collectIterations(ctx, "adjustPoseOnly");
     F.write_back(false);
     last_report_ = {rep.termination, rep.num_solves, rep.iterations_total, rep.n_trimmed_landmarks, rep.n_depth_blocks,
                     rep.n_repr_blocks, rep.n_gp_blocks, rep.initial_cost, rep.final_cost, rep.time_sec};

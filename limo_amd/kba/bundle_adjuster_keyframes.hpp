@@ -12,8 +12,7 @@
 #include "keyframe.hpp"
 #include "landmark_selector.hpp"
 
-struct limo_ctx;
-struct limo_ray;
+#include "../../include/limo_hip.h"  // limo_ctx, limo_ray, limo_ba_iteration
 
 namespace keyframe_bundle_adjustment {
 
@@ -74,6 +73,17 @@ public:
         double initial_cost = 0, final_cost = 0, time_sec = 0;
     } last_report_;
 
+    // Ceres' per-iteration progress table (the reference sets Solver::Options::minimizer_progress_to_stdout = true,
+    // robust_optimization/robust_solving.hpp:105; off here by default - this shim has printed nothing so far).  true: solve() and
+    // adjustPoseOnly() switch the library's iteration log on (include/limo_hip.h:limo_ba_iteration), keep the entries of their call
+    // (lastIterations) and print to stdout: a caption line per call, then one header and one row per entry for every solve of the
+    // schedule.  A backend without the
+    // iteration-log symbols gives no log: nothing is printed, lastIterations() is empty.
+    bool minimizer_progress_to_stdout_ = false;
+    const std::vector<limo_ba_iteration>& lastIterations() const {
+        return last_iterations_;
+    }
+
 public:
     std::map<KeyframeId, Keyframe::Ptr> keyframes_;
     std::map<LandmarkId, Landmark::Ptr> landmarks_;
@@ -95,6 +105,9 @@ private:
     // landmark ids a pushed keyframe measures, in id order (the keys of its measurements_ as one contiguous array: the window cut
     // merges them instead of walking the maps node by node); rebuilt from the map whenever it does not look like it any more
     const std::vector<LandmarkId>& measuredIds(const Keyframe& kf);
+    void setIterationLog(limo_ctx* ctx);      // before the solve: the context's switch follows minimizer_progress_to_stdout_
+    void collectIterations(limo_ctx* ctx, const char* what);  // behind it: last_iterations_ and the table
+    std::vector<limo_ba_iteration> last_iterations_;
     limo_ctx* ctx_ = nullptr;
     double solver_time_sec;
 };
