@@ -268,6 +268,15 @@ int64_t limo_ctx_coop_fallbacks(const limo_ctx* ctx);
  *   info[7]  the linearisation that ran: 1 k_lin_lm<true> (LDS; also what the one-launch kernels contain), 0 k_lin_lm<false>
  *            (scalar loads: KBA_LIN_VLDS=0, windows with many views) */
 int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]);
+/* Which ground-plane Schur waves the last limo_ba_batch_solve on this context ran (same bits either way; how a test or a profile
+ * tells which kernel it has looked at).  A ground-plane group is NARROW when every ground-plane row of its landmarks hangs on one
+ * keyframe: its waves build a two-panel tile.  Groups are classified when the batch is packed, and only in a batch whose
+ * ground-plane tile has three panels.
+ *   info[0]  narrow and  info[1]  wide ground-plane groups of the batch (0, 0: nothing classified)
+ *   info[2]  launches of the solve in which narrow groups ran narrow waves (k_schur_lean_gp, k_schur_lean_pair)
+ *   info[3]  launches of the solve in which three-panel ground-plane waves ran: for the wide groups, next to the narrow waves in
+ *            the same launch; for every group in a batch that classified nothing and under KBA_SCHUR_GP_WIDE=1 (info[2] is 0 then) */
+int limo_ctx_last_schur_gp_info(const limo_ctx* ctx, int64_t info[4]);
 
 /*
  * Per-iteration solver log: what the reference prints for every solve (minimizer_progress_to_stdout = true,

@@ -96,6 +96,13 @@ class Context:
         keys = ("recovered", "coop_G", "groups", "slots", "rounds", "pair_launches", "lin_variant")
         return dict({"path": self.SOLVE_PATHS.get(int(v[0]), "NONE")}, **{k: int(v[1 + i]) for i, k in enumerate(keys)})
 
+    def last_schur_gp_info(self):
+        """limo_ctx_last_schur_gp_info: narrow / wide ground-plane Schur groups of the batch of the last solve on this context and the
+        launches that ran narrow / three-panel ground-plane waves."""
+        v = (C.c_int64 * 4)()
+        _check(self.lib.limo_ctx_last_schur_gp_info(self.ptr, v), self.ptr, "limo_ctx_last_schur_gp_info")
+        return dict(zip(("narrow_groups", "wide_groups", "narrow_launches", "wide_launches"), (int(x) for x in v)))
+
     def set_iteration_log(self, on):
         """limo_ctx_set_iteration_log: the solves on this context record Ceres' per-iteration table (off by default)."""
         _check(self.lib.limo_ctx_set_iteration_log(self.ptr, int(bool(on))), self.ptr, "limo_ctx_set_iteration_log")

@@ -36,6 +36,9 @@ struct BatchPlan {
     int asm_bytes = 0, solve_bytes = 0, trim_bytes = 0;  // k_cam_assemble, k_cam_solve, k_trim_select
     int schur_wave_lds = 0;  // LDS of one Schur wave inside the one-launch solve
     int onelaunch_lds = 0;   // the window-level phases of a one-launch solve (k_solve_wg; k_solve_coop adds its Schur waves)
+    // gp_tm == 3 and the pack found narrow ground-plane groups (PackedBatch::n_sgrp_narrow): k_schur_lean_gp serves the ground-plane
+    // groups - a narrow one on a tile of the pose columns, the rhs and one keyframe's <= 4 plane slots (two panels)
+    bool narrow = false;
 };
 
 inline BatchPlan plan_batch(const PackedBatch& P, const PlanKernelSizes& ks) {
@@ -63,6 +66,7 @@ inline BatchPlan plan_batch(const PackedBatch& P, const PlanKernelSizes& ks) {
         p.gp_wpe = p.gp_tm == 1 ? 3 : 2;
         p.leangp_lds = ks.lean_lds(max_nf + 1);
         p.pair_ok = p.plain_tm == 2 && p.gp_tm == 3;
+        p.narrow = p.gp_tm == 3 && P.n_sgrp_narrow > 0;
     }
     if (p.any_gen) {
         const int tiles = t_gen * (t_gen + 1) / 2, npw = (tiles + ks.wide_waves - 1) / ks.wide_waves;
@@ -132,6 +136,7 @@ struct SolveSwitches {
     double coop_timeout_ms = 50.0;  // KBA_COOP_TIMEOUT_MS: what a barrier of k_solve_coop waits before it gives the launch up
     bool groups_set = false;      // KBA_GROUPS is set ...
     int groups = 0;               // ... slot groups of a streaming solve (stream_geometry clamps to 1 .. 4) instead of its own rule
+    bool gp_wide = false;         // KBA_SCHUR_GP_WIDE (debugging aid): every ground-plane group runs the three-panel tile, the narrow kernel never
 };
 
 inline SolveSwitches read_solve_switches() {
@@ -152,6 +157,7 @@ inline SolveSwitches read_solve_switches() {
         s.groups_set = true;
         s.groups = std::atoi(e);
     }
+    s.gp_wide = on("KBA_SCHUR_GP_WIDE");
     return s;
 }
 

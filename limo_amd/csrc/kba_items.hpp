@@ -758,11 +758,24 @@ KBA_HD int schur_need_index(int n, int ca, int cb) { return ca * (n + 1) - ca * 
 KBA_HD int64_t slab_packed_base(int q, int n_plain, int nf, int nfq) {
     return q < n_plain ? (int64_t)q * schur_need_pad(nfq) : (int64_t)n_plain * schur_need_pad(nfq) + (int64_t)(q - n_plain) * schur_need_pad(nf);
 }
+// Panels (16 columns) of the ground-plane tile of a batch's fast-class windows, at most 3: the TM of their k_schur_lean<TM, true>.
+template <class Windows>
+inline int schur_gp_panels(const Windows& win) {
+    int max_nf = 0;
+    for (const WinDesc& d : win)
+        if (d.schur_fast && d.nf > max_nf) max_nf = d.nf;
+    const int t = (max_nf + 16) / 16;
+    return t < 3 ? t : 3;
+}
 // The record of the group of Schur blocks that starts at block sb of window w (kba_layout.hpp:SchurGroup), for the spans given:
 // at pack time for BatchView::sgrp, and by a Schur wave itself when it runs with other spans than those.  Fast-class windows only
 // (WinDesc::schur_fast: kl / view / col0 describe its <= 4 free keyframes).
+// With the row tables (lm_gp: landmark -> its ground-plane row or -1, gp_kf: row -> keyframe; the pack-time route) a ground-plane
+// group is also classified (SchurGroup::gp_class): NARROW when every row of its landmarks hangs on the same keyframe, or on
+// keyframes without a free plane slot - whatever the landmarks' state: trimming never changes the class.  Without the tables (a
+// wave that builds the record itself: other spans, the tile layout) every group is wide.
 KBA_HD SchurGroup schur_group_make(const WinDesc& wd, int w, int sb, int span, int span_gp, const int32_t* sblk_lm0, const int32_t* sblk_n,
-                                   const int32_t* cslot) {
+                                   const int32_t* cslot, const int32_t* lm_gp = nullptr, const int32_t* gp_kf = nullptr) {
     SchurGroup g;
     const int sb_last = schur_group_last(wd, sb, span, span_gp);
     g.w = w;
@@ -772,14 +785,45 @@ KBA_HD SchurGroup schur_group_make(const WinDesc& wd, int w, int sb, int span, i
     g.nf = wd.nf, g.nfq = wd.nfq, g.nf_pad = wd.nf_pad;
     g.kf0 = wd.kf0, g.view0 = wd.view0, g.cam0 = wd.cam0;
     g.q_slab = schur_slab_of(wd, sb, span, span_gp);
-    g.pad = 0;
     for (int k = 0; k < 4; ++k) {
         const bool on = k < wd.n_fk;
         g.kl[k] = on ? wd.fk[k] : -1;
         g.view[k] = on ? wd.fk_view[k] : -1;
         const int ci = on ? cslot[wd.cam0 + wd.fk[k] * kCamSlots] : -1;
         g.col0[k] = ci < 0 ? -1 : schur_col(ci, wd.nfq);
-        g.pad2[k] = 0;
+    }
+    g.gp_class = kSchurGpWide;
+    g.gp_ci0 = g.gp_ns = 0;
+    g.pad2[0] = g.pad2[1] = 0;
+    if (lm_gp && gp_kf && sb - wd.sblk0 >= wd.n_sblk_plain) {
+        int kn = kSchurGpNoPlane;
+        bool narrow = true;
+        for (int l = 0; l < g.n_lm && narrow; ++l) {
+            const int gr = lm_gp[g.lm_first + l];
+            if (gr < 0) continue;
+            const int k = gp_kf[gr] - wd.kf0;
+            const int32_t* cs = cslot + wd.cam0 + k * kCamSlots;
+            if (cs[6] < 0 && cs[7] < 0 && cs[8] < 0 && cs[9] < 0) continue;  // no free plane slot: the row adds to pose columns only
+            // (free plane slots behind a fixed pose block - no packed window has them - stay the wide tile's business)
+            if (cs[0] < 0 || (kn >= 0 && kn != k)) narrow = false;
+            kn = k;
+        }
+        if (narrow && kn >= 0) {  // the keyframe's free plane slots: consecutive compact indices (kba_pack.cpp numbers them in slot order)
+            int first = -1, n = 0;
+            for (int s = 6; s < kCamSlots; ++s) {
+                const int ci = cslot[wd.cam0 + kn * kCamSlots + s];
+                if (ci < 0) continue;
+                if (first < 0) first = ci;
+                if (ci != first + n) narrow = false;
+                ++n;
+            }
+            g.gp_ci0 = first, g.gp_ns = n;
+        }
+        if (narrow) {
+            g.gp_class = kn;
+        } else {
+            g.gp_ci0 = g.gp_ns = 0;
+        }
     }
     g.off_tile = wd.spart_off + (int64_t)g.q_slab * ((int64_t)wd.nf_pad * wd.nf_pad);
     g.off_packed = wd.spart_off + slab_packed_base(g.q_slab, schur_plain_slabs(wd, span), wd.nf, wd.nfq);
@@ -802,6 +846,16 @@ KBA_HD int slab_packed_write(bool gp, int zr, int zc, int nf, int nfq) {
     if (zr == nfq) return schur_need_index(n, zc - 1, n);
     return schur_need_index(n, zr - (zr > nfq ? 1 : 0), zc - (zc > nfq ? 1 : 0));
 }
+// The Z tile of a NARROW ground-plane group (SchurGroup::gp_class): the pose columns and the rhs where they always are, the ns free
+// plane slots of the group's keyframe (compact indices [ci0, ci0 + ns)) right behind the rhs, no column for any other plane slot.
+// schur_narrow_col: column zc of schur_col space -> column of the narrow tile, or -1; schur_narrow_zc: its inverse for a column
+// c < nfq + 1 + ns; schur_narrow_covers: compact slot ci has a column.  Both maps are monotone: an upper-triangle entry stays one.
+KBA_HD int schur_narrow_col(int zc, int nfq, int ci0, int ns) {
+    if (zc <= nfq) return zc;
+    return zc - 1 >= ci0 && zc - 1 < ci0 + ns ? nfq + 1 + (zc - 1 - ci0) : -1;
+}
+KBA_HD int schur_narrow_zc(int c, int nfq, int ci0) { return c <= nfq ? c : c - nfq + ci0; }
+KBA_HD bool schur_narrow_covers(int ci, int nfq, int ci0, int ns) { return ci < nfq || (ci >= ci0 && ci < ci0 + ns); }
 
 // ======================================================================================= back-substitution
 // Product of factors >= 1 kept as mantissa x 2^exponent: sum_j log(f_j) = log(prod_j f_j) costs ONE logarithm per landmark

@@ -830,8 +830,15 @@ __device__ __forceinline__ void schur_wave_sync() {
         __syncthreads();
     }
 }
-template <int TM, bool GP, bool COOP>
+// NARROW (TM = 2, GP, packed slabs only): the wave of a narrow ground-plane group (SchurGroup::gp_class: all its ground-plane rows
+// hang on one keyframe).  A row of Z is then non-zero in the pose columns, the rhs and the <= 4 free plane slots of that keyframe:
+// the tile keeps those <= 29 columns (kba_items.hpp:schur_narrow_col) - two panels, three accumulator tiles, 36 MFMAs per tile of 16
+// landmarks instead of 72 - and the epilogue stores +0.0 to the slab entries of the plane slots it has no column for, which is what
+// the three-panel tile sums there (same products in the same k-order everywhere else: same bits).  The caller picks the variant by
+// the record's class (k_schur_lean_gp, k_schur_lean_pair); a NARROW wave that meets a wide record leaves at once.
+template <int TM, bool GP, bool COOP, bool NARROW = false>
 __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, int span, int span_gp, int slab_packed, double* smem) {
+    static_assert(!NARROW || (TM == 2 && GP && !COOP), "the narrow tile: two panels, ground-plane groups, packed slabs");
     // ---- the head: everything a wave waits for before its first tile.  What describes the group is ONE record right behind the
     //      worklist entry (kba_layout.hpp:SchurGroup, scalar loads; with other spans than the record's - the landmark-sharded solve -
     //      the wave builds it from the window's descriptor and the block tables as the waves of rounds 3-6 did); then the index
@@ -847,6 +854,9 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
         const int w = bv.sblk_win[sb];
         g = schur_group_make(bv.win[w], w, sb, span, span_gp, bv.sblk_lm0, bv.sblk_n, bv.cslot);
     }
+    if constexpr (NARROW) {  // (wave-uniform: the record sits in scalar registers)
+        if (g.gp_class == kSchurGpWide) return;
+    }
     // Lock-step lists hold finished windows: their waves leave below, once the first loads are on their way (every address is
     // valid whatever the window's state).  (COOP: k_solve_coop only gets here for a window that iterates - and workgroup 0 may be
     // writing the window's LM state at this very moment (lm_decide_lin runs beside the Schur phase), so the state is not read)
@@ -854,7 +864,7 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     // shared the wait of the kernel-argument pointers in front of the first vector load, a trip of its own behind the record)
     const int active = COOP ? 1 : __hip_atomic_load(&bv.st[g.w].active, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int nfq = g.nfq, nfp = g.nf_pad;
-    const int ncol = GP ? g.nf + 1 : nfq + 1;  // columns of the tile, the rhs (column nfq) included
+    const int ncol = NARROW ? nfq + 1 + g.gp_ns : GP ? g.nf + 1 : nfq + 1;  // columns of the tile, the rhs (column nfq) included
     const int ld = schur_lean_ld(ncol);
     const int Tt = (ncol + 15) / 16;
     // Two-tile Gram (plain blocks, 17..25 columns): the <= 24 pose columns are covered by TWO 16x16 products instead of
@@ -981,7 +991,8 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
             if (li >= 5 && li < 15) mine_w[li == 14 ? kSpQq1 : li - 5] = vw ? v2 : 0.0;  // [37..45] R | [46] |q|^2 - 1
             if (li < kCamSlots) {
                 mine_w[kSpScale + li] = sc;
-                zcs[kq * 12 + li] = ci < 0 ? -1 : schur_col(ci, nfq);
+                const int zc = ci < 0 ? -1 : schur_col(ci, nfq);
+                zcs[kq * 12 + li] = NARROW ? schur_narrow_col(zc, nfq, g.gp_ci0, g.gp_ns) : zc;  // (-1 stays -1: the map keeps columns <= nfq)
             }
         }
         if (lane < 16) Z[3 * kSchurLm * ld + lane] = 0.0;
@@ -1149,6 +1160,38 @@ __device__ __forceinline__ void schur_lean_group(const BatchView& bv, int sb, in
     const bool packed = !COOP && slab_packed != 0;
     double* out = bv.S_part + (packed ? g.off_packed : g.off_tile);
     const int T = nfp / 16;
+    if constexpr (NARROW) {
+        // the accumulators go to the packed places of their real (zr, zc); every other entry of the slab - it involves a plane slot
+        // without a column here - gets the +0.0 the three-panel tile sums there: the camera solve reads the whole slab
+        double* outn = bv.S_part + g.off_packed;
+        const int nf = g.nf, ci0 = g.gp_ci0, ns = g.gp_ns;
+        int idx = 0;
+#pragma unroll
+        for (int tr = 0; tr < 2; ++tr)
+#pragma unroll
+            for (int tc = tr; tc < 2; ++tc) {
+                if (tc < Tt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = tr * 16 + kq + 4 * r, col = tc * 16 + li;
+                        if (row < ncol && col < ncol) {
+                            const int k = slab_packed_write(true, schur_narrow_zc(row, nfq, ci0), schur_narrow_zc(col, nfq, ci0), nf, nfq);
+                            if (k >= 0) outn[k] = acc[idx][r];
+                        }
+                    }
+                }
+                ++idx;
+            }
+        // entries (ca, cb <= nf) with a slot outside the tile: such a slot is a plane slot, so cb lies in [nfq, nf] (<= 16 plane slots:
+        // four rows per trip, a lane per column; then the rhs entries of those slots)
+        for (int ca = kq; ca < nf; ca += 4) {
+            const int cb = nfq + li;
+            if (cb >= ca && cb < nf && !(schur_narrow_covers(ca, nfq, ci0, ns) && schur_narrow_covers(cb, nfq, ci0, ns)))
+                outn[schur_need_index(nf, ca, cb)] = 0.0;
+        }
+        if (nfq + lane < nf && !schur_narrow_covers(nfq + lane, nfq, ci0, ns)) outn[schur_need_index(nf, nfq + lane, nf)] = 0.0;
+        return;
+    }
     if (two_tile && packed) {
         // the two products and the rhs sums go from the registers to their packed places (no staging matrix: nothing has to be
         // zero-filled, and no entry is written twice - the second product leaves the block {0..7} x {16..23} to the first)
@@ -1268,13 +1311,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     extern __shared__ __attribute__((aligned(16))) double smem[];
     schur_lean_group<TM, GP, false>(bv, sb, span, span_gp, slab_packed, smem);
 }
+// The ground-plane groups of a batch that has narrow ones (the records' spans, packed slabs): a wave runs the narrow tile or the
+// three-panel tile as its record says.  ONE launch over the list: about one group in fifty of the C2 benchmark windows is wide, and a
+// second launch whose waves leave on every narrow record cost 41 us per round of 4096 slots for them (profiles/r11_schur_narrow.txt).
+// Both variants run two waves per SIMD (188 / 232 registers; the narrow one alone at three waves spills: 76 B of scratch, and is slower).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_schur_lean_gp(BatchView bv, const int32_t* wl) {
+    const int sb = wl_at(bv, wl, blockIdx.x);
+    if (sb < 0) return;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    if (bv.sgrp[sb].gp_class != kSchurGpWide)
+        schur_lean_group<2, true, false, true>(bv, sb, kSchurSpan, kSchurSpanGp, 1, smem);
+    else
+        schur_lean_group<3, true, false>(bv, sb, kSchurSpan, kSchurSpanGp, 1, smem);
+}
 
 // The plain and the ground-plane groups of a round in ONE launch (workgroups [0, n_plain_cap) take the plain list, the others the
 // ground-plane list): for rounds with few windows in flight, where each of the two launches is one tile chain of latency (21 + 25 us
 // at 16 windows: scripts/gpu_round_timeline.py) and the two lists are independent.  The kernel carries the larger variant's registers
 // (218: two waves per SIMD), so it is only used while the batch drains (limo_hip.hip: kSchurPairBound); same device functions, same
-// slabs, same bits.
-template <int TMP, int TMG>
+// slabs, same bits.  NARROW: the batch has narrow ground-plane groups (the records' spans, packed slabs) - their waves run the narrow tile.
+template <int TMP, int TMG, bool NARROW = false>
 __global__ __launch_bounds__(64) void k_schur_lean_pair(BatchView bv, const int32_t* wl_plain, int n_plain_cap, const int32_t* wl_gp, int span, int span_gp, int slab_packed) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if ((int)blockIdx.x < n_plain_cap) {
@@ -1282,7 +1338,11 @@ __global__ __launch_bounds__(64) void k_schur_lean_pair(BatchView bv, const int3
         if (sb >= 0) schur_lean_group<TMP, false, false>(bv, sb, span, span_gp, slab_packed, smem);
     } else {
         const int sb = wl_at(bv, wl_gp, blockIdx.x - n_plain_cap);
-        if (sb >= 0) schur_lean_group<TMG, true, false>(bv, sb, span, span_gp, slab_packed, smem);
+        if (sb < 0) return;
+        if (NARROW && bv.sgrp[sb].gp_class != kSchurGpWide)
+            schur_lean_group<2, true, false, true>(bv, sb, span, span_gp, slab_packed, smem);
+        else
+            schur_lean_group<TMG, true, false>(bv, sb, span, span_gp, slab_packed, smem);
     }
 }
 

@@ -111,15 +111,20 @@ struct alignas(128) SchurGroup {
     int32_t nf, nfq, nf_pad;   // WinDesc::nf, nfq, nf_pad
     int32_t kf0, view0, cam0;  // WinDesc::kf0, view0, cam0
     int32_t q_slab;            // the group's partial slab (kba_items.hpp:schur_slab_of)
-    int32_t pad;
+    int32_t gp_class;          // ground-plane groups (kba_items.hpp:schur_group_make): kSchurGpWide, or the group is NARROW - every ground-plane
+                               // row of its landmarks hangs on ONE keyframe with free plane slots (its local index stands here) or on
+                               // keyframes without any (kSchurGpNoPlane) - and its Z tile needs no column for the other keyframes' plane slots
     int32_t kl[4];             // per free keyframe: local keyframe index (or -1),
     int32_t view[4];           //   its view (global index, or -1),
     int32_t col0[4];           //   tile column of its first pose slot, or -1: its pose block is not free
     int64_t off_tile;          // the slab's place in S_part, tile layout (spart_off + q_slab * nf_pad^2)
     int64_t off_packed;        //   and packed layout (kba_items.hpp:slab_packed_base)
-    int32_t pad2[4];
+    int32_t gp_ci0, gp_ns;     // narrow groups: first compact index and number of the free plane slots of keyframe gp_class (consecutive
+                               // in the compact numbering; 0, 0 without any)
+    int32_t pad2[2];
 };
 static_assert(sizeof(SchurGroup) == 128, "one cache line per record");
+constexpr int kSchurGpNoPlane = -1, kSchurGpWide = -2;  // SchurGroup::gp_class
 
 // Per-window Levenberg-Marquardt state (device resident; see kba_lm.hpp).
 struct WinState {

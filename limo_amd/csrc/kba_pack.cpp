@@ -815,13 +815,23 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
     P.n_lblk = (int)P.lblk_win.size();
     P.n_sblk = (int)P.sblk_win.size();
     // what a lean Schur wave needs to know about the group that starts at a block (spans of an unsharded batch)
+    // (ground-plane groups are classified narrow / wide where the batch's ground-plane tile has three panels - schur_gp_panels, the
+    // rule of kba_batch_plan.hpp:plan_batch - and nowhere else: two panels are what a narrow wave runs anyway)
     P.sgrp.assign((size_t)P.n_sblk, SchurGroup{});
+    const bool classify = schur_gp_panels(P.win) >= 3;
     for_windows([&](int w) {
         const WinDesc& d = P.win[w];
         if (!d.schur_fast) return;
         for (int sb = d.sblk0; sb < d.sblk0 + d.n_sblk; ++sb)
-            P.sgrp[sb] = schur_group_make(d, w, sb, kSchurSpan, kSchurSpanGp, P.sblk_lm0.data(), P.sblk_n.data(), P.cslot.data());
+            P.sgrp[sb] = schur_group_make(d, w, sb, kSchurSpan, kSchurSpanGp, P.sblk_lm0.data(), P.sblk_n.data(), P.cslot.data(),
+                                          classify ? P.lm_gp.data() : nullptr, classify ? P.gp_kf.data() : nullptr);
     });
+    P.n_sgrp_narrow = P.n_sgrp_wide = 0;
+    if (classify)
+        for (const WinDesc& d : P.win) {
+            if (!d.schur_fast) continue;
+            for (int i = d.n_sblk_plain; i < d.n_sblk; i += kSchurSpanGp) (P.sgrp[d.sblk0 + i].gp_class == kSchurGpWide ? P.n_sgrp_wide : P.n_sgrp_narrow)++;
+        }
     if (P.evaluate_only) {
         // The materialised pass (k_evaluate) writes the rows that EXIST: the depth rows go into COMPACT planes over the depth
         // observations only, indexed by the observation's rank among them in packed order (obs_rank).  Its work items are

@@ -103,6 +103,9 @@ struct PackedBatch {
     uvec<int32_t> obs_src;  // packed observation -> index in the caller's window
     std::vector<int32_t> lblk_win, lblk_lm0, lblk_n, sblk_win, sblk_lm0, sblk_n;
     std::vector<SchurGroup> sgrp;  // [n_sblk] kba_layout.hpp:SchurGroup (fast-class windows; zero elsewhere)
+    // ground-plane groups of fast-class windows by SchurGroup::gp_class, in a batch whose ground-plane tile has three panels (more
+    // than 32 columns in some fast-class window); a batch of two panels or one classifies nothing: 0 / 0, every record wide
+    int32_t n_sgrp_narrow = 0, n_sgrp_wide = 0;
     std::vector<int32_t> gp_lm, gp_kf;
     std::vector<double> gp_w;
 };

@@ -85,6 +85,8 @@ struct limo_ba_batch : Executor {
     int32_t* d_flags = nullptr;
     BatchPlan plan;  // kernel variants and LDS sizes (kba_batch_plan.hpp) ...
     const void *schur_fn_plain = nullptr, *schur_fn_leangp = nullptr, *schur_fn_gen = nullptr;  // ... and the variants as kernels
+    const void* schur_fn_narrow = nullptr;  // plan.narrow: k_schur_lean_gp
+    bool gp_wide = false;                   // SolveSwitches::gp_wide of the solve in progress
     bool schur_pair_ok = false;      // plan.pair_ok, and KBA_NO_SCHUR_PAIR is not set
     static constexpr int kSchurPairBound = 384;  // windows in flight in a slot group up to which a round launches the pair kernel (192: -0.7 %, 768: -9 % at 1024 windows)
     int32_t* h_flags = nullptr;  // pinned
@@ -121,6 +123,7 @@ struct limo_ba_batch : Executor {
     double last_solve_sec = 0.0;
     // what limo_ctx_last_solve_info tells about the solve in progress beyond its path (reset by limo_ba_batch_solve)
     int64_t n_rounds = 0, n_pair_launches = 0;
+    int64_t n_narrow_launches = 0, n_widegp_launches = 0;  // launches that ran narrow / three-panel ground-plane waves (limo_ctx_last_schur_gp_info)
     int lin_variant = 1;  // k_lin_lm<true> / <false> of the last launch; the one-launch kernels always linearise through LDS
 
     ~limo_ba_batch() override {
@@ -328,6 +331,12 @@ struct limo_ba_batch : Executor {
             schur_pair_ok = plan.pair_ok && !(std::getenv("KBA_NO_SCHUR_PAIR") && std::atoi(std::getenv("KBA_NO_SCHUR_PAIR")) != 0);
             if (schur_pair_ok)
                 HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_schur_lean_pair<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(plan.plain_lds, plan.leangp_lds)));
+            if (plan.narrow) {
+                schur_fn_narrow = (const void*)k_schur_lean_gp;
+                HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_narrow, hipFuncAttributeMaxDynamicSharedMemorySize, plan.leangp_lds));
+                if (schur_pair_ok)
+                    HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_schur_lean_pair<2, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(plan.plain_lds, plan.leangp_lds)));
+            }
         }
         if (plan.any_gen) {
             schur_fn_gen = schur_kernel(2, plan.wide_npw, 0);
@@ -703,12 +712,18 @@ struct limo_ba_batch : Executor {
 
     // The Schur kernels of one view over its three lists, in this order: both fast-class lists in ONE launch where the caller allows
     // the pair kernel (kba_kernels.hip:k_schur_lean_pair), else plain groups, then ground-plane groups; then the generic windows.
+    // Ground-plane groups of a batch in which the pack found narrow ones (plan.narrow; SchurGroup::gp_class), where the records' spans
+    // and packed slabs are in use: k_schur_lean_gp, and k_schur_lean_pair<2, 3, true> in a draining round - their waves run the
+    // narrow tile or the three-panel tile as the record says.  KBA_SCHUR_GP_WIDE: the three-panel kernels, as in every other batch.
     void launch_schur(const BatchView& v, const int32_t* wl_plain, int n_plain, const int32_t* wl_fgp, int n_fgp, const int32_t* wl_gen, int n_gen, bool pair,
                       hipStream_t s) {
         int span = c.schur_span, span_gp = c.schur_span_gp, packed = c.slab_packed;
+        const bool narrow = plan.narrow && !gp_wide && packed && span == kSchurSpan && span_gp == kSchurSpanGp;
+        const bool wide = !narrow || P.n_sgrp_wide > 0;  // three-panel waves run
         if (pair) {
             void* args[] = {(void*)&v, (void*)&wl_plain, (void*)&n_plain, (void*)&wl_fgp, (void*)&span, (void*)&span_gp, (void*)&packed};
-            note(hipLaunchKernel((const void*)k_schur_lean_pair<2, 3>, dim3(n_plain + n_fgp), dim3(64), args, std::max(plan.plain_lds, plan.leangp_lds), s),
+            note(hipLaunchKernel(narrow ? (const void*)k_schur_lean_pair<2, 3, true> : (const void*)k_schur_lean_pair<2, 3>, dim3(n_plain + n_fgp), dim3(64), args,
+                                 std::max(plan.plain_lds, plan.leangp_lds), s),
                  "launch k_schur_lean_pair");
             ++n_pair_launches;
         }
@@ -716,9 +731,17 @@ struct limo_ba_batch : Executor {
             void* args[] = {(void*)&v, (void*)&wl_plain, (void*)&span, (void*)&span_gp, (void*)&packed};
             note(hipLaunchKernel(schur_fn_plain, dim3(n_plain), dim3(64), args, plan.plain_lds, s), "launch k_schur_lean");
         }
-        if (!pair && n_fgp) {
+        if (!pair && n_fgp && narrow) {
+            void* args[] = {(void*)&v, (void*)&wl_fgp};
+            note(hipLaunchKernel(schur_fn_narrow, dim3(n_fgp), dim3(64), args, plan.leangp_lds, s), "launch k_schur_lean_gp");
+        }
+        if (!pair && n_fgp && !narrow) {
             void* args[] = {(void*)&v, (void*)&wl_fgp, (void*)&span, (void*)&span_gp, (void*)&packed};
             note(hipLaunchKernel(schur_fn_leangp, dim3(n_fgp), dim3(64), args, plan.leangp_lds, s), "launch k_schur_lean (gp)");
+        }
+        if (pair || n_fgp) {
+            n_narrow_launches += narrow ? 1 : 0;
+            n_widegp_launches += wide ? 1 : 0;
         }
         if (n_gen) {
             void* args[] = {(void*)&v, (void*)&wl_gen, (void*)&span, (void*)&span_gp};
@@ -1322,7 +1345,8 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     facts.coop_benched = ctx->coop_benched;
     const SolveChoice ch = choose_solve_path(b->P, b->plan, sw, facts);
     if (ch.benched) ++ctx->coop_benched;
-    b->n_rounds = b->n_pair_launches = 0;
+    b->n_rounds = b->n_pair_launches = b->n_narrow_launches = b->n_widegp_launches = 0;
+    b->gp_wide = sw.gp_wide;
     b->lin_variant = 1;
     long long* info = ctx->last_solve_info;
     std::fill(info, info + 8, 0ll);
@@ -1389,6 +1413,10 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     info[5] = b->n_rounds;
     info[6] = b->n_pair_launches;
     info[7] = b->lin_variant;
+    ctx->last_schur_gp_info[0] = b->P.n_sgrp_narrow;
+    ctx->last_schur_gp_info[1] = b->P.n_sgrp_wide;
+    ctx->last_schur_gp_info[2] = b->n_narrow_launches;
+    ctx->last_schur_gp_info[3] = b->n_widegp_launches;
     HIP_TRY(ctx, hipEventRecord(b->ev_total_b, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
@@ -1677,6 +1705,12 @@ int limo_ctx_exchange_stats(limo_ctx* ctx, int64_t* stats3) {
 int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]) {
     if (!ctx || !info) return LIMO_ERR_INVALID;
     for (int i = 0; i < 8; ++i) info[i] = ctx->last_solve_info[i];
+    return LIMO_OK;
+}
+
+int limo_ctx_last_schur_gp_info(const limo_ctx* ctx, int64_t info[4]) {
+    if (!ctx || !info) return LIMO_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) info[i] = ctx->last_schur_gp_info[i];
     return LIMO_OK;
 }
 
