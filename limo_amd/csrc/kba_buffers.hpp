@@ -72,6 +72,9 @@ void for_each_buffer(const PackedBatch& P, BatchView& bv, F f) {
     KBA_BUF(obs_u, TO * sizeof(float), P.obs_u.data());
     KBA_BUF(obs_v, TO * sizeof(float), P.obs_v.data());
     KBA_BUF(obs_d, TO * sizeof(float), P.obs_d.data());
+    // three planes over lm_slot's entries (kba_layout.hpp:BatchView::pair_m): from the pack where it filled them (the emulator), else
+    // left to the owner of the buffers (the library: k_pair_fill at create)
+    KBA_BUF(pair_m, (P.evaluate_only ? 1 : P.lm_slot.size()) * 3 * sizeof(float), P.pair_m.empty() ? nullptr : P.pair_m.data());
     KBA_BUF(lblk_win, NL * I, P.lblk_win.data());
     KBA_BUF(lblk_lm0, NL * I, P.lblk_lm0.data());
     KBA_BUF(lblk_n, NL * I, P.lblk_n.data());
@@ -89,7 +92,11 @@ void for_each_buffer(const PackedBatch& P, BatchView& bv, F f) {
     KBA_BUF(gp_cost_c, TG * D, nullptr);
     // evaluate-only batches (limo_ba_evaluate): rows u, v over the observations + the depth row over the depth observations
     KBA_BUF(obs_r, (size_t)(P.evaluate_only ? P.SO * 2 + P.SD : 1) * D, nullptr);
-    KBA_BUF(obs_c, (P.evaluate_only ? 1 : P.lm_slot.size() * 2) * D, nullptr);  // two planes over lm_slot's entries (kba_layout.hpp:obs_c_stride)
+    // two planes over lm_slot's entries (kba_layout.hpp:obs_c_stride).  No initial contents are needed, but not because nobody reads
+    // them blind: backsub_lane loads the planes of EVERY pair of a state-1 landmark's free views without asking whether the pair
+    // exists and relies on +0.0 there - which k_lin_lm / lin_lm_lane store for every such pair on every linearisation, and no
+    // back-substitution of a window runs before its first linearisation.  A change to those stores has to keep that.
+    KBA_BUF(obs_c, (P.evaluate_only ? 1 : P.lm_slot.size() * 2) * D, nullptr);
     KBA_BUF(obs_Jp, (size_t)(P.evaluate_only ? P.SO * 12 + P.SD * 6 : 1) * D, nullptr);
     KBA_BUF(obs_Jl, (size_t)(P.evaluate_only ? P.SO * 6 + P.SD * 3 : 1) * D, nullptr);
     if (P.evaluate_only) KBA_BUF(echunk, (size_t)std::max(1, P.n_echunk) * sizeof(EvalChunk), P.echunk.empty() ? nullptr : P.echunk.data());

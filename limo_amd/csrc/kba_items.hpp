@@ -86,16 +86,20 @@ struct LinIn {
     int live;     // landmark in the problem
 };
 
-KBA_HD void lin_fetch(const BatchView& bv, int64_t o, int gl, LinIn& in) {
+// r = the pair's index (view j of the window, landmark gl: j * SL + gl): the measurement comes from the pair planes
+// (kba_layout.hpp:BatchView::pair_m).  Returns false where the landmark has no observation in the view.
+KBA_HD bool lin_fetch_pair(const BatchView& bv, int64_t r, int gl, LinIn& in) {
     in.live = bv.lm_state[gl] != 0;
     in.p[0] = bv.lm[3 * (int64_t)gl];
     in.p[1] = bv.lm[3 * (int64_t)gl + 1];
     in.p[2] = bv.lm[3 * (int64_t)gl + 2];
     in.w = bv.lm_weight[gl];
     in.sw = sqrt(in.w);
-    in.u = bv.obs_u[o];
-    in.v = bv.obs_v[o];
-    in.d = bv.obs_d[o];
+    const int64_t PS = obs_c_stride(bv);
+    in.u = bv.pair_m[r];
+    in.v = bv.pair_m[PS + r];
+    in.d = bv.pair_m[2 * PS + r];
+    return in.d != kPairMissing;
 }
 
 // One observation at the CURRENT parameters: residual r (3, loss-corrected), the four scalars c4 = (au, xn, yn, sd) of
@@ -451,10 +455,8 @@ KBA_HD int lin_lm_lane(const BatchView& bv, const SolveConsts& c, int w, int gl,
     for (int i = 0; i < 3; ++i) acc.g[i] = 0.0;
     int fail = 0;
     for (int j = 0; j < wd.n_view; ++j) {
-        const int s = bv.lm_slot[(int64_t)j * bv.SL + gl];
-        if (s < 0) continue;
         LinIn in;
-        lin_fetch(bv, s, gl, in);
+        if (!lin_fetch_pair(bv, (int64_t)j * bv.SL + gl, gl, in)) continue;
         const double* vl = bv.view_lin + (int64_t)kViewLin * (wd.view0 + j);
         double r3[3], c4[4];
         if (j < wd.n_view_fixed0) {  // keyframe without a free pose block: cost and residual only (nobody reads its planes)
@@ -874,8 +876,12 @@ KBA_HD double logprod_log(const LogProd& a) { return log(a.m) + static_cast<doub
 
 // y_l = (V'+D^2)^-1 (g' - W'^T y_c);  delta_l = -S_l y_l;  candidate = lm + delta_l;  then the cost of the landmark's
 // observations AT THE CANDIDATE (Evaluator cost-only pass): the lane holds the candidate landmark, the candidate
-// poses' per-view constants are in view_lin_c (k_cam_solve), so the measurements (12 B per observation through the slot
-// table) are all that is read - the separate observation-major cost pass read 52 B per observation.
+// poses' per-view constants are in view_lin_c (k_cam_solve), so the measurements (12 B per pair at the pair's own index,
+// kba_layout.hpp:BatchView::pair_m - no slot table) are all that is read - the separate observation-major cost pass read
+// 52 B per observation.  Per pair: 16 B of planes in the views with a free pose block + 12 B of measurement in every view.
+// (The planes could be formed again from the measurement, the landmark and the view instead of loaded - lin_obs_core on the
+// same inputs gives the same bits - but the kernel is not bound by its bytes alone: the rebuilding k_backsub took 427 us per launch
+// against 341, profiles/r12_pair_measurements.txt.)
 // part: [2] model-cost-change part, [3] |x - x_cand|^2, [4] |x_cand|^2, [6] candidate cost, [7] 1 = a functor failed
 // w = window of the landmark (uniform over the workgroup: scalar loads of the window's and the views' constants)
 KBA_HD void backsub_lane(const BatchView& bv, const SolveConsts& c, int w, int gl, double* part) {
@@ -892,35 +898,31 @@ KBA_HD void backsub_lane(const BatchView& bv, const SolveConsts& c, int w, int g
         return;
     }
     const WinDesc& wd = bv.win[w];
-    // The view loops are branch-free and software-pipelined (slot two views ahead, data one view ahead): a pair the
-    // landmark does not have reads observation 0 and contributes exact zeros - with `continue` around the loads the
-    // memory queue drained at every view.
-    const int32_t* slot = bv.lm_slot + gl;
+    // The view loops are branch-free and software-pipelined (the pair's data one view ahead, at addresses the lane knows at its
+    // start): a pair the landmark does not have reads its inert entry (planes +0.0; measurement 0, 0, kPairMissing) and contributes
+    // exact zeros - with `continue` around the loads the memory queue drained at every view.
     const int n_view = wd.n_view;
     if (state == 1) {
         double a[3] = {0, 0, 0};
         // (the leading views of keyframes without a free pose block have a zero camera step: their terms of `a` are exact
         // zeros - the loop starts behind them and their planes are never loaded)
-        // The planes sit at the pair's own index (kba_layout.hpp:BatchView::obs_c): slot and planes of a view are three coalesced
-        // loads whose addresses the lane knows at its start, all one view ahead - the slot only says whether the pair exists.
+        // The planes sit at the pair's own index (kba_layout.hpp:BatchView::obs_c): two coalesced loads whose addresses the lane
+        // knows at its start, one view ahead.  They hold +0.0 where the pair does not exist (k_lin_lm writes every pair of these
+        // views on every linearisation), so nothing has to say whether it does: no slot load.
         const int j0 = wd.n_view_fixed0;
         const double* au_p = bv.obs_c;
         const double* sd_p = au_p + obs_c_stride(bv);
         int64_t r = (int64_t)j0 * bv.SL + gl;  // the pair's index, one view ahead of the loop
-        int s_cur = -1;
         double aun = 0.0, sdn = 0.0;
         if (j0 < n_view) {
-            s_cur = bv.lm_slot[r];
             aun = au_p[r];
             sdn = sd_p[r];
         }
         for (int j = j0; j < n_view; ++j) {
-            const bool have = s_cur >= 0;
             double c4[4];
-            c4[0] = have ? aun : 0.0;
-            c4[3] = have ? sdn : 0.0;
+            c4[0] = aun;
+            c4[3] = sdn;
             r += j + 1 < n_view ? bv.SL : 0;  // (the last view reloads itself: nobody reads it)
-            s_cur = bv.lm_slot[r];
             aun = au_p[r];
             sdn = sd_p[r];
             // E^T (F dc) of the pair, with F dc = c^T Rc (dR x + d_trans) = c^T (K x + k0) and E = c^T H: the view's
@@ -982,26 +984,17 @@ KBA_HD void backsub_lane(const BatchView& bv, const SolveConsts& c, int w, int g
     // (a constant landmark's pairs with the leading views of keyframes without a free pose block are fixed cost: not evaluated here)
     const int j_prog = state == 2 ? wd.n_view_fixed0 : 0;
     {
-        int s_cur = slot[0];
-        int s_nxt = n_view > 1 ? slot[bv.SL] : -1;
-        float un, vn, dn;
-        {
-            const int64_t o = s_cur >= 0 ? s_cur : 0;
-            un = bv.obs_u[o];
-            vn = bv.obs_v[o];
-            dn = bv.obs_d[o];
-        }
+        // the measurement of the pair at the pair's index, one view ahead; kPairMissing says that the pair does not exist
+        const int64_t PS = obs_c_stride(bv);
+        const float* pm = bv.pair_m + gl;  // u; v and d one and two planes on
+        float un = pm[0], vn = pm[PS], dn = pm[2 * PS];
         for (int j = 0; j < n_view; ++j) {
-            const bool have = s_cur >= 0 && j >= j_prog;
             const float u = un, v = vn, d = dn;
-            s_cur = s_nxt;
-            s_nxt = j + 2 < n_view ? slot[(int64_t)(j + 2) * bv.SL] : -1;
-            {
-                const int64_t o = s_cur >= 0 ? s_cur : 0;
-                un = bv.obs_u[o];
-                vn = bv.obs_v[o];
-                dn = bv.obs_d[o];
-            }
+            const bool have = d != kPairMissing && j >= j_prog;
+            pm += j + 1 < n_view ? bv.SL : 0;  // (the last view reloads itself: nobody reads it)
+            un = pm[0];
+            vn = pm[PS];
+            dn = pm[2 * PS];
             const double* vc = bv.view_lin_c + (int64_t)kViewLin * (wd.view0 + j);
             const double z0 = vc[0] * xc[0] + vc[1] * xc[1] + vc[2] * xc[2] + vc[9];
             const double z1 = vc[3] * xc[0] + vc[4] * xc[1] + vc[5] * xc[2] + vc[10];

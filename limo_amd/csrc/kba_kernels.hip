@@ -377,15 +377,16 @@ __global__ void k_view_consts(BatchView bv) {
 //   * the view's 37 constants (kba_items.hpp:view_consts_item) are wave-uniform: the workgroup copies its window's constants
 //     into LDS once and reads them from there (VLDS, the default since round 5); the other variant reads view_lin through the
 //     constant address space (written by k_sched_fill or k_view_consts, the launch before: scalar loads although plane stores precede them);
-//   * the observation of the pair (slot table -> index s -> u, v, d: 12 B) is fetched one view ahead, the slot two ahead;
-//   * branch-free: a landmark that does not see the view (or is out of the problem) runs the same arithmetic on a valid
-//     dummy observation, contributes zeros and stores +0.0 into the pair's place of the planes (kba_layout.hpp:BatchView::obs_c);
+//   * the measurement of the pair (u, v, d: 12 B at the pair's own index, kba_layout.hpp:BatchView::pair_m - no slot table, no
+//     dependent gather) is fetched one view ahead;
+//   * branch-free: a landmark that does not see the view (or is out of the problem) runs the same arithmetic on the pair's inert
+//     entry (0, 0, kPairMissing), contributes zeros and stores +0.0 into the pair's place of the planes (BatchView::obs_c);
 //   * the 28 camera-side sums of the view leave each WAVE through one reduce-scatter into the wave's LDS slice (no
 //     barrier in the loop); after the last view one barrier, then lane (view, entry) adds the four slices.
-// Bytes per pair: 4 (slot) + 12 (u, v, d) read, 16 (planes au, sd) written - also for a pair the landmark does not have, in the views
-// with a free pose block (+0.0: the planes are indexed by the pair); per landmark 32 read + 72 (V, g) + 48 (Bt) written -
-// 79 B per observation under counters (round 5); the separate view-major linearise + landmark-major accumulate pair of round 1
-// moved 101 + 93.
+// Bytes per pair: 12 (u, v, d) read - also for a pair the landmark does not have - 16 (planes au, sd) written, the same, in the
+// views with a free pose block (+0.0: the planes are indexed by the pair); per landmark 32 read + 72 (V, g) + 48 (Bt) written.
+// (79 B per observation under counters in round 5, with the slot table; the separate view-major linearise + landmark-major
+// accumulate pair of round 1 moved 101 + 93.)
 typedef const double __attribute__((address_space(4))) cdouble;
 constexpr int kLinAccl = 13;  // doubles per lane that lin_lm_block parks in LDS: V 6 | g 3 | Jacobi scale 3 | ground-plane row
 // (the body of k_lin_lm for landmark workgroup b; k_solve_wg runs it for the workgroups of its window one after the other)
@@ -428,7 +429,6 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     in.sw = sqrt(in.w);
     LmTailIn tail;  // (fetched here, in front of the view loop's stores: kba_items.hpp:LmTailIn)
     lin_lm_tail_fetch(bv, w, gl, tail);
-    const int32_t* slot = bv.lm_slot + gl;
     double* out = bv.lv_part + wd.lvpart_off + (int64_t)(b - wd.lblk0) * n_view * kLinPartial;
     extern __shared__ __attribute__((aligned(16))) double lin_lds[];  // [kLinAccl][kBlock] sums, tail inputs | VLDS: [view][kLinVlds] | [view][wave][kLinPartial]
     double* const vlds = lin_lds + kLinAccl * kBlock;
@@ -467,16 +467,12 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         for (int i = 0; i < 3; ++i) accl[(6 + i) * kBlock] = a.g[i];
     };
     int fail = 0;
-    // pipeline: slot of view j + 2, measurement of view j + 1 in flight while view j computes
-    int s_cur = slot[0];
-    int s_nxt = n_view > 1 ? slot[bv.SL] : -1;
-    float u_n, v_n, d_n;
-    {
-        const int64_t o = s_cur >= 0 ? s_cur : 0;
-        u_n = bv.obs_u[o];
-        v_n = bv.obs_v[o];
-        d_n = bv.obs_d[o];
-    }
+    // pipeline: the measurement of view j + 1 in flight while view j computes - three direct loads at the pair's index
+    // (kba_layout.hpp:BatchView::pair_m; kPairMissing in the depth plane: the landmark has no observation in the view)
+    const float* const pair_u = bv.pair_m + gl;
+    const float* const pair_v = pair_u + plane_stride;
+    const float* const pair_d = pair_v + plane_stride;
+    float u_n = pair_u[0], v_n = pair_v[0], d_n = pair_d[0];
     const int rs14_idx = rs14_index(lane);
     // ---- the leading views of keyframes WITHOUT a free pose block (WinDesc::n_view_fixed0: the Pose-fixed oldest keyframe of
     //      a sliding window): same pipeline, same landmark-block terms, but no planes stored, no pose Jacobian, no U / g, and only the
@@ -491,19 +487,16 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
         // (the constants are read where they are used - scalar loads the compiler places next to their instructions; a local
         // copy of all 55 would not fit the scalar register file)
         VT vl = vc + (int64_t)j * kVStride;
-        const int s = s_cur;
         in.u = u_n;
         in.v = v_n;
         in.d = d_n;
-        s_cur = s_nxt;
-        s_nxt = j + 2 < n_view ? slot[(int64_t)(j + 2) * bv.SL] : -1;
         {
-            const int64_t o = s_cur >= 0 ? s_cur : 0;
-            u_n = bv.obs_u[o];
-            v_n = bv.obs_v[o];
-            d_n = bv.obs_d[o];
+            const int64_t rn = (int64_t)(j + 1 < n_view ? j + 1 : j) * bv.SL;  // (the last view reloads itself: nobody reads it)
+            u_n = pair_u[rn];
+            v_n = pair_v[rn];
+            d_n = pair_d[rn];
         }
-        const bool have = state != 0 && s >= 0;
+        const bool have = state != 0 && in.d != kPairMissing;
         in.live = have;
         LinLane l;
         double r3[3], c4[4];
@@ -515,19 +508,16 @@ __device__ __forceinline__ void lin_lm_block(const BatchView& bv, const SolveCon
     }
     for (int j = j_cam0; j < n_view; ++j) {
         VT vl = vc + (int64_t)j * kVStride;
-        const int s = s_cur;
         in.u = u_n;
         in.v = v_n;
         in.d = d_n;
-        s_cur = s_nxt;
-        s_nxt = j + 2 < n_view ? slot[(int64_t)(j + 2) * bv.SL] : -1;
         {
-            const int64_t o = s_cur >= 0 ? s_cur : 0;
-            u_n = bv.obs_u[o];
-            v_n = bv.obs_v[o];
-            d_n = bv.obs_d[o];
+            const int64_t rn = (int64_t)(j + 1 < n_view ? j + 1 : j) * bv.SL;  // (the last view reloads itself: nobody reads it)
+            u_n = pair_u[rn];
+            v_n = pair_v[rn];
+            d_n = pair_d[rn];
         }
-        const bool have = state != 0 && s >= 0;
+        const bool have = state != 0 && in.d != kPairMissing;
         in.live = have;
         LinLane l;
         double r3[3], c4[4];
@@ -2116,6 +2106,26 @@ __global__ void k_unpack(ExchangeLayout L, const WinDesc* win, const double* ran
 
 // out = landmark positions of the landmarks this shard owns, zero elsewhere (input of the final all-reduce that
 // gives every rank every landmark).
+// The measurements at the pair's index (kba_layout.hpp:BatchView::pair_m), once per batch at create: entry i of lm_slot -> the
+// observation's u, v and its depth if that is > 0, else kPairNoDepth; 0, 0, kPairMissing where the landmark has no observation in the
+// view - what the packer writes on the host for the emulator (kba_pack.cpp, pass 2).  n = entries of lm_slot = obs_c_stride(bv).
+__global__ __launch_bounds__(kBlock) void k_pair_fill(BatchView bv, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int s = bv.lm_slot[i];
+    float u = 0.0f, v = 0.0f, d = kPairMissing;
+    if (s >= 0) {
+        u = bv.obs_u[s];
+        v = bv.obs_v[s];
+        const float od = bv.obs_d[s];
+        d = od > 0.0f ? od : kPairNoDepth;
+    }
+    float* pm = const_cast<float*>(bv.pair_m);
+    pm[i] = u;
+    pm[n + i] = v;
+    pm[2 * n + i] = d;
+}
+
 __global__ void k_lm_owned(BatchView bv, double* out, int rank, int n_shards, int world) {
     const int gl = blockIdx.x * blockDim.x + threadIdx.x;
     if (gl >= bv.TL) return;

@@ -243,6 +243,14 @@ struct BatchView {
     const int32_t* blk_n;       // [n_blk]
     const int32_t* obs_lm;      // [TO] global landmark
     const float *obs_u, *obs_v, *obs_d;  // [TO]
+    // The measurement of a PAIR (view j of its window, packed landmark gl) at the pair's own index j * SL + gl - the index of its
+    // entry in lm_slot and of its planes in obs_c: three float planes u | v | d, [3][Vmax][SL], plane k at k * obs_c_stride(bv).  A
+    // landmark lane knows the addresses from the window's record alone, three coalesced loads with no slot load in front of them
+    // (solver batches; kba_pack.cpp fills them once per batch, the measurements of a batch never change).  An existing pair holds
+    // the observation's u, v and its depth when that is > 0, else kPairNoDepth (every caller value that is not > 0: 0, negatives,
+    // NaN); a pair the landmark does not have holds u = v = 0 and kPairMissing.  The
+    // readers only test d > 0 and d == kPairMissing; obs_u / obs_v / obs_d keep the caller's values (trimming, k_evaluate, download).
+    const float* pair_m;        // [3][Vmax*SL]  (one entry per plane in evaluate-only batches)
     const int32_t* lblk_win;    // [n_lblk]
     const int32_t* lblk_lm0;
     const int32_t* lblk_n;
@@ -326,6 +334,10 @@ struct BatchView {
     int32_t sched_off[SL_COUNT];  // offset of list k's count word inside sched_lists
     int32_t* sched_done_host;   // pinned ring (4 words): windows finished as of round r at [r & 3]
 };
+
+// depth values of the d plane of BatchView::pair_m that no measured depth can have (a measured depth is > 0)
+constexpr float kPairNoDepth = -1.0f;   // the pair exists, its observation carries no depth
+constexpr float kPairMissing = -2.0f;   // the landmark has no observation in the view
 
 // doubles between the two planes of BatchView::obs_c (solver batches): the rows of lm_slot
 #if defined(__HIPCC__)

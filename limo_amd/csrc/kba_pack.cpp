@@ -361,6 +361,18 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
     P.lm_slot.resize((size_t)std::max(1, P.Vmax) * P.SL);  // filled with -1 per window in pass 2, padding here
     for (int v = 0; v < std::max(1, P.Vmax); ++v)
         for (int64_t l = P.TL; l < P.SL; ++l) P.lm_slot[(size_t)v * P.SL + l] = -1;
+    // the measurements at the pair's index (kba_layout.hpp:BatchView::pair_m): filled next to lm_slot in pass 2, padding here
+    const bool host_pairs = po.host_pair_planes && !po.evaluate_only;  // (an evaluate-only batch has no reader of the planes)
+    const size_t n_pair = P.lm_slot.size();
+    P.pair_m.clear();
+    if (host_pairs) {
+        P.pair_m.resize(3 * n_pair);
+        for (int v = 0; v < std::max(1, P.Vmax); ++v)
+            for (int64_t l = P.TL; l < P.SL; ++l) {
+                P.pair_m[(size_t)v * P.SL + l] = P.pair_m[n_pair + (size_t)v * P.SL + l] = 0.0f;
+                P.pair_m[2 * n_pair + (size_t)v * P.SL + l] = kPairMissing;
+            }
+    }
     P.view_kf.resize(P.TV);
     P.view_win.resize(P.TV);
     P.view_cam.assign((size_t)P.TV * 16, 0.0);
@@ -389,6 +401,12 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
         WinDesc& d = P.win[w];
         for (int v = 0; v < std::max(1, P.Vmax); ++v)
             std::fill_n(P.lm_slot.data() + (size_t)v * P.SL + d.lm0, W.n_lm, -1);
+        if (host_pairs)
+            for (int v = 0; v < std::max(1, P.Vmax); ++v) {
+                std::fill_n(P.pair_m.data() + (size_t)v * P.SL + d.lm0, W.n_lm, 0.0f);
+                std::fill_n(P.pair_m.data() + n_pair + (size_t)v * P.SL + d.lm0, W.n_lm, 0.0f);
+                std::fill_n(P.pair_m.data() + 2 * n_pair + (size_t)v * P.SL + d.lm0, W.n_lm, kPairMissing);
+            }
         std::memcpy(P.pose.data() + (size_t)d.kf0 * 7, W.kf_pose, sizeof(double) * 7 * W.n_kf);
         std::memcpy(P.pdir.data() + (size_t)d.kf0 * 3, W.kf_plane_dir, sizeof(double) * 3 * W.n_kf);
         std::memcpy(P.pdist.data() + d.kf0, W.kf_plane_dist, sizeof(double) * W.n_kf);
@@ -561,6 +579,12 @@ int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options
                     return;
                 }
                 slot = o;
+                if (host_pairs) {  // the pair's measurement at the pair's index; the plane's depth is canonical (kPairNoDepth)
+                    const size_t r = (size_t)v * P.SL + d.lm0 + l;
+                    P.pair_m[r] = W.obs_u[src];
+                    P.pair_m[n_pair + r] = W.obs_v[src];
+                    P.pair_m[2 * n_pair + r] = W.obs_d[src] > 0.0f ? W.obs_d[src] : kPairNoDepth;
+                }
                 lm_nobs[l]++;
                 if (W.obs_d[src] > 0.0f) depth_blocks++;
             }

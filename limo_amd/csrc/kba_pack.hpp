@@ -100,6 +100,9 @@ struct PackedBatch {
     std::vector<int32_t> obs_rank;  // evaluate-only batches: index of the observation's depth row in the depth planes or -1
     uvec<int32_t> obs_lm;
     uvec<float> obs_u, obs_v, obs_d;
+    // the measurements u | v | d over lm_slot's entries, [3][lm_slot.size()] (kba_layout.hpp:BatchView::pair_m) - only with
+    // PackOptions::host_pair_planes (the emulator); empty otherwise: the library fills the device planes itself (k_pair_fill)
+    uvec<float> pair_m;
     uvec<int32_t> obs_src;  // packed observation -> index in the caller's window
     std::vector<int32_t> lblk_win, lblk_lm0, lblk_n, sblk_win, sblk_lm0, sblk_n;
     std::vector<SchurGroup> sgrp;  // [n_sblk] kba_layout.hpp:SchurGroup (fast-class windows; zero elsewhere)
@@ -125,6 +128,9 @@ struct PackOptions {
     // flagged landmarks of a window form their own run of the packed order behind the variable ones (WinDesc::n_lm_const): landmark
     // workgroups of their own, no Schur block.  A window without a flag set packs exactly as it does without the array.
     const uint8_t* const* lm_fixed = nullptr;
+    // Fill PackedBatch::pair_m on the host.  The library turns it off: 12 B x Vmax x SL would be written here and cross the bus,
+    // where a kernel at create forms the planes from lm_slot and obs_u / obs_v / obs_d, which are on the device anyway.
+    bool host_pair_planes = true;
 };
 
 // Returns LIMO_OK or a negative limo_status; err receives a message.

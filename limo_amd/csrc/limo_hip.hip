@@ -257,6 +257,12 @@ struct limo_ba_batch : Executor {
         }
         if (zero_total) HIP_TRY(ctx, hipMemsetAsync(arena + init_total, 0, zero_total, ctx->stream));
         if (status != LIMO_OK) return status;
+        // the measurements at the pair's index, from the slot table and the observations that have just been uploaded (the same stream)
+        if (!P.evaluate_only && P.pair_m.empty()) {
+            const int64_t n_pair = (int64_t)P.lm_slot.size();
+            hipLaunchKernelGGL(k_pair_fill, dim3((unsigned)((n_pair + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, bv, n_pair);
+            HIP_TRY(ctx, hipGetLastError());
+        }
         pv.assign(1, bv);
         if (shard_P > 1) {
             xl = exchange_layout(P);
@@ -1257,7 +1263,9 @@ static int batch_create_impl(limo_ctx* ctx, int32_t n, const limo_ba_window* win
     int rc = LIMO_OK;
     try {  // (the pack's host threads hand their exceptions to the caller, kba_pack.cpp:PackPool - none may cross the C ABI)
         PackArenaLend loan(lending ? &lend : nullptr);
-        rc = pack_windows(n, windows, o, po, b->P, ctx->err);
+        PackOptions pod = po;
+        pod.host_pair_planes = false;  // (k_pair_fill forms the planes on the device: limo_ba_batch::upload)
+        rc = pack_windows(n, windows, o, pod, b->P, ctx->err);
     } catch (const std::bad_alloc&) {
         ctx->err = "pack_windows: out of host memory";
         return LIMO_ERR_RUNTIME;

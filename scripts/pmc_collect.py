@@ -33,6 +33,7 @@ GROUPS = {
     "sq": [["SQ_BUSY_CYCLES", "SQ_WAVE_CYCLES", "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_INSTS_VALU_MFMA_MOPS_F64", "SQ_INSTS_VALU", "SQ_ACTIVE_INST_ANY", "SQ_WAIT_INST_ANY", "SQ_WAIT_ANY"],
            ["GRBM_GUI_ACTIVE", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_VALU", "SQ_INST_CYCLES_VMEM", "SQ_WAIT_INST_LDS", "SQ_LDS_BANK_CONFLICT"]],
 }
+ONCE_PER_BATCH = ("k_pair_fill",)  # limo_ba_batch's upload: the measurements at the pair's index (kba_kernels.hip)
 SIMDS_PER_SAMPLED_SE = 32  # SQ counters are sampled on one shader engine (8 CUs x 4 SIMDs on this part): ratios, not absolutes
 
 
@@ -129,7 +130,8 @@ def collect(passes, timeout, workload=None, per_pass=90.0):
         if "SQ_LDS_BANK_CONFLICT" in k and k.get("SQ_INSTS_LDS"):
             k["lds_bank_conflict_per_lds_inst"] = k["SQ_LDS_BANK_CONFLICT"] / k["SQ_INSTS_LDS"]
     if meta:
-        tot = sum(k.get("hbm_MB", 0.0) for n, k in out["kernels"].items() if n.startswith("k_"))
+        # (kernels that run once per batch, at create, are no part of a round's traffic: they keep their own entry)
+        tot = sum(k.get("hbm_MB", 0.0) for n, k in out["kernels"].items() if n.startswith("k_") and n.split("<")[0] not in ONCE_PER_BATCH)
         if tot > 0.0:
             out["round_hbm_MB"] = tot
             out["round_hbm_bytes_per_observation"] = tot * 1e6 / meta["observations"]
