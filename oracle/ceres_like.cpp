@@ -434,6 +434,16 @@ struct Minimizer {
             pr.r = residuals;
             pr.D = lm_diagonal;
             pr.y = ok ? step : std::vector<double>();
+            pr.scale = scale;
+            pr.col_user.assign(prog.num_eff, nullptr);
+            pr.col_comp.assign(prog.num_eff, 0);
+            for (const ParamBlock* pb : prog.pblocks)
+                for (int c = 0; c < pb->lsize(); ++c) {
+                    pr.col_user[pb->delta_off + c] = pb->user;
+                    pr.col_comp[pb->delta_off + c] = c;
+                }
+            pr.cost = x_cost;
+            pr.fixed_cost = sum.fixed_cost;
         }
         if (!ok) return;
         for (auto& s : step) s = -s;

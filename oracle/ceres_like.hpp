@@ -284,10 +284,17 @@ struct SolverSummary {
 // Test probe (tests/test_oracle_crosscheck.py): the linear least-squares problem of the FIRST trust-region step as the
 // Schur-based LinearSolve saw it - dense (column-scaled) Jacobian, residuals, LM diagonal - and the step it returned, so
 // that a dense solver outside this library can solve  min |J y - r|^2 + |D y|^2  independently.
+// For tests/lm_step_common.py it also carries the Jacobi column scale in use (ones when jacobi_scaling is off), the parameter block
+// behind every tangent column (the block's user pointer and the component inside the block's tangent space: the caller knows which of
+// its arrays the pointer lies in), and the cost at the point of the probe without the fixed cost, which stands next to it.
 struct StepProbe {
     bool filled = false;
     int num_residuals = 0, num_eff = 0, num_e = 0;
     std::vector<double> J, r, D, y;  // J row-major num_residuals x num_eff; e-blocks (landmarks) first
+    std::vector<double> scale;       // num_eff
+    std::vector<const double*> col_user;  // num_eff
+    std::vector<int> col_comp;            // num_eff
+    double cost = 0, fixed_cost = 0;
 };
 
 struct SolverOptions {  // ceres::Solver::Options defaults (1.13) + the reference's overrides

@@ -245,6 +245,8 @@ void print_summary(const SolverSummary& s) {
 // group ids (= landmark indices of the caller's window) removed by the last solve_trimmed of this thread: lets a
 // test rebuild the problem the final solve actually saw (tests/test_basin_restart.py)
 static thread_local std::vector<unsigned long> g_last_removed;
+// the iteration summaries of the solves the last solve_trimmed of this thread kept (oracle_last_iteration_log)
+static thread_local std::vector<std::vector<IterationSummary>> g_last_tables;
 
 struct TrimResult {
     std::vector<SolverSummary> summaries;
@@ -299,6 +301,8 @@ TrimResult solve_trimmed(const std::vector<int>& number_iterations,
     if (getenv("ORACLE_VERBOSE")) print_summary(fin);
     R.n_trimmed = (int)all_removed.size();
     g_last_removed.assign(all_removed.begin(), all_removed.end());
+    g_last_tables.clear();
+    for (const auto& s : R.summaries) g_last_tables.push_back(s.iterations);
     return R;
 }
 
@@ -743,27 +747,52 @@ int oracle_functor_jacobian(int kind, const double* consts, const double* p0, co
     return cost->Evaluate(ps, residuals, jj) ? cost->nres : 0;
 }
 
+// The solve() problem BUILT at the parameters of `w` (the nearest keyframe and weight of every ground-plane row, the scale the scale
+// regulariser holds: constants of the problem, fixed when it is built) on private copies of the parameter arrays, which then take the
+// values of `at` (pose, plane direction, plane distance, landmarks; the whole set or null): where the problem is evaluated.
+struct ProblemAt {
+    std::vector<double> pose, dir, dist, lm;
+    limo_ba_window c;
+    Built B;
+    ProblemAt(const limo_ba_window& w, const limo_ba_options& o, const double* const* at)
+        : pose(w.kf_pose, w.kf_pose + 7 * (size_t)w.n_kf), dir(w.kf_plane_dir, w.kf_plane_dir + 3 * (size_t)w.n_kf),
+          dist(w.kf_plane_dist, w.kf_plane_dist + w.n_kf), lm(w.lm_pos, w.lm_pos + 3 * (size_t)w.n_lm), c(w) {
+        c.kf_pose = pose.data();
+        c.kf_plane_dir = dir.data();
+        c.kf_plane_dist = dist.data();
+        c.lm_pos = lm.data();
+        build_solve_problem(c, o, B);
+        if (at) {
+            std::copy(at[0], at[0] + pose.size(), pose.begin());
+            std::copy(at[1], at[1] + dir.size(), dir.begin());
+            std::copy(at[2], at[2] + dist.size(), dist.begin());
+            std::copy(at[3], at[3] + lm.size(), lm.begin());
+        }
+    }
+};
+
 // First trust-region step of the solve() problem of `w` (w is left at its input values): fills the probe arrays (see
 // StepProbe).  sizes3 = (num_residuals, num_eff, num_e); arrays may be null to query the sizes first.
-int oracle_ba_first_step(const limo_ba_window* w, const limo_ba_options* o, int32_t* sizes3, double* J, double* r, double* D, double* y) {
+//   at4      null, or the parameter arrays (kf_pose, kf_plane_dir, kf_plane_dist, lm_pos; shapes of w) the step is taken FROM: the
+//            problem is the one built at w (see ProblemAt) - how a test looks at the second step of a solve
+//   scale    num_eff: the Jacobi column scale of the probe (ones with jacobi_scaling off); J is scaled by it
+//   colmap   num_eff x 3: the parameter block of every tangent column - kind (0 landmark, 1 pose, 2 plane direction, 3 plane
+//            distance), index in the caller's window, component of the block's tangent space
+//   costs2   cost at the point of the probe WITHOUT the fixed cost, the fixed cost
+// A probe whose Schur-based solve failed (an invalid step) still has everything but y: y is NaN then.
+static int step_probe(const limo_ba_window* w, const limo_ba_options* o, const double* const* at4, bool need_y, int32_t* sizes3, double* J, double* r,
+                      double* D, double* y, double* scale, int32_t* colmap, double* costs2) {
     if (!w || !o || !sizes3) return LIMO_ERR_INVALID;
     // private copies of the parameter arrays: Solve() writes the result of its one iteration back
-    std::vector<double> pose(w->kf_pose, w->kf_pose + 7 * (size_t)w->n_kf), dir(w->kf_plane_dir, w->kf_plane_dir + 3 * (size_t)w->n_kf),
-        dist(w->kf_plane_dist, w->kf_plane_dist + w->n_kf), lm(w->lm_pos, w->lm_pos + 3 * (size_t)w->n_lm);
-    limo_ba_window c = *w;
-    c.kf_pose = pose.data();
-    c.kf_plane_dir = dir.data();
-    c.kf_plane_dist = dist.data();
-    c.lm_pos = lm.data();
-    Built B;
-    build_solve_problem(c, *o, B);
+    ProblemAt P(*w, *o, at4);
     SolverOptions so = make_options(*o, 1, 1);
     so.max_num_iterations = 1;
     StepProbe probe;
     so.probe = &probe;
     SolverSummary sum;
-    Solve(so, &B.problem, &sum);
-    if (!probe.filled || probe.y.empty()) return 1;
+    Solve(so, &P.B.problem, &sum);
+    if (!probe.filled || (need_y && probe.y.empty())) return 1;
+    if (probe.y.empty()) probe.y.assign(probe.num_eff, std::numeric_limits<double>::quiet_NaN());
     sizes3[0] = probe.num_residuals;
     sizes3[1] = probe.num_eff;
     sizes3[2] = probe.num_e;
@@ -771,7 +800,81 @@ int oracle_ba_first_step(const limo_ba_window* w, const limo_ba_options* o, int3
     if (r) std::memcpy(r, probe.r.data(), sizeof(double) * probe.r.size());
     if (D) std::memcpy(D, probe.D.data(), sizeof(double) * probe.D.size());
     if (y) std::memcpy(y, probe.y.data(), sizeof(double) * probe.y.size());
+    if (scale) std::memcpy(scale, probe.scale.data(), sizeof(double) * probe.scale.size());
+    if (colmap) {
+        const limo_ba_window& c = P.c;
+        for (int i = 0; i < probe.num_eff; ++i) {
+            const double* u = probe.col_user[i];
+            int kind = -1, index = -1;
+            if (u >= c.lm_pos && u < c.lm_pos + 3 * (size_t)c.n_lm) {
+                kind = 0;
+                index = (int)((u - c.lm_pos) / 3);
+            } else if (u >= c.kf_pose && u < c.kf_pose + 7 * (size_t)c.n_kf) {
+                kind = 1;
+                index = (int)((u - c.kf_pose) / 7);
+            } else if (u >= c.kf_plane_dir && u < c.kf_plane_dir + 3 * (size_t)c.n_kf) {
+                kind = 2;
+                index = (int)((u - c.kf_plane_dir) / 3);
+            } else if (u >= c.kf_plane_dist && u < c.kf_plane_dist + c.n_kf) {
+                kind = 3;
+                index = (int)(u - c.kf_plane_dist);
+            }
+            colmap[3 * i + 0] = kind;
+            colmap[3 * i + 1] = index;
+            colmap[3 * i + 2] = probe.col_comp[i];
+        }
+    }
+    if (costs2) {
+        costs2[0] = probe.cost;
+        costs2[1] = probe.fixed_cost;
+    }
     return LIMO_OK;
+}
+
+int oracle_ba_step_probe(const limo_ba_window* w, const limo_ba_options* o, const double* const* at4, int32_t* sizes3, double* J, double* r,
+                         double* D, double* y, double* scale, int32_t* colmap, double* costs2) {
+    return step_probe(w, o, at4, false, sizes3, J, r, D, y, scale, colmap, costs2);
+}
+
+int oracle_ba_first_step(const limo_ba_window* w, const limo_ba_options* o, int32_t* sizes3, double* J, double* r, double* D, double* y) {
+    return step_probe(w, o, nullptr, true, sizes3, J, r, D, y, nullptr, nullptr, nullptr);
+}
+
+// Total cost (with loss) of the solve() problem built at `w`, evaluated at the parameter arrays of at4 (see oracle_ba_step_probe).
+int oracle_ba_problem_cost_at(const limo_ba_window* w, const limo_ba_options* o, const double* const* at4, double* cost) {
+    if (!w || !o || !at4 || !cost) return LIMO_ERR_INVALID;
+    ProblemAt P(*w, *o, at4);
+    std::vector<ResidualBlock*> all;
+    for (auto& b : P.B.problem.blocks) all.push_back(b.get());
+    return P.B.problem.Evaluate(all, true, cost, nullptr) ? LIMO_OK : 1;
+}
+
+// The iteration table of the last oracle_ba_solve / oracle_ba_adjust_pose_only on this thread as limo_ba_iteration entries (what
+// ORACLE_VERBOSE prints, at full precision): every solve that solveTrimmed kept, in order (a discarded first attempt is not among
+// them; `solve` counts the kept ones).  Returns the number of entries; at most cap of them are written.
+int oracle_last_iteration_log(int32_t cap, limo_ba_iteration* out) {
+    int n = 0;
+    for (size_t si = 0; si < g_last_tables.size(); ++si)
+        for (const IterationSummary& it : g_last_tables[si]) {
+            if (out && n < cap) {
+                limo_ba_iteration e;
+                std::memset(&e, 0, sizeof(e));
+                e.solve = (int32_t)si;
+                e.solve_kind = si + 1 == g_last_tables.size() ? 2 : 0;
+                e.iteration = it.iteration;
+                e.step_is_valid = it.step_is_valid ? 1 : 0;
+                e.step_is_successful = it.step_is_successful ? 1 : 0;
+                e.cost = it.cost;
+                e.cost_change = it.cost_change;
+                e.gradient_max_norm = it.gradient_max_norm;
+                e.step_norm = it.step_norm;
+                e.relative_decrease = it.relative_decrease;
+                e.trust_region_radius = it.trust_region_radius;
+                out[n] = e;
+            }
+            ++n;
+        }
+    return n;
 }
 
 // loss function known-answer access: kind 0 trivial, 1 huber, 2 cauchy; scaled by weight

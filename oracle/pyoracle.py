@@ -50,6 +50,10 @@ def load():
     lib.oracle_num_procs.restype = C.c_int
     lib.oracle_functor_jacobian.argtypes = [C.c_int, dp, dp, dp, dp, dp, dp, dp]
     lib.oracle_ba_first_step.argtypes = [C.POINTER(_ffi.BaWindow), C.POINTER(_ffi.BaOptions), ip, dp, dp, dp, dp]
+    dpp = C.POINTER(dp)
+    lib.oracle_ba_step_probe.argtypes = [C.POINTER(_ffi.BaWindow), C.POINTER(_ffi.BaOptions), dpp, ip, dp, dp, dp, dp, dp, ip, dp]
+    lib.oracle_ba_problem_cost_at.argtypes = [C.POINTER(_ffi.BaWindow), C.POINTER(_ffi.BaOptions), dpp, dp]
+    lib.oracle_last_iteration_log.argtypes = [C.c_int32, C.POINTER(_ffi.BaIteration)]
     _lib = lib
     return lib
 
@@ -169,6 +173,64 @@ def first_step(window, opts):
     if rc != 0:
         raise RuntimeError("oracle_ba_first_step rc=%d" % rc)
     return {"J": J, "r": r, "D": D, "y": y, "num_e": int(sizes[2])}
+
+
+COL_LANDMARK, COL_POSE, COL_PLANE_DIR, COL_PLANE_DIST = range(4)  # kinds of step_probe()["col"][:, 0]
+
+
+def _at4(window, at):
+    """The parameter arrays of `at` (a window of the shapes of `window`) as the double*[4] of oracle_ba_step_probe, and what keeps
+    them alive."""
+    assert at.kf_pose.shape == window.kf_pose.shape and at.lm_pos.shape == window.lm_pos.shape
+    keep = [np.ascontiguousarray(a, np.float64) for a in (at.kf_pose, at.kf_plane_dir, at.kf_plane_dist, at.lm_pos)]
+    return (_ffi.c_double_p * 4)(*[_dp(a) for a in keep]), keep
+
+
+def step_probe(window, opts, at=None):
+    """first_step() with what tests/lm_step_common.py needs on top: "scale" (the Jacobi column scale J is scaled by; ones with
+    jacobi_scaling off), "col" (int32 [n, 3]: kind COL_*, index in the window, tangent component of the parameter block behind every
+    column), "cost" (at the point of the probe, without the fixed cost) and "fixed_cost".  at: None, or a window holding the
+    parameters the step is taken from - the problem itself (ground-plane rows, the scale regulariser's constant) is the one built at
+    `window`, as in a solve that started there.  None when the solve takes no step."""
+    lib = load()
+    s = window.as_struct()
+    at4, keep = (None, None) if at is None else _at4(window, at)
+    sizes = np.zeros(3, np.int32)
+    sp = sizes.ctypes.data_as(_ffi.c_int32_p)
+    rc = lib.oracle_ba_step_probe(C.byref(s), C.byref(opts), at4, sp, None, None, None, None, None, None, None)
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise RuntimeError("oracle_ba_step_probe rc=%d" % rc)
+    m, n = int(sizes[0]), int(sizes[1])
+    J, r, D, y, scale, col, costs = np.zeros((m, n)), np.zeros(m), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((n, 3), np.int32), np.zeros(2)
+    rc = lib.oracle_ba_step_probe(C.byref(s), C.byref(opts), at4, sp, _dp(J), _dp(r), _dp(D), _dp(y), _dp(scale), col.ctypes.data_as(_ffi.c_int32_p), _dp(costs))
+    if rc != 0:
+        raise RuntimeError("oracle_ba_step_probe rc=%d" % rc)
+    return {"J": J, "r": r, "D": D, "y": y, "num_e": int(sizes[2]), "scale": scale, "col": col, "cost": float(costs[0]), "fixed_cost": float(costs[1])}
+
+
+def problem_cost_at(window, opts, at):
+    """Total cost (with loss) of the solve() problem built at `window`, evaluated at the parameters of the window `at`."""
+    lib = load()
+    s = window.as_struct()
+    at4, keep = _at4(window, at)
+    cost = np.zeros(1)
+    rc = lib.oracle_ba_problem_cost_at(C.byref(s), C.byref(opts), at4, _dp(cost))
+    if rc != 0:
+        raise RuntimeError("oracle_ba_problem_cost_at rc=%d" % rc)
+    return float(cost[0])
+
+
+def last_iteration_log():
+    """The iteration table of the last solve() / adjust_pose_only() on this thread as an array of _ffi.iteration_dtype(): the rows
+    ORACLE_VERBOSE prints, at full precision."""
+    lib = load()
+    n = lib.oracle_last_iteration_log(0, None)
+    out = np.zeros(n, _ffi.iteration_dtype())
+    if n:
+        lib.oracle_last_iteration_log(n, out.ctypes.data_as(C.POINTER(_ffi.BaIteration)))
+    return out
 
 
 def loss(kind, a, weight, s):
