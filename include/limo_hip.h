@@ -649,6 +649,51 @@ int limo_depth_last_reasons(limo_ctx* ctx, int32_t frame, uint8_t* reasons, size
 int limo_depth_set_timing(limo_ctx* ctx, int32_t on);
 int limo_depth_last_kernel_ms(limo_ctx* ctx, double* ms4);
 
+/* --- five-point motion prior ------------------------------------------------------------------------- */
+/*
+ * Relative camera motion from image correspondences alone: the prior the node computes for every frame that arrives
+ * without a tf prior (helpers::getMotionUnscaled called at keyframe_bundle_adjustment_ros_tool/src/mono_lidar/
+ * mono_lidar.cpp:156-162 and mono_standalone.cpp:112).  Replaces calcMotion5Point,
+ * src/commons/general_helpers.hpp:103-140: cv::findEssentialMat(points1, points0, focal, pp, RANSAC, probability, 2.0)
+ * (:122) + cv::recoverPose (:129); the mean-flow gate (:112-121) and getMotionUnscaled's scaling and frame changes
+ * (:209-231) stay with the caller (limo_amd/kba/five_point.hpp:matches / meanFlow / motionUnscaled).
+ * Runs on the device (limo_amd/csrc/five_point.hip): every minimal sample of a round at once, every model scored against
+ * every match, the adaptive stopping rule applied afterwards on the host.  The result is the one of the host estimator
+ * limo_amd/kba/five_point.hpp:estimateMotion for the same inputs and seed, BIT FOR BIT (limo_amd/csrc/five_point_core.hpp).
+ */
+typedef struct limo_five_point_params {
+    double probability;    /* 0.999  general_helpers.hpp:221 (getMotionUnscaled's argument to calcMotion5Point) */
+    double threshold_px;   /* 2.0    general_helpers.hpp:122 (last argument of cv::findEssentialMat) */
+    int32_t max_samples;   /* 1000   cv::findEssentialMat's RANSAC iteration cap; 1 .. 16384 */
+    int32_t chunk;         /* 0 = the library's schedule; > 0: samples per device round.  No result depends on it */
+} limo_five_point_params;
+typedef struct limo_five_point_motion { /* five_point::Motion; what calcMotion5Point hands back through cv::recoverPose (:129-139) */
+    int32_t ok, inliers, in_front, samples;
+    double E[9], R[9], t[3];            /* row-major; x_b = R x_a + t, |t| = 1; b^T E a = 0 */
+} limo_five_point_motion;
+typedef struct limo_five_point_frame { /* helpers::getMatches' two point lists (general_helpers.hpp:35-74) */
+    int32_t n;
+    const double* pts_a;               /* [n*2] pixels */
+    const double* pts_b;               /* [n*2] pixels */
+    uint64_t seed;                     /* of the sample picks (OpenCV draws from its global RNG) */
+} limo_five_point_frame;
+/* the values calcMotion5Point is called with (general_helpers.hpp:122, :221) */
+void limo_five_point_default_params(limo_five_point_params* out);
+/*
+ * One pair of frames (general_helpers.hpp:122-129).  n < 5, or no sample giving a model: LIMO_OK with ok = 0, R = I,
+ * t = (0, 0, 1).  NULL pointers, n < 0, a non-finite coordinate or an out-of-range parameter: LIMO_ERR_INVALID.
+ * inlier: the mask cv::findEssentialMat returns (:122 `mask`), one byte per match, or NULL.
+ */
+int limo_five_point(limo_ctx* ctx, const limo_five_point_frame* frame, double focal, double cx, double cy,
+                    const limo_five_point_params* params, limo_five_point_motion* out, uint8_t* inlier /* [n] or NULL */);
+/*
+ * The same for n_frames pairs of one camera (an offline replay; N sequences in lock step): the frame is a grid dimension of
+ * every kernel, a frame whose stopping rule has fired takes no part in later rounds.  out[i] holds the bytes of frame i's
+ * single call.  limo_last_error names the frame an error belongs to.
+ */
+int limo_five_point_batch(limo_ctx* ctx, int32_t n_frames, const limo_five_point_frame* frames, double focal, double cx, double cy,
+                          const limo_five_point_params* params, limo_five_point_motion* out /* [n_frames] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,32 @@ class DepthFrame(C.Structure):  # struct limo_depth_frame (pointers as integers:
 DEPTH_DEVICE_POINTERS = 1
 
 
+class FivePointParams(C.Structure):  # struct limo_five_point_params
+    _fields_ = [("probability", C.c_double), ("threshold_px", C.c_double), ("max_samples", C.c_int32), ("chunk", C.c_int32)]
+
+
+class FivePointMotion(C.Structure):  # struct limo_five_point_motion
+    _fields_ = [
+        ("ok", C.c_int32),
+        ("inliers", C.c_int32),
+        ("in_front", C.c_int32),
+        ("samples", C.c_int32),
+        ("E", C.c_double * 9),
+        ("R", C.c_double * 9),
+        ("t", C.c_double * 3),
+    ]
+
+    def as_dict(self):
+        import numpy as np
+
+        return {"ok": bool(self.ok), "inliers": int(self.inliers), "in_front": int(self.in_front), "samples": int(self.samples),
+                "E": np.array(self.E[:]).reshape(3, 3), "R": np.array(self.R[:]).reshape(3, 3), "t": np.array(self.t[:])}
+
+
+class FivePointFrame(C.Structure):  # struct limo_five_point_frame
+    _fields_ = [("n", C.c_int32), ("pts_a", c_double_p), ("pts_b", c_double_p), ("seed", C.c_uint64)]
+
+
 class DepthParams(C.Structure):  # struct limo_depth_params
     _fields_ = [
         ("pixelarea_search_width", C.c_int32),
@@ -313,6 +339,9 @@ ABI_SYMBOLS = [
     "limo_depth_last_reasons",
     "limo_depth_set_timing",
     "limo_depth_last_kernel_ms",
+    "limo_five_point_default_params",
+    "limo_five_point",
+    "limo_five_point_batch",
 ]
 
 _lib = None
@@ -434,5 +463,12 @@ def load():
     lib.limo_depth_last_ground_plane.argtypes = [vp, C.c_int32, c_double_p, c_int32_p]
     if not older:
         lib.limo_depth_last_reasons.argtypes = [vp, C.c_int32, c_uint8_p, C.c_size_t]
+    if hasattr(lib, "limo_five_point"):  # (added without an ABI bump, as the ones above)
+        lib.limo_five_point_default_params.argtypes = [C.POINTER(FivePointParams)]
+        lib.limo_five_point_default_params.restype = None
+        lib.limo_five_point.argtypes = [vp, C.POINTER(FivePointFrame), C.c_double, C.c_double, C.c_double, C.POINTER(FivePointParams),
+                                        C.POINTER(FivePointMotion), c_uint8_p]
+        lib.limo_five_point_batch.argtypes = [vp, C.c_int32, C.POINTER(FivePointFrame), C.c_double, C.c_double, C.c_double, C.POINTER(FivePointParams),
+                                              C.POINTER(FivePointMotion)]
     _lib = lib
     return lib

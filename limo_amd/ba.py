@@ -148,6 +148,54 @@ class Context:
         _check(rc, self.ptr, "limo_landmark_init")
         return pos, ok
 
+    def five_point_params(self, probability=None, threshold_px=None, max_samples=None, chunk=None):
+        """limo_five_point_default_params, with the given fields replaced."""
+        p = _ffi.FivePointParams()
+        self.lib.limo_five_point_default_params(C.byref(p))
+        for name, v in (("probability", probability), ("threshold_px", threshold_px), ("max_samples", max_samples), ("chunk", chunk)):
+            if v is not None:
+                setattr(p, name, v)
+        return p
+
+    def five_point(self, pts_a, pts_b, focal, cx, cy, seed=1, params=None, with_mask=False):
+        """limo_five_point: relative motion x_b = R x_a + t from matches pts_a / pts_b ([n, 2] pixels).  Returns the Motion as a
+        dict (plus "raw": the struct's bytes, "inlier": the mask with with_mask)."""
+        a = np.ascontiguousarray(pts_a, np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(pts_b, np.float64).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("five_point: %d points in a, %d in b" % (len(a), len(b)))
+        fr = _ffi.FivePointFrame(len(a), a.ctypes.data_as(_ffi.c_double_p), b.ctypes.data_as(_ffi.c_double_p), int(seed))
+        p = params if params is not None else self.five_point_params()
+        m = _ffi.FivePointMotion()
+        mask = np.zeros(max(1, len(a)), np.uint8) if with_mask else None
+        rc = self.lib.limo_five_point(self.ptr, C.byref(fr), float(focal), float(cx), float(cy), C.byref(p), C.byref(m),
+                                      mask.ctypes.data_as(_ffi.c_uint8_p) if with_mask else None)
+        _check(rc, self.ptr, "limo_five_point")
+        out = m.as_dict()
+        out["raw"] = bytes(m)
+        if with_mask:
+            out["inlier"] = mask[: len(a)]
+        return out
+
+    def five_point_batch(self, frames, focal, cx, cy, params=None):
+        """limo_five_point_batch: frames = [(pts_a, pts_b, seed), ...]; one dict per frame, as five_point returns it."""
+        keep = [(np.ascontiguousarray(a, np.float64).reshape(-1, 2), np.ascontiguousarray(b, np.float64).reshape(-1, 2), int(s)) for a, b, s in frames]
+        n = len(keep)
+        arr = (_ffi.FivePointFrame * max(1, n))()
+        for i, (a, b, s) in enumerate(keep):
+            if len(a) != len(b):
+                raise ValueError("five_point_batch: frame %d: %d points in a, %d in b" % (i, len(a), len(b)))
+            arr[i] = _ffi.FivePointFrame(len(a), a.ctypes.data_as(_ffi.c_double_p), b.ctypes.data_as(_ffi.c_double_p), s)
+        p = params if params is not None else self.five_point_params()
+        ms = (_ffi.FivePointMotion * max(1, n))()
+        _check(self.lib.limo_five_point_batch(self.ptr, n, arr, float(focal), float(cx), float(cy), C.byref(p), ms), self.ptr, "limo_five_point_batch")
+        out = []
+        for i in range(n):
+            d = ms[i].as_dict()
+            d["raw"] = bytes(ms[i])
+            out.append(d)
+        return out
+
     def adjust_pose_only(self, window, prior, opts):
         s = window.as_struct()
         rep = _ffi.BaReport()

@@ -34,6 +34,11 @@
 #include "keyframe_selector.hpp"
 #include "landmark_selection_voxel.hpp"
 
+// The five-point entry points are weak references: the driver also links against backends that serve the C-ABI without them (the
+// test backends tests/cpp/oracle_abi.cpp and emu_pipeline.cpp) - there the addresses are null and the host estimator runs.
+#pragma weak limo_five_point
+#pragma weak limo_five_point_default_params
+
 namespace keyframe_bundle_adjustment {
 
 struct StreamParams {
@@ -54,6 +59,11 @@ struct StreamParams {
     // RANSAC in the frame loop; adjustPoseOnly refines either against the fixed landmarks).
     enum class MotionPrior { ConstantVelocity, FivePoint };
     MotionPrior motion_prior = MotionPrior::ConstantVelocity;
+    // Where the five-point estimate of MotionPrior::FivePoint is computed: limo_five_point (the device: every minimal sample of a round
+    // at once) where the library behind the C-ABI has it, else - and always with `false` - five_point::estimateMotion on the host.
+    // The two give the same Motion bit for bit, hence the same pose rows.  The default follows the measurement of BASELINE.md §4.16
+    // (at a third of the matches wrong the device call is 3 - 5 x the host's).
+    bool five_point_on_device = false;
     // landmark selection (keyframe_ba_monolid.launch:36-38; wiring of MonoLidar::reconfigureRequest, mono_lidar.cpp:396-430)
     unsigned max_number_landmarks_near_bin = 200, max_number_landmarks_middle_bin = 200, max_number_landmarks_far_bin = 100;
     double roi_middle = 15., roi_far = 40.;                            // :405-408
@@ -88,6 +98,8 @@ public:
         // selection, window cut + labels; and of sec_pose_only / sec_solve the share spent inside the C-ABI calls
         double sec_keyframe = 0., sec_select = 0., sec_window = 0., sec_abi_pose_only = 0., sec_abi_solve = 0., sec_depth_history = 0.;
         double sec_depth_thread = 0.;  // time the depth thread worked (beside the calling thread: not part of sec_total)
+        int five_point_calls = 0, five_point_device_calls = 0;  // estimates of the five-point prior, and how many of them limo_five_point made
+        double sec_five_point = 0.;
     };
 
     StreamDriver(const StreamParams& p, Camera::Ptr camera, const EigenPose& T_camera_lidar) : p_(p), camera_(camera), T_cam_lidar_(T_camera_lidar) {
@@ -130,6 +142,7 @@ public:
             worker_.join();
         }
         if (ctx_) limo_ctx_destroy(ctx_);
+        if (five_point_ctx_) limo_ctx_destroy(five_point_ctx_);
     }
     StreamDriver(const StreamDriver&) = delete;
     StreamDriver& operator=(const StreamDriver&) = delete;
@@ -332,8 +345,7 @@ private:
     // (prior_speed while there is only one keyframe), applied to the last keyframe's pose.
     EigenPose fivePointPrior(TimestampNSec stamp, const Tracklets& tracklets) {
         const Keyframe& last_kf = ba_.getKeyframe();
-        EigenPose motion = five_point::motionUnscaled(camera_->focal_length, camera_->principal_point, stamp, last_kf.timestamp_, tracklets,
-                                                      camera_->getEigenPose(), p_.prior_speed, (uint64_t)stamp, &last_five_point_);
+        EigenPose motion = motionUnscaled(stamp, last_kf.timestamp_, tracklets, (uint64_t)stamp);
         const auto kfs = ba_.getSortedActiveKeyframePtrs();
         if (kfs.size() > 1) {
             const Keyframe &k1 = *kfs[kfs.size() - 1], &k0 = *kfs[kfs.size() - 2];
@@ -342,6 +354,70 @@ private:
             for (int i = 0; i < 3; ++i) motion.t[i] = motion.t[i] / std::max(0.0001, n) * speed * (convert(stamp) - convert(k1.timestamp_));
         }
         return motion * (kfs.empty() ? last_kf.getEigenPose() : kfs.back()->getEigenPose());
+    }
+    // five_point::motionUnscaled (five_point.hpp:650-671, helpers::getMotionUnscaled, general_helpers.hpp:209-231) with the estimator of
+    // its middle line chosen by fivePointOnDevice(): matches, the mean-flow gate, the scaling by speed x dt and the frame changes are
+    // its statements, written here once for both estimators.
+    EigenPose motionUnscaled(TimestampNSec stamp_cur, TimestampNSec stamp_last_kf, const Tracklets& tracklets, uint64_t seed) {
+        std::vector<Vector2d> last_points, cur_points;
+        five_point::matches(tracklets, stamp_last_kf, stamp_cur, {23, 24, 25, 26}, last_points, cur_points);
+        EigenPose cam_t0_t1 = EigenPose::Identity();  // camera at t0 <- camera at t1
+        cam_t0_t1.t[2] = 1.;
+        if (!last_points.empty() && five_point::meanFlow(last_points, cur_points) >= 5.) {
+            // calcMotion5Point: findEssentialMat(points1 = cur, points0 = last), recoverPose(E, cur, last): x_last = R x_cur + t
+            const auto t0 = std::chrono::steady_clock::now();
+            const bool on_device = fivePointOnDevice();
+            const five_point::Motion m = on_device ? estimateMotionOnDevice(cur_points, last_points, seed)
+                                                   : five_point::estimateMotion(cur_points, last_points, camera_->focal_length, camera_->principal_point,
+                                                                                0.999, 2.0, seed);
+            ++stats_.five_point_calls;
+            stats_.five_point_device_calls += on_device;
+            stats_.sec_five_point += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            last_five_point_ = m;
+            if (m.ok) {
+                for (int i = 0; i < 9; ++i) cam_t0_t1.R[i] = m.R[i];
+                for (int i = 0; i < 3; ++i) cam_t0_t1.t[i] = m.t[i];
+            }
+        } else if (!last_points.empty()) {
+            cam_t0_t1.t[2] = 0.;  // "not enough flow": calcMotion5Point zeroes the translation before it returns (:118-121)
+        }
+        const double dt = convert(stamp_cur) - convert(stamp_last_kf);
+        const double n = std::sqrt(cam_t0_t1.t[0] * cam_t0_t1.t[0] + cam_t0_t1.t[1] * cam_t0_t1.t[1] + cam_t0_t1.t[2] * cam_t0_t1.t[2]);
+        for (int i = 0; i < 3; ++i) cam_t0_t1.t[i] = cam_t0_t1.t[i] / std::max(0.0001, n) * p_.prior_speed * dt;
+        const EigenPose T_camera_vehicle = camera_->getEigenPose();
+        return T_camera_vehicle.inverse() * cam_t0_t1.inverse() * T_camera_vehicle;
+    }
+    bool fivePointOnDevice() const { return p_.five_point_on_device && &limo_five_point != nullptr && &limo_five_point_default_params != nullptr; }
+    // limo_five_point with the arguments motionUnscaled gives estimateMotion (probability 0.999, 2 px, 1000 samples).  It runs on a
+    // context of its own: the driver's first context belongs to the depth thread while a frame is in flight (DepthAhead::Thread).
+    five_point::Motion estimateMotionOnDevice(const std::vector<Vector2d>& pts_a, const std::vector<Vector2d>& pts_b, uint64_t seed) {
+        static_assert(sizeof(Vector2d) == 2 * sizeof(double), "Vector2d is two doubles: a point list is the [n*2] array of the C-ABI");
+        if (!five_point_ctx_) {
+            int dev = 0;
+            if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
+            if (limo_ctx_create(dev, &five_point_ctx_) != LIMO_OK) throw std::runtime_error("StreamDriver: no HIP device (limo_ctx_create)");
+        }
+        limo_five_point_params prm;
+        limo_five_point_default_params(&prm);
+        limo_five_point_frame fr;
+        fr.n = (int32_t)std::min(pts_a.size(), pts_b.size());
+        fr.pts_a = fr.n ? &pts_a[0].v[0] : nullptr;
+        fr.pts_b = fr.n ? &pts_b[0].v[0] : nullptr;
+        fr.seed = seed;
+        limo_five_point_motion mo;
+        const int rc = limo_five_point(five_point_ctx_, &fr, camera_->focal_length, camera_->principal_point[0], camera_->principal_point[1], &prm, &mo, nullptr);
+        if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_five_point: ") + limo_last_error(five_point_ctx_));
+        five_point::Motion m;
+        m.ok = mo.ok != 0;
+        m.inliers = mo.inliers;
+        m.in_front = mo.in_front;
+        m.samples = mo.samples;
+        for (int i = 0; i < 9; ++i) {
+            m.E[i] = mo.E[i];
+            m.R[i] = mo.R[i];
+        }
+        for (int i = 0; i < 3; ++i) m.t[i] = mo.t[i];
+        return m;
     }
     // constant velocity from the last two poses; before there are two: straight ahead at prior_speed
     EigenPose constantVelocityPrior(TimestampNSec stamp) const {
@@ -525,6 +601,7 @@ private:
     BundleAdjusterKeyframes ba_;
     KeyframeSelector selector_;
     limo_ctx* ctx_ = nullptr;
+    limo_ctx* five_point_ctx_ = nullptr;  // of estimateMotionOnDevice, made at its first call
     limo_depth_params depth_params_;
     struct History {  // the depths this driver assigned to a track in the last frames it was seen in (ring, newest at head - 1)
         static constexpr int kDepth = 16;
