@@ -8,9 +8,12 @@
 //   limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--poses out.txt] [--gt-poses gt.txt]
 //               [--dump-velodyne DIR] [--velodyne DIR] [--no-depth] [--depth-ahead thread|stream|none] [--quiet]
 //               [--depth-params FILE] [--progress] [--five-point-prior [--five-point-host | --five-point-device]]
+//               [--select-host | --select-device]
 // --five-point-prior takes the frame's motion prior from the five-point algorithm, as the reference's node does without a tf prior
 // (mono_lidar.cpp:157-186), instead of constant velocity; --five-point-host / --five-point-device say where its RANSAC runs (the host
 // estimator five_point.hpp, or limo_five_point) instead of StreamParams' default.  Same pose rows, bit for bit.
+// --select-host / --select-device say where solve() selects its landmarks (the host selector, or limo_landmark_select) instead of
+// StreamParams' default.  Same pose rows, bit for bit.
 // --progress prints Ceres' per-iteration table for every adjustPoseOnly and solve to stdout, as the reference's node does
 // (BundleAdjusterKeyframes::minimizer_progress_to_stdout_); the pose rows do not change.
 // --depth-params reads the depth estimator's settings from a mono_lidar_fusion_parameters.yaml (the file the reference
@@ -46,6 +49,7 @@ int main(int argc, char** argv) {
     std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path;
     bool use_depth = true, quiet = false, five_point_prior = false, progress = false;
     int five_point_where = -1;  // 0: host, 1: device, -1: StreamParams' default
+    int select_where = -1;      // landmark selection of solve(): the same
     StreamParams::DepthAhead depth_ahead = StreamParams::DepthAhead::Thread;
     double min_flow = -1., time_between_keyframes = -1.;
     for (int i = 1; i < argc; ++i) {
@@ -78,8 +82,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--five-point-prior")) five_point_prior = true;  // the node's prior without tf (mono_lidar.cpp:157-186)
         else if (!std::strcmp(argv[i], "--five-point-host")) five_point_where = 0;
         else if (!std::strcmp(argv[i], "--five-point-device")) five_point_where = 1;
+        else if (!std::strcmp(argv[i], "--select-host")) select_where = 0;
+        else if (!std::strcmp(argv[i], "--select-device")) select_where = 1;
         else {
-            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--five-point-host] [--five-point-device] [--quiet] [--progress]\n");
+            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--five-point-host] [--five-point-device] [--select-host] [--select-device] [--quiet] [--progress]\n");
             return 2;
         }
     }
@@ -95,6 +101,7 @@ int main(int argc, char** argv) {
     if (time_between_keyframes > 0.) sp.time_between_keyframes_sec = time_between_keyframes;
     if (five_point_prior) sp.motion_prior = StreamParams::MotionPrior::FivePoint;
     if (five_point_where >= 0) sp.five_point_on_device = five_point_where == 1;
+    if (select_where >= 0) sp.landmark_selection_on_device = select_where == 1;
     sp.solver_time_sec = -1.;  // no wall-clock cap: the drive is reproducible
     sp.image_width = (int)world.W;
     sp.image_height = (int)world.H;
@@ -277,6 +284,7 @@ int main(int argc, char** argv) {
     std::printf("frames %d\nfps %.3f\nate_rmse %.6f\nate_max %.6f\ndepth_fraction %.4f\nkeyframes %d\nsolves %d\nsolves_on_non_keyframes %d\ndepth_prefetched %d\n", n_frames,
                 n_frames / sec_pipeline, ate, worst, (double)st.features_with_depth / std::max(1, st.features), st.keyframes, st.solves, st.solves_on_non_keyframes,
                 st.depth_prefetched);
+    std::printf("select_device_calls %d\n", driver.adjuster().device_selections_);
     if (five_point_prior)
         std::printf("limo_stream: five-point prior: %d estimates (%d on the device), %.3f ms each\nfive_point_calls %d\nfive_point_device_calls %d\nfive_point_ms %.4f\n",
                     st.five_point_calls, st.five_point_device_calls, st.five_point_calls ? 1e3 * st.sec_five_point / st.five_point_calls : 0., st.five_point_calls,

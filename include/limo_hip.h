@@ -694,6 +694,64 @@ int limo_five_point(limo_ctx* ctx, const limo_five_point_frame* frame, double fo
 int limo_five_point_batch(limo_ctx* ctx, int32_t n_frames, const limo_five_point_frame* frames, double focal, double cx, double cy,
                           const limo_five_point_params* params, limo_five_point_motion* out /* [n_frames] */);
 
+/* --- landmark selection ------------------------------------------------------------------------------ */
+/*
+ * Which landmarks of the window enter the next solve: the selector the node runs in front of every solve()
+ * (keyframe_bundle_adjustment/src/bundle_adjuster_keyframes.cpp:118 cheirality rejection, always first; the schemes
+ * keyframe_bundle_adjustment_ros_tool/src/mono_lidar/mono_lidar.cpp:396-430 adds: voxel sparsification :396-408 and "depth
+ * assurance" :409-426; the union is LandmarkSelector::select, include/keyframe_bundle_adjustment/landmark_selector.hpp:118-253).
+ *   rejection       landmark_selection_scheme_cheirality.cpp:22-60: dropped iff behind some camera that measured it
+ *   sparsification  landmark_selection_scheme_voxel.cpp:116-233: frame of the newest keyframe, z in [-20, 100], distance to the driven
+ *                   path (far / middle pipe), one representative per voxel, budgets: near = largest image flow, middle = hashed
+ *                   rank seeded with the newest stamp, far = seen by the most keyframes; ties go to the smaller id
+ *   must-haves      landmark_selection_scheme_add_depth.cpp:16-76: per entry the `count` landmarks that pass the predicate, are
+ *                   measured in the active keyframe of time rank frame_index and have the smallest key (then id)
+ * Runs on the device (limo_amd/csrc/landmark_select.hip).  The bytes are those of the host classes limo_amd/kba/landmark_selector.hpp
+ * + landmark_selection_voxel.hpp compiled with floating-point contraction off (limo_amd/csrc/landmark_select_core.hpp states the
+ * arithmetic once for both).  Outlier removal and the "unselected" bookkeeping of LandmarkSelector stay with the caller.
+ * A pool whose voxel indices leave (-2^20, 2^20) (e.g. a voxel size of 1e-5 m) is finished on the host with the same statement.
+ * Limits: n_kf <= 64, n_cam <= 8 (LIMO_ERR_INVALID beyond; the shim then uses its host selector).
+ */
+enum { LIMO_SELECT_HAS_DEPTH = 0, LIMO_SELECT_IS_GROUND = 1 };           /* predicate: Landmark::has_measured_depth / is_ground_plane */
+enum { LIMO_SELECT_KEY_MEASURED_DEPTH = 0, LIMO_SELECT_KEY_RANGE = 1 };  /* key, smallest win: (double)m.d / (double)(float)|T_kf p| (mono_lidar.cpp:412-423) */
+typedef struct limo_select_add { int32_t frame_index, count, predicate, key; } limo_select_add;
+typedef struct limo_select_params {
+    double voxel_size_xyz[3];      /* 0.5 0.5 0.3  mono_lidar.cpp:404 */
+    double roi_far, roi_middle;    /* 40, 15       mono_lidar.cpp:405-408 */
+    uint32_t max_near, max_middle, max_far;   /* 200 200 100  keyframe_ba_monolid.launch:36-38 */
+    int32_t n_add; const limo_select_add* add;
+    int32_t sort_capacity;         /* 0 = the library's; > 0: landmarks the on-chip sort takes before the global-memory path.  No result depends on it */
+} limo_select_params;
+typedef struct limo_select_pool {  /* active keyframes ascending keyframe id, candidate landmarks ascending id */
+    int32_t n_kf, n_cam, n_lm, n_obs;
+    const double* kf_pose;         /* [n_kf*7]   as limo_ba_window */
+    const uint64_t* kf_stamp;      /* [n_kf]     */
+    const double* cam;             /* [n_cam*10] as limo_ba_window */
+    const uint64_t* lm_id;         /* [n_lm] strictly ascending */
+    const double* lm_pos;          /* [n_lm*3]   */
+    const uint8_t* lm_has_depth;   /* [n_lm]     */
+    const uint8_t* lm_is_ground;   /* [n_lm]     */
+    const int32_t *obs_kf, *obs_lm, *obs_cam; const float *obs_u, *obs_v, *obs_d;  /* [n_obs] any order, each (kf, lm, cam) once */
+} limo_select_pool;
+/* the node's wiring (mono_lidar.cpp:404-408, launch :36-38); its must-have list needs the window size: n_add = 0 here */
+void limo_select_default_params(limo_select_params* out);
+/*
+ * out[i]: low two bits 0 = not chosen by the voxel scheme, 1 = near, 2 = middle, 3 = far field; | 4 = must-have; 8 = rejected by
+ * cheirality (nothing else set).  Selected iff out[i] & 7.  n_kf == 0 or n_lm == 0: LIMO_OK, out all zero.  Non-finite landmark
+ * positions are no error (the comparisons decide, as on the host).  LIMO_ERR_INVALID (limo_last_error names pool and field), before
+ * anything is launched: NULL pointers, negative sizes, an index out of range, lm_id not strictly ascending, a (kf, lm, cam) twice,
+ * a non-positive voxel size or roi, an unknown predicate or key, n_kf > 64, n_cam > 8.
+ */
+int limo_landmark_select(limo_ctx* ctx, const limo_select_pool* pool, const limo_select_params* params, uint8_t* out /* [n_lm] */);
+/* The same for n_pools windows (N sequences in lock step): the pool is a grid dimension of every kernel, three launches whatever
+ * n_pools is.  out[p] holds the bytes of pool p's single call. */
+int limo_landmark_select_batch(limo_ctx* ctx, int32_t n_pools, const limo_select_pool* pools, const limo_select_params* params,
+                               uint8_t* const* out);
+/* Measurement aid (scripts/bench_landmark_select.py): with timing on, HIP events are recorded around the three kernels of a call;
+ * limo_select_last_kernel_ms returns the device time of the last call in milliseconds. */
+int limo_select_set_timing(limo_ctx* ctx, int32_t on);
+int limo_select_last_kernel_ms(limo_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,67 @@ class FivePointFrame(C.Structure):  # struct limo_five_point_frame
     _fields_ = [("n", C.c_int32), ("pts_a", c_double_p), ("pts_b", c_double_p), ("seed", C.c_uint64)]
 
 
+SELECT_HAS_DEPTH, SELECT_IS_GROUND = 0, 1  # predicate of a must-have entry
+SELECT_KEY_MEASURED_DEPTH, SELECT_KEY_RANGE = 0, 1  # its key (the smallest win)
+
+
+class SelectAdd(C.Structure):  # struct limo_select_add
+    _fields_ = [("frame_index", C.c_int32), ("count", C.c_int32), ("predicate", C.c_int32), ("key", C.c_int32)]
+
+
+class SelectParams(C.Structure):  # struct limo_select_params
+    _fields_ = [
+        ("voxel_size_xyz", C.c_double * 3),
+        ("roi_far", C.c_double),
+        ("roi_middle", C.c_double),
+        ("max_near", C.c_uint32),
+        ("max_middle", C.c_uint32),
+        ("max_far", C.c_uint32),
+        ("n_add", C.c_int32),
+        ("add", C.POINTER(SelectAdd)),
+        ("sort_capacity", C.c_int32),
+    ]
+
+
+class SelectPool(C.Structure):  # struct limo_select_pool
+    _fields_ = [
+        ("n_kf", C.c_int32),
+        ("n_cam", C.c_int32),
+        ("n_lm", C.c_int32),
+        ("n_obs", C.c_int32),
+        ("kf_pose", c_double_p),
+        ("kf_stamp", C.POINTER(C.c_uint64)),
+        ("cam", c_double_p),
+        ("lm_id", C.POINTER(C.c_uint64)),
+        ("lm_pos", c_double_p),
+        ("lm_has_depth", c_uint8_p),
+        ("lm_is_ground", c_uint8_p),
+        ("obs_kf", c_int32_p),
+        ("obs_lm", c_int32_p),
+        ("obs_cam", c_int32_p),
+        ("obs_u", C.POINTER(C.c_float)),
+        ("obs_v", C.POINTER(C.c_float)),
+        ("obs_d", C.POINTER(C.c_float)),
+    ]
+
+
+def select_pool(pool):
+    """struct limo_select_pool from a dict of arrays (kf_pose [n_kf,7], kf_stamp, cam [n_cam,10], lm_id, lm_pos [n_lm,3], lm_has_depth,
+    lm_is_ground, obs_kf, obs_lm, obs_cam, obs_u, obs_v, obs_d).  Returns (struct, the arrays it points into - keep them alive)."""
+    import numpy as np
+
+    spec = (("kf_pose", np.float64, c_double_p), ("kf_stamp", np.uint64, C.POINTER(C.c_uint64)), ("cam", np.float64, c_double_p),
+            ("lm_id", np.uint64, C.POINTER(C.c_uint64)), ("lm_pos", np.float64, c_double_p), ("lm_has_depth", np.uint8, c_uint8_p),
+            ("lm_is_ground", np.uint8, c_uint8_p), ("obs_kf", np.int32, c_int32_p), ("obs_lm", np.int32, c_int32_p), ("obs_cam", np.int32, c_int32_p),
+            ("obs_u", np.float32, C.POINTER(C.c_float)), ("obs_v", np.float32, C.POINTER(C.c_float)), ("obs_d", np.float32, C.POINTER(C.c_float)))
+    keep = {k: np.ascontiguousarray(pool[k], t) for k, t, _ in spec}
+    w = SelectPool()
+    w.n_kf, w.n_cam, w.n_lm, w.n_obs = len(keep["kf_stamp"]), keep["cam"].size // 10, len(keep["lm_id"]), len(keep["obs_kf"])
+    for k, _, ct in spec:
+        setattr(w, k, keep[k].ctypes.data_as(ct))
+    return w, keep
+
+
 class DepthParams(C.Structure):  # struct limo_depth_params
     _fields_ = [
         ("pixelarea_search_width", C.c_int32),
@@ -342,6 +403,11 @@ ABI_SYMBOLS = [
     "limo_five_point_default_params",
     "limo_five_point",
     "limo_five_point_batch",
+    "limo_select_default_params",
+    "limo_landmark_select",
+    "limo_landmark_select_batch",
+    "limo_select_set_timing",
+    "limo_select_last_kernel_ms",
 ]
 
 _lib = None
@@ -470,5 +536,12 @@ def load():
                                         C.POINTER(FivePointMotion), c_uint8_p]
         lib.limo_five_point_batch.argtypes = [vp, C.c_int32, C.POINTER(FivePointFrame), C.c_double, C.c_double, C.c_double, C.POINTER(FivePointParams),
                                               C.POINTER(FivePointMotion)]
+    if hasattr(lib, "limo_landmark_select"):  # (added without an ABI bump, as the ones above)
+        lib.limo_select_default_params.argtypes = [C.POINTER(SelectParams)]
+        lib.limo_select_default_params.restype = None
+        lib.limo_landmark_select.argtypes = [vp, C.POINTER(SelectPool), C.POINTER(SelectParams), c_uint8_p]
+        lib.limo_landmark_select_batch.argtypes = [vp, C.c_int32, C.POINTER(SelectPool), C.POINTER(SelectParams), C.POINTER(c_uint8_p)]
+        lib.limo_select_set_timing.argtypes = [vp, C.c_int32]
+        lib.limo_select_last_kernel_ms.argtypes = [vp, c_double_p]
     _lib = lib
     return lib

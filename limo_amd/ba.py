@@ -196,6 +196,55 @@ class Context:
             out.append(d)
         return out
 
+    def select_params(self, add=(), **fields):
+        """limo_select_default_params with the given fields replaced (voxel_size_xyz, roi_far, roi_middle, max_near, max_middle, max_far,
+        sort_capacity); add = [(frame_index, count, predicate, key), ...] is the must-have list."""
+        p = _ffi.SelectParams()
+        self.lib.limo_select_default_params(C.byref(p))
+        for name, v in fields.items():
+            if name == "voxel_size_xyz":
+                p.voxel_size_xyz[:] = [float(x) for x in v]
+            else:
+                setattr(p, name, v)
+        if len(add):
+            p._add_keep = (_ffi.SelectAdd * len(add))(*[_ffi.SelectAdd(*(int(x) for x in a)) for a in add])  # (kept alive with the struct)
+            p.add, p.n_add = p._add_keep, len(add)
+        return p
+
+    def landmark_select(self, pool, params=None):
+        """limo_landmark_select: pool = dict of arrays (see _ffi.select_pool).  Returns one byte per landmark: low two bits 0 not chosen
+        by the voxel scheme / 1 near / 2 middle / 3 far, | 4 must-have, 8 rejected by cheirality; selected iff byte & 7."""
+        w, keep = _ffi.select_pool(pool)
+        p = params if params is not None else self.select_params()
+        out = np.zeros(max(1, w.n_lm), np.uint8)
+        _check(self.lib.limo_landmark_select(self.ptr, C.byref(w), C.byref(p), out.ctypes.data_as(_ffi.c_uint8_p)), self.ptr, "limo_landmark_select")
+        del keep
+        return out[: w.n_lm]
+
+    def landmark_select_batch(self, pools, params=None):
+        """limo_landmark_select_batch: one byte array per pool, the bytes of its single call."""
+        n = len(pools)
+        arr = (_ffi.SelectPool * max(1, n))()
+        keep, outs = [], []
+        for i, pool in enumerate(pools):
+            arr[i], k = _ffi.select_pool(pool)
+            keep.append(k)
+            outs.append(np.zeros(max(1, arr[i].n_lm), np.uint8))
+        ptrs = (_ffi.c_uint8_p * max(1, n))(*[o.ctypes.data_as(_ffi.c_uint8_p) for o in outs])
+        p = params if params is not None else self.select_params()
+        _check(self.lib.limo_landmark_select_batch(self.ptr, n, arr, C.byref(p), ptrs), self.ptr, "limo_landmark_select_batch")
+        del keep
+        return [o[: arr[i].n_lm] for i, o in enumerate(outs)]
+
+    def select_kernel_ms(self):
+        """limo_select_last_kernel_ms: device time of the kernels of the last landmark_select[_batch] call (after set_select_timing(True))."""
+        ms = C.c_double(0.0)
+        _check(self.lib.limo_select_last_kernel_ms(self.ptr, C.byref(ms)), self.ptr, "limo_select_last_kernel_ms")
+        return ms.value
+
+    def set_select_timing(self, on):
+        _check(self.lib.limo_select_set_timing(self.ptr, int(bool(on))), self.ptr, "limo_select_set_timing")
+
     def adjust_pose_only(self, window, prior, opts):
         s = window.as_struct()
         rep = _ffi.BaReport()

@@ -62,6 +62,9 @@ struct limo_ctx {
     std::vector<limo_ba_iteration> last_log;
     std::vector<int32_t> last_log_n;
     std::vector<size_t> last_log_off;
+    // limo_select_set_timing: HIP events around the kernels of limo_landmark_select[_batch]; the device time of the last call
+    bool select_timing = false;
+    double select_last_ms = 0.;
     // Device blocks released by finished batches, kept for the next one (size class = power of two): a single-window
     // call (limo_ba_solve, limo_ba_adjust_pose_only) would otherwise spend more time in hipMalloc / hipFree than in
     // its kernels.  At most kPoolPerClass blocks per class are kept; everything is freed with the context.

@@ -203,6 +203,7 @@ limo_ctx* BundleAdjusterKeyframes::context() {
 // test backends tests/cpp/oracle_abi.cpp and emu_pipeline.cpp) - there the addresses are null and the shim behaves as "no log".
 #pragma weak limo_ctx_set_iteration_log
 #pragma weak limo_ctx_last_iteration_log
+#pragma weak limo_landmark_select  // (tests/cpp/oracle_abi.cpp and emu_pipeline.cpp have no device selection: solve() then selects on the host)
 
 void BundleAdjusterKeyframes::setIterationLog(limo_ctx* ctx) {
     last_iterations_.clear();
@@ -669,6 +670,68 @@ std::string report_string(const limo_ba_report& r, const char* what) {
 
 }  // namespace
 
+void BundleAdjusterKeyframes::setDeviceSelection(const limo_select_params* params) {
+    device_selection_ = params != nullptr;
+    if (!params) return;
+    select_params_ = *params;
+    select_add_.assign(params->add, params->add + (params->add ? std::max(0, params->n_add) : 0));
+    select_params_.n_add = (int32_t)select_add_.size();
+}
+
+// The active landmarks minus the selector's outliers as a limo_select_pool (keyframes and observations by the merge passes of Flat),
+// limo_landmark_select, and the result handed to the selector.  false: the call did not return LIMO_OK - nothing has changed.
+bool BundleAdjusterKeyframes::selectOnDevice(const LandmarkView& active_lms, const std::map<KeyframeId, Keyframe::ConstPtr>& active_kfs) {
+    Flat F;
+    std::vector<uint64_t> kf_stamp, lm_id;
+    // (a camera is a column of the flattened table by its object, a camera of the host schemes by its id: the same thing as long as
+    // every id names one object in the window)
+    std::map<CameraId, const Camera*> by_id;
+    std::map<const Camera*, CameraId> by_object;
+    for (const auto& id : active_keyframe_ids_) {
+        Keyframe& kf = *keyframes_.at(id);
+        F.add_keyframe(kf);
+        kf_stamp.push_back(kf.timestamp_);
+        for (const auto& c : kf.cameras_) {
+            if (!by_id.emplace(c.first, c.second.get()).first->second || by_id.at(c.first) != c.second.get()) return false;
+            if (by_object.emplace(c.second.get(), c.first).first->second != c.first) return false;
+        }
+    }
+    if (F.kfs.size() != active_kfs.size()) return false;  // (select() would be given other keyframes than the window holds)
+    std::vector<std::pair<LandmarkId, int>> lm_index;
+    std::vector<uint8_t> has_depth;
+    const std::set<LandmarkId>& outliers = landmark_selector_->getOutliers();
+    auto io = outliers.cbegin();
+    F.reserve_landmarks(active_lms.size());
+    for (const auto& el : active_lms) {
+        while (io != outliers.cend() && *io < el.first) ++io;
+        if (io != outliers.cend() && *io == el.first) continue;
+        lm_index.push_back({el.first, (int)lm_id.size()});
+        lm_id.push_back(el.first);
+        for (int i = 0; i < 3; ++i) F.lm_pos.push_back(el.second->pos[i]);
+        F.lm_gp.push_back(el.second->is_ground_plane ? 1 : 0);
+        has_depth.push_back(el.second->has_measured_depth ? 1 : 0);
+    }
+    for (size_t k = 0; k < F.kfs.size(); ++k) F.add_observations((int)k, *F.kfs[k], lm_index);
+    limo_select_pool w;
+    w.n_kf = (int32_t)F.kfs.size(), w.n_cam = (int32_t)F.cam_index.size(), w.n_lm = (int32_t)lm_id.size(), w.n_obs = (int32_t)F.obs_kf.size();
+    w.kf_pose = F.kf_pose.data(), w.kf_stamp = kf_stamp.data(), w.cam = F.cam.data();
+    w.lm_id = lm_id.data(), w.lm_pos = F.lm_pos.data(), w.lm_has_depth = has_depth.data(), w.lm_is_ground = F.lm_gp.data();
+    w.obs_kf = F.obs_kf.data(), w.obs_lm = F.obs_lm.data(), w.obs_cam = F.obs_cam.data();
+    w.obs_u = F.u.data(), w.obs_v = F.v.data(), w.obs_d = F.d.data();
+    select_params_.add = select_add_.empty() ? nullptr : select_add_.data();
+    std::vector<uint8_t> out(lm_id.size() + 1);
+    if (limo_landmark_select(context(), &w, &select_params_, out.data()) != LIMO_OK) return false;
+    using Category = LandmarkCategorizatonInterface::Category;
+    std::vector<LandmarkId> selection;
+    std::vector<std::pair<LandmarkId, Category>> categories;
+    for (size_t i = 0; i < lm_id.size(); ++i) {
+        if ((out[i] & 7) != 0) selection.push_back(lm_id[i]);
+        if ((out[i] & 3) != 0) categories.push_back({(LandmarkId)lm_id[i], (out[i] & 3) == 1 ? Category::NearField : (out[i] & 3) == 2 ? Category::MiddleField : Category::FarField});
+    }
+    landmark_selector_->acceptSelection(active_lms, active_kfs, selection, std::move(categories));
+    return true;
+}
+
 std::string BundleAdjusterKeyframes::solve() {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
     if (keyframes_.size() < 3) throw NotEnoughKeyframesException(keyframes_.size(), 3);
@@ -687,7 +750,12 @@ std::string BundleAdjusterKeyframes::solve() {
     }
     const auto active_kfs = getActiveKeyframeConstPtrs();
     const auto t_s0b = clk::now();
-    selected_landmark_ids_ = landmark_selector_->select(active_lms, active_kfs);
+    if (device_selection_ && &limo_landmark_select != nullptr && selectOnDevice(active_lms, active_kfs)) {
+        selected_landmark_ids_ = landmark_selector_->getLastSelection();
+        ++device_selections_;
+    } else {
+        selected_landmark_ids_ = landmark_selector_->select(active_lms, active_kfs);
+    }
     const auto t_s1 = clk::now();
 
     Flat F;

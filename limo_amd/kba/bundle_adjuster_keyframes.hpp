@@ -84,6 +84,15 @@ public:
         return last_iterations_;
     }
 
+    // Where solve() selects its landmarks (not in the reference).  With parameters set, solve() flattens the active landmarks, minus the
+    // selector's outliers, into a limo_select_pool and calls limo_landmark_select (the device form of cheirality + voxel + add-depth as
+    // StreamDriver wires them: include/limo_hip.h); the selector takes the result over (LandmarkSelector::acceptSelection), so outliers,
+    // categories and the unselected bookkeeping go on as before.  landmark_selector_->select runs instead whenever the call returns
+    // anything but LIMO_OK (a window above 64 keyframes or 8 cameras, a backend without the symbol).  The parameters must say what the
+    // schemes added to landmark_selector_ say: the two paths then give the same selection.  nullptr turns it off; off is the default.
+    void setDeviceSelection(const limo_select_params* params);
+    int device_selections_ = 0;  // solve() calls whose selection limo_landmark_select made
+
 public:
     std::map<KeyframeId, Keyframe::Ptr> keyframes_;
     std::map<LandmarkId, Landmark::Ptr> landmarks_;
@@ -108,6 +117,10 @@ private:
     void setIterationLog(limo_ctx* ctx);      // before the solve: the context's switch follows minimizer_progress_to_stdout_
     void collectIterations(limo_ctx* ctx, const char* what);  // behind it: last_iterations_ and the table
     std::vector<limo_ba_iteration> last_iterations_;
+    bool selectOnDevice(const LandmarkView& active_lms, const std::map<KeyframeId, Keyframe::ConstPtr>& active_kfs);
+    bool device_selection_ = false;
+    limo_select_params select_params_{};
+    std::vector<limo_select_add> select_add_;
     limo_ctx* ctx_ = nullptr;
     double solver_time_sec;
 };

@@ -222,37 +222,7 @@ public:
             }
         }
         const auto t4 = clk::now();
-        if (!kfs.empty()) {
-            // markUnselected(id, newest) for every landmark that was not selected, then clean(newest - 10 s)
-            // (landmark_selector.hpp:226-252) - as ONE merge pass: landmarks, selection and the bookkeeping entries are all sorted
-            // by id; entries last marked more than ten seconds ago are dropped on the way.  (Two std::maps with a lookup each per
-            // unselected landmark and a queue of the marks were 0.5 ms of every solve().)
-            TimestampNSec newest = 0;
-            for (const auto& kf : kfs) newest = std::max(newest, kf.second->timestamp_);
-            const TimestampNSec ten_s = convert(TimestampSec(10.));
-            const TimestampNSec oldest = newest > ten_s ? newest - ten_s : 0;
-            std::vector<Unselected> merged;
-            merged.reserve(unselected_.size() + landmarks.size());
-            auto is = selection.cbegin();
-            auto iu = unselected_.cbegin();
-            for (const auto& lm : landmarks) {
-                while (is != selection.cend() && *is < lm.first) ++is;
-                if (is != selection.cend() && *is == lm.first) continue;
-                const LandmarkId id = lm.first;
-                for (; iu != unselected_.cend() && iu->id < id; ++iu)
-                    if (!(iu->last_seen < oldest)) merged.push_back(*iu);
-                if (iu != unselected_.cend() && iu->id == id) {
-                    merged.push_back({id, iu->count + 1, newest});
-                    ++iu;
-                } else {
-                    merged.push_back({id, 1u, newest});
-                }
-            }
-            for (; iu != unselected_.cend(); ++iu)
-                if (!(iu->last_seen < oldest)) merged.push_back(*iu);
-            unselected_.swap(merged);
-            unselected_stale_ = true;
-        }
+        noteUnselected(landmarks, kfs, selection);
         last_selected_lms_ = selection;
         if (trace) {
             auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -260,6 +230,20 @@ public:
                          us(t0, t1), us(t1, t2), us(t2, t3), us(t3, t4), us(t4, clk::now()), unselected_.size());
         }
         return selection;
+    }
+
+    // A selection that was made elsewhere (limo_landmark_select on the device, BundleAdjusterKeyframes::setDeviceSelection - not in the
+    // reference): what the tail of select() does with its own - the selection and the categories are remembered, the landmarks of
+    // `landmarks` (the active ones, outliers included, as select() is given them) that are not in it are marked unselected.  Afterwards
+    // nothing in this class tells which path selected.  `selection` and `categories` are sorted by id.
+    void acceptSelection(const LandmarkView& landmarks, const KeyframeMap& kfs, const std::vector<LandmarkId>& selection,
+                         std::vector<std::pair<LandmarkId, LandmarkCategorizatonInterface::Category>> categories) {
+        std::set<LandmarkId> sel;
+        for (const auto& id : selection) sel.insert(sel.end(), id);
+        categories_.swap(categories);
+        categories_stale_ = true;
+        noteUnselected(landmarks, kfs, sel);
+        last_selected_lms_.swap(sel);
     }
 
     void markUnselected(LandmarkId lm_id, TimestampNSec last_time_seen) {
@@ -305,6 +289,41 @@ public:
     std::set<LandmarkId> outlier_ids_;
 
 private:
+    // the bookkeeping behind a selection (landmark_selector.hpp:226-252)
+    void noteUnselected(const LandmarkView& landmarks, const KeyframeMap& kfs, const std::set<LandmarkId>& selection) {
+        if (!kfs.empty()) {
+            // markUnselected(id, newest) for every landmark that was not selected, then clean(newest - 10 s)
+            // (landmark_selector.hpp:226-252) - as ONE merge pass: landmarks, selection and the bookkeeping entries are all sorted
+            // by id; entries last marked more than ten seconds ago are dropped on the way.  (Two std::maps with a lookup each per
+            // unselected landmark and a queue of the marks were 0.5 ms of every solve().)
+            TimestampNSec newest = 0;
+            for (const auto& kf : kfs) newest = std::max(newest, kf.second->timestamp_);
+            const TimestampNSec ten_s = convert(TimestampSec(10.));
+            const TimestampNSec oldest = newest > ten_s ? newest - ten_s : 0;
+            std::vector<Unselected> merged;
+            merged.reserve(unselected_.size() + landmarks.size());
+            auto is = selection.cbegin();
+            auto iu = unselected_.cbegin();
+            for (const auto& lm : landmarks) {
+                while (is != selection.cend() && *is < lm.first) ++is;
+                if (is != selection.cend() && *is == lm.first) continue;
+                const LandmarkId id = lm.first;
+                for (; iu != unselected_.cend() && iu->id < id; ++iu)
+                    if (!(iu->last_seen < oldest)) merged.push_back(*iu);
+                if (iu != unselected_.cend() && iu->id == id) {
+                    merged.push_back({id, iu->count + 1, newest});
+                    ++iu;
+                } else {
+                    merged.push_back({id, 1u, newest});
+                }
+            }
+            for (; iu != unselected_.cend(); ++iu)
+                if (!(iu->last_seen < oldest)) merged.push_back(*iu);
+            unselected_.swap(merged);
+            unselected_stale_ = true;
+        }
+    }
+
     template <typename S>
     std::vector<LandmarkId> run(const std::shared_ptr<const S>& scheme, const LandmarkView& lms, const KeyframeMap& kfs) {
         auto cat = std::dynamic_pointer_cast<const LandmarkCategorizatonInterface>(scheme);

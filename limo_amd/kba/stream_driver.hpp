@@ -64,6 +64,10 @@ struct StreamParams {
     // The two give the same Motion bit for bit, hence the same pose rows.  The default follows the measurement of BASELINE.md §4.16
     // (at a third of the matches wrong the device call is 3 - 5 x the host's).
     bool five_point_on_device = false;
+    // Where solve() selects its landmarks: limo_landmark_select (the device; BundleAdjusterKeyframes::setDeviceSelection, with the values
+    // below) where the library behind the C-ABI has it, else - and always with `false` - the host selector.  The two give the same
+    // selection, hence the same pose rows.  The default follows the measurement of BASELINE.md §4.17.
+    bool landmark_selection_on_device = false;
     // landmark selection (keyframe_ba_monolid.launch:36-38; wiring of MonoLidar::reconfigureRequest, mono_lidar.cpp:396-430)
     unsigned max_number_landmarks_near_bin = 200, max_number_landmarks_middle_bin = 200, max_number_landmarks_far_bin = 100;
     double roi_middle = 15., roi_far = 40.;                            // :405-408
@@ -123,6 +127,18 @@ public:
             ap.params_per_keyframe.push_back(std::make_tuple(i, p.add_ground_landmarks_per_keyframe, [](const Landmark::ConstPtr& lm) { return lm->is_ground_plane; },
                                                              [](const Measurement&, const Vector3d& local) { return (float)local.norm(); }));
         ba_.landmark_selector_->addScheme(LandmarkSelectionSchemeAddDepth::createConst(ap));
+        if (p.landmark_selection_on_device) {  // the same wiring as limo_select_params (the host schemes above stay: they take over when the call is refused)
+            limo_select_params sp{};
+            for (int i = 0; i < 3; ++i) sp.voxel_size_xyz[i] = p.voxel_size_xyz[i];
+            sp.roi_far = p.roi_far, sp.roi_middle = p.roi_middle;
+            sp.max_near = p.max_number_landmarks_near_bin, sp.max_middle = p.max_number_landmarks_middle_bin, sp.max_far = p.max_number_landmarks_far_bin;
+            std::vector<limo_select_add> add;
+            if (p.add_depth_landmarks_newest > 0) add.push_back({0, p.add_depth_landmarks_newest, LIMO_SELECT_HAS_DEPTH, LIMO_SELECT_KEY_MEASURED_DEPTH});
+            for (int i = 0; i < p.max_size_optimization_window && p.add_ground_landmarks_per_keyframe > 0; ++i)
+                add.push_back({i, p.add_ground_landmarks_per_keyframe, LIMO_SELECT_IS_GROUND, LIMO_SELECT_KEY_RANGE});
+            sp.n_add = (int32_t)add.size(), sp.add = add.data();
+            ba_.setDeviceSelection(&sp);
+        }
         int dev = 0;  // LIMO_DEVICE: the GPU of this sequence (one process per GPU and sequence, scripts/stream_replicas.py)
         if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
         if (limo_ctx_create(dev, &ctx_) != LIMO_OK) throw std::runtime_error("StreamDriver: no HIP device (limo_ctx_create)");

@@ -1,0 +1,136 @@
+// landmark_select_ref.cpp — the checker of limo_landmark_select: Keyframe / Landmark / Camera objects built from a flat pool, and
+// LandmarkSelector with cheirality + voxel + add-depth exactly as StreamDriver wires them (limo_amd/kba/stream_driver.hpp:110-125,
+// bundle_adjuster_keyframes.cpp:184), behind a C entry point with the C-ABI's output byte.  Built by tests/landmark_select_common.py
+// with -ffp-contract=off.  test_landmark_select_core.cpp includes this file.
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <vector>
+
+#include "../../include/limo_hip.h"
+#include "../../limo_amd/csrc/kba_math.hpp"
+#include "../../limo_amd/kba/landmark_selection_voxel.hpp"
+
+namespace keyframe_bundle_adjustment {
+// the conversions of limo_amd/kba/bundle_adjuster_keyframes.cpp:108-153 (that file needs a C-ABI backend to link; the checker has none)
+Pose convert(const EigenPose& p) {  // (only ever handed the identity rotation here: Camera's constructor; the pose is assigned afterwards)
+    return Pose{{1., 0., 0., 0., p.t[0], p.t[1], p.t[2]}};
+}
+EigenPose convert(const Pose& pose) {
+    EigenPose p;
+    kba::quat_R(pose.data(), p.R);
+    p.t[0] = pose[4];
+    p.t[1] = pose[5];
+    p.t[2] = pose[6];
+    return p;
+}
+TimestampSec convert(const TimestampNSec& ts) { return static_cast<TimestampSec>(ts * 1e-09); }
+TimestampNSec convert(const TimestampSec& ts) { return static_cast<TimestampNSec>(ts * 1e09); }
+}  // namespace keyframe_bundle_adjustment
+
+namespace kb = keyframe_bundle_adjustment;
+
+// out[n_lm]: the byte limo_landmark_select documents.  seconds (may be NULL): wall time of LandmarkSelector::select alone.
+// flags & 1: no cheirality scheme (the voxel scheme alone, as tests/cpp/test_kba_shim.cpp's LandmarkSelector.voxel wires it).
+// returns 0, or -1 bad arguments, -2 the selection is not (categorised) U (must-haves), -3 acceptSelection leaves another state than select
+extern "C" int landmark_select_ref(const limo_select_pool* w, const limo_select_params* prm, uint8_t* out, double* seconds, int32_t flags) {
+    if (!w || !prm || (w->n_lm > 0 && !out)) return -1;
+    std::map<kb::KeyframeId, kb::Keyframe::ConstPtr> kfs;
+    std::vector<std::shared_ptr<kb::Keyframe>> kf_obj(w->n_kf);
+    for (int k = 0; k < w->n_kf; ++k) {
+        auto kf = std::make_shared<kb::Keyframe>();
+        kf->timestamp_ = w->kf_stamp[k];
+        for (int i = 0; i < 7; ++i) kf->pose_[i] = w->kf_pose[7 * k + i];
+        for (int c = 0; c < w->n_cam; ++c) {
+            const double* cm = w->cam + 10 * c;
+            auto cam = std::make_shared<kb::Camera>(cm[0], kb::Vector2d(cm[1], cm[2]), kb::EigenPose::Identity());
+            for (int i = 0; i < 7; ++i) cam->pose_camera_vehicle[i] = cm[3 + i];
+            kf->cameras_[(kb::CameraId)c] = cam;
+        }
+        kf->is_active_ = true;
+        kf_obj[k] = kf;
+    }
+    for (int o = 0; o < w->n_obs; ++o)
+        kf_obj[w->obs_kf[o]]->measurements_[w->lm_id[w->obs_lm[o]]][(kb::CameraId)w->obs_cam[o]] = kb::Measurement(w->obs_u[o], w->obs_v[o], w->obs_d[o]);
+    for (int k = 0; k < w->n_kf; ++k) kfs[(kb::KeyframeId)k] = kf_obj[k];
+    kb::LandmarkView view;
+    for (int i = 0; i < w->n_lm; ++i) {
+        auto lm = std::make_shared<kb::Landmark>(kb::Vector3d(w->lm_pos + 3 * i), w->lm_has_depth[i] != 0);
+        lm->is_ground_plane = w->lm_is_ground[i] != 0;
+        view.push_back({(kb::LandmarkId)w->lm_id[i], lm});
+    }
+    kb::LandmarkSparsificationSchemeVoxel::Parameters vp;
+    vp.max_num_landmarks_near = prm->max_near;
+    vp.max_num_landmarks_middle = prm->max_middle;
+    vp.max_num_landmarks_far = prm->max_far;
+    vp.voxel_size_xyz = {{prm->voxel_size_xyz[0], prm->voxel_size_xyz[1], prm->voxel_size_xyz[2]}};
+    vp.roi_far_xyz = {{prm->roi_far, prm->roi_far, prm->roi_far}};
+    vp.roi_middle_xyz = {{prm->roi_middle, prm->roi_middle, prm->roi_middle}};
+    kb::LandmarkSelectionSchemeAddDepth::Parameters ap;
+    for (int e = 0; e < prm->n_add; ++e) {
+        const limo_select_add& a = prm->add[e];
+        kb::LandmarkSelectionSchemeAddDepth::Comparator pred;
+        kb::LandmarkSelectionSchemeAddDepth::Sorter key;
+        if (a.predicate == LIMO_SELECT_HAS_DEPTH)
+            pred = [](const kb::Landmark::ConstPtr& lm) { return lm->has_measured_depth; };
+        else
+            pred = [](const kb::Landmark::ConstPtr& lm) { return lm->is_ground_plane; };
+        if (a.key == LIMO_SELECT_KEY_MEASURED_DEPTH)
+            key = [](const kb::Measurement& m, const kb::Vector3d&) { return m.d; };
+        else
+            key = [](const kb::Measurement&, const kb::Vector3d& local) { return (float)local.norm(); };
+        ap.params_per_keyframe.push_back(std::make_tuple(a.frame_index, a.count, pred, key));
+    }
+    kb::LandmarkSelector selector;
+    if (!(flags & 1)) selector.addScheme(kb::LandmarkRejectionSchemeCheirality::create());
+    selector.addScheme(kb::LandmarkSparsificationSchemeVoxel::createConst(vp));
+    auto add_scheme = kb::LandmarkSelectionSchemeAddDepth::createConst(ap);
+    selector.addScheme(add_scheme);
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::set<kb::LandmarkId> selection = selector.select(view, kfs);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    // the parts: what cheirality kept, the must-haves from that pool, the categories of the voxel scheme
+    std::vector<kb::LandmarkId> kept;
+    if (flags & 1)
+        for (const auto& e : view) kept.push_back(e.first);
+    else
+        kept = kb::LandmarkRejectionSchemeCheirality::kept(view, kfs);
+    kb::LandmarkView pool;
+    for (const auto& e : view)
+        if (std::binary_search(kept.begin(), kept.end(), e.first)) pool.push_back(e);
+    const std::vector<kb::LandmarkId> must = add_scheme->getSelectionSorted(pool, kfs);
+    const auto& cats = selector.getLandmarkCategories();
+    size_t n_sel = 0;
+    for (int i = 0; i < w->n_lm; ++i) {
+        const kb::LandmarkId id = w->lm_id[i];
+        uint8_t b = 0;
+        if (!std::binary_search(kept.begin(), kept.end(), id)) {
+            b = 8;
+        } else {
+            const auto it = cats.find(id);
+            if (it != cats.end()) b = it->second == kb::LandmarkCategorizatonInterface::Category::NearField ? 1 : it->second == kb::LandmarkCategorizatonInterface::Category::MiddleField ? 2 : 3;
+            if (std::binary_search(must.begin(), must.end(), id)) b |= 4;
+        }
+        out[i] = b;
+        if ((b & 7) != 0) {
+            ++n_sel;
+            if (!selection.count(id)) return -2;
+        }
+    }
+    if (n_sel != selection.size()) return -2;
+    // LandmarkSelector::acceptSelection (what the shim does with the device's bytes): a second selector handed the selection and the
+    // categories read back from `out` ends in the state of the one that selected
+    kb::LandmarkSelector other;
+    std::vector<kb::LandmarkId> sel_ids;
+    std::vector<std::pair<kb::LandmarkId, kb::LandmarkCategorizatonInterface::Category>> sel_cats;
+    for (int i = 0; i < w->n_lm; ++i) {
+        using Category = kb::LandmarkCategorizatonInterface::Category;
+        if ((out[i] & 7) != 0) sel_ids.push_back(w->lm_id[i]);
+        if ((out[i] & 3) != 0) sel_cats.push_back({(kb::LandmarkId)w->lm_id[i], (out[i] & 3) == 1 ? Category::NearField : (out[i] & 3) == 2 ? Category::MiddleField : Category::FarField});
+    }
+    other.acceptSelection(view, kfs, sel_ids, sel_cats);
+    if (other.getLastSelection() != selector.getLastSelection() || other.getLandmarkCategories() != selector.getLandmarkCategories() ||
+        other.getUnselectedLandmarks() != selector.getUnselectedLandmarks())
+        return -3;
+    return 0;
+}
