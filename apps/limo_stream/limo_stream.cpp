@@ -8,7 +8,13 @@
 //   limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--poses out.txt] [--gt-poses gt.txt]
 //               [--dump-velodyne DIR] [--velodyne DIR] [--no-depth] [--depth-ahead thread|stream|none] [--quiet]
 //               [--depth-params FILE] [--progress] [--five-point-prior [--five-point-host | --five-point-device]]
-//               [--select-host | --select-device]
+//               [--select-host | --select-device] [--sequences N [--frames-step K] [--stagger S] [--host-threads T]]
+// --sequences N drives N sequences in lock step through ONE LockstepDriver (limo_amd/kba/lockstep_driver.hpp: one batched device call
+// per stage and tick for all of them) instead of one StreamDriver: sequence i is the synthetic drive of --seed (seed + i), runs
+// frames - i*K frames (--frames-step K) and gets its first frame at tick i*S (--stagger S); --host-threads T sets the threads of the
+// per-sequence host phases (default min(N, 16)).  --poses P writes P.0 .. P.(N-1), each the bytes the single drive of that seed and frame
+// count writes; the last line printed is one JSON object: sequences, aggregate frames_per_s, per stage the batched calls, what they
+// carried and the single-call fallbacks, per-sequence ATE.  No --progress, --velodyne, --dump-velodyne in this form; --depth-ahead is ignored (a tick assigns its own depths).
 // --five-point-prior takes the frame's motion prior from the five-point algorithm, as the reference's node does without a tf prior
 // (mono_lidar.cpp:157-186), instead of constant velocity; --five-point-host / --five-point-device say where its RANSAC runs (the host
 // estimator five_point.hpp, or limo_five_point) instead of StreamParams' default.  Same pose rows, bit for bit.
@@ -34,108 +40,43 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
+#include <optional>
 #include <string>
 
 #include "../../limo_amd/kba/depth_params_yaml.hpp"
 #include "../../limo_amd/kba/kitti_io.hpp"
+#include "../../limo_amd/kba/lockstep_driver.hpp"
 #include "../../limo_amd/kba/stream_driver.hpp"
 #include "synth_world.hpp"
 
 using namespace keyframe_bundle_adjustment;
 
-int main(int argc, char** argv) {
-    int n_frames = 200, n_feat = 1500, n_az = 2000, window = 5, misannounce_every = 0;
-    uint64_t seed = 7;
-    std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path;
-    bool use_depth = true, quiet = false, five_point_prior = false, progress = false;
-    int five_point_where = -1;  // 0: host, 1: device, -1: StreamParams' default
-    int select_where = -1;      // landmark selection of solve(): the same
-    StreamParams::DepthAhead depth_ahead = StreamParams::DepthAhead::Thread;
-    double min_flow = -1., time_between_keyframes = -1.;
-    for (int i = 1; i < argc; ++i) {
-        auto arg = [&](const char* name) { return !std::strcmp(argv[i], name) && i + 1 < argc; };
-        if (arg("--frames")) n_frames = std::atoi(argv[++i]);
-        else if (arg("--features")) n_feat = std::atoi(argv[++i]);
-        else if (arg("--az")) n_az = std::atoi(argv[++i]);
-        else if (arg("--seed")) seed = std::strtoull(argv[++i], nullptr, 10);
-        else if (arg("--window")) window = std::atoi(argv[++i]);
-        else if (arg("--misannounce-every")) misannounce_every = std::atoi(argv[++i]);  // (testing aid, see the frame loop)
-        else if (arg("--min-flow")) min_flow = std::atof(argv[++i]);
-        else if (arg("--time-between-keyframes")) time_between_keyframes = std::atof(argv[++i]);
-        else if (arg("--poses")) poses_path = argv[++i];
-        else if (arg("--gt-poses")) gt_path = argv[++i];
-        else if (arg("--dump-velodyne")) dump_dir = argv[++i];
-        else if (arg("--velodyne")) replay_dir = argv[++i];
-        else if (arg("--depth-params")) depth_params_path = argv[++i];
-        else if (!std::strcmp(argv[i], "--no-depth")) use_depth = false;
-        else if (!std::strcmp(argv[i], "--no-prefetch")) depth_ahead = StreamParams::DepthAhead::None;
-        else if (arg("--depth-ahead")) {
-            const std::string m = argv[++i];
-            if (m != "thread" && m != "stream" && m != "none") {
-                std::fprintf(stderr, "limo_stream: --depth-ahead thread|stream|none\n");
-                return 2;
-            }
-            depth_ahead = m == "thread" ? StreamParams::DepthAhead::Thread : m == "stream" ? StreamParams::DepthAhead::Stream : StreamParams::DepthAhead::None;
-        }
-        else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
-        else if (!std::strcmp(argv[i], "--progress")) progress = true;
-        else if (!std::strcmp(argv[i], "--five-point-prior")) five_point_prior = true;  // the node's prior without tf (mono_lidar.cpp:157-186)
-        else if (!std::strcmp(argv[i], "--five-point-host")) five_point_where = 0;
-        else if (!std::strcmp(argv[i], "--five-point-device")) five_point_where = 1;
-        else if (!std::strcmp(argv[i], "--select-host")) select_where = 0;
-        else if (!std::strcmp(argv[i], "--select-device")) select_where = 1;
-        else {
-            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--five-point-host] [--five-point-device] [--select-host] [--select-device] [--quiet] [--progress]\n");
-            return 2;
-        }
-    }
-    using clk = std::chrono::steady_clock;
-    synth_world::World world(n_frames, seed);
-    world.n_az = n_az;
-    Camera::Ptr cam = std::make_shared<Camera>(world.f, Vector2d(world.cx, world.cy), world.cam_veh);
-    StreamParams sp;
-    sp.max_size_optimization_window = window;
-    sp.assign_depth = use_depth;
-    sp.depth_ahead = depth_ahead;
-    if (min_flow >= 0.) sp.min_median_flow = min_flow;
-    if (time_between_keyframes > 0.) sp.time_between_keyframes_sec = time_between_keyframes;
-    if (five_point_prior) sp.motion_prior = StreamParams::MotionPrior::FivePoint;
-    if (five_point_where >= 0) sp.five_point_on_device = five_point_where == 1;
-    if (select_where >= 0) sp.landmark_selection_on_device = select_where == 1;
-    sp.solver_time_sec = -1.;  // no wall-clock cap: the drive is reproducible
-    sp.image_width = (int)world.W;
-    sp.image_height = (int)world.H;
-    sp.height_over_ground = synth_world::World::kHeightOverGround;
-    StreamDriver driver(sp, cam, world.cam_lidar);
-    driver.adjuster().minimizer_progress_to_stdout_ = progress;
-    if (!depth_params_path.empty()) {
-        std::string err;
-        if (!depth_params_yaml::load(depth_params_path, &driver.depthParams(), &err)) {
-            std::fprintf(stderr, "limo_stream: --depth-params %s\n", err.c_str());
-            return 2;
-        }
-    }
+namespace {
 
-    std::mt19937_64 rng(seed * 31 + 1);
+// a frame as the sensor drivers deliver it: the tracker's message and the sweep in a page-locked buffer
+struct Frame {
+    Tracklets ts;
+    float* scan = nullptr;
+    size_t cap = 0, n_pts = 0, n_tracks = 0;
+};
+
+// the sensors of one synthetic drive: frame t's sweep and the tracker's message for it (frames are asked for in order)
+struct Synth {
+    Synth(synth_world::World& w, uint64_t seed, int n_feat_, const std::string& replay, const std::string& dump)
+            : world(w), rng(seed * 31 + 1), n_feat(n_feat_), replay_dir(replay), dump_dir(dump) {}
+    synth_world::World& world;
+    std::mt19937_64 rng;
+    int n_feat;
+    std::string replay_dir, dump_dir;
     const int history = 10;
     std::vector<int> live;  // landmarks tracked in the previous frame
     std::map<int, int> first_seen;
     std::vector<float> cloud;
     std::vector<uint8_t> cloud_ground;
-    double sec_synth = 0., sec_pipeline = 0.;
     size_t n_points = 0;
-    // a frame as the sensor drivers deliver it: the tracker's message and the sweep in a page-locked buffer
-    struct Frame {
-        Tracklets ts;
-        float* scan = nullptr;
-        size_t cap = 0, n_pts = 0, n_tracks = 0;
-    } frames[2];
-    auto release = [&]() {
-        driver.cancelPrefetch();
-        for (Frame& fr : frames)
-            if (fr.scan) limo_host_free(fr.scan);
-    };
-    auto synthesize = [&](int t, Frame& out) -> bool {
+
+    bool frame(int t, Frame& out) {
         world.sweep(t, cloud, cloud_ground);  // (also labels the returns that hit the ground: the features' class labels come from it)
         if (!replay_dir.empty()) {
             std::vector<float> scan;
@@ -199,7 +140,253 @@ int main(int argc, char** argv) {
         out.n_tracks = ts.tracks.size();
         out.ts = std::move(ts);
         return true;
+    }
+};
+
+// --sequences N: N synthetic drives (seed, seed + 1, ...) through one LockstepDriver.  Sequence i runs frames - i * frames_step frames and
+// gets its first frame at tick i * stagger; every tick hands the driver the frames that are due.  The input of a tick is synthesised
+// before the tick and timed apart from it, as in the single drive.
+struct LockstepOptions {
+    int sequences = 0, frames_step = 0, stagger = 0, host_threads = 0, perturb_rig = -1;
+    int n_frames = 200, n_feat = 1500, n_az = 2000;
+    uint64_t seed = 7;
+    std::string poses_path, gt_path, depth_params_path;
+    bool quiet = false;
+};
+
+int run_lockstep(const LockstepOptions& o, StreamParams sp) {
+    using clk = std::chrono::steady_clock;
+    const int N = o.sequences;
+    struct Drive {
+        std::unique_ptr<synth_world::World> world;
+        std::unique_ptr<Synth> synth;
+        Camera::Ptr cam;
+        Frame frame;
+        int n_frames = 0, first_tick = 0;
     };
+    std::vector<Drive> drives(N);
+    std::vector<LockstepDriver::Rig> rigs;
+    int n_ticks = 0, total_frames = 0;
+    for (int i = 0; i < N; ++i) {
+        Drive& d = drives[i];
+        d.n_frames = o.n_frames - i * o.frames_step;
+        d.first_tick = i * o.stagger;
+        if (d.n_frames <= 0) {
+            std::fprintf(stderr, "limo_stream: --frames-step leaves sequence %d without a frame\n", i);
+            return 2;
+        }
+        d.world = std::make_unique<synth_world::World>(d.n_frames, o.seed + (uint64_t)i);
+        d.world->n_az = o.n_az;
+        d.synth = std::make_unique<Synth>(*d.world, o.seed + (uint64_t)i, o.n_feat, std::string(), std::string());
+        // --perturb-rig I (testing aid): sequence I comes with another focal length - the driver must refuse it
+        d.cam = std::make_shared<Camera>(d.world->f + (i == o.perturb_rig ? 1. : 0.), Vector2d(d.world->cx, d.world->cy), d.world->cam_veh);
+        rigs.push_back({d.cam, d.world->cam_lidar});
+        n_ticks = std::max(n_ticks, d.first_tick + d.n_frames);
+        total_frames += d.n_frames;
+    }
+    sp.image_width = (int)drives[0].world->W;
+    sp.image_height = (int)drives[0].world->H;
+    std::unique_ptr<LockstepDriver> driver;
+    try {
+        driver = std::make_unique<LockstepDriver>(sp, rigs, o.host_threads);
+    } catch (const std::invalid_argument& e) {
+        std::fprintf(stderr, "limo_stream: %s\n", e.what());
+        return 2;
+    }
+    if (!o.depth_params_path.empty()) {
+        std::string err;
+        if (!depth_params_yaml::load(o.depth_params_path, &driver->depthParams(), &err)) {
+            std::fprintf(stderr, "limo_stream: --depth-params %s\n", err.c_str());
+            return 2;
+        }
+    }
+    auto release = [&]() {
+        for (Drive& d : drives)
+            if (d.frame.scan) limo_host_free(d.frame.scan);
+    };
+    double sec_synth = 0., sec_pipeline = 0.;
+    std::vector<std::optional<LockstepDriver::Frame>> tick(N);
+    for (int T = 0; T < n_ticks; ++T) {
+        const auto t0 = clk::now();
+        for (int i = 0; i < N; ++i) {
+            Drive& d = drives[i];
+            const int t = T - d.first_tick;
+            tick[i].reset();
+            if (t < 0 || t >= d.n_frames) continue;
+            if (!d.synth->frame(t, d.frame)) {
+                release();
+                return 1;
+            }
+            tick[i].emplace();
+            tick[i]->tracklets = std::move(d.frame.ts);  // (the tracker's message is handed over: the driver fills in depths)
+            tick[i]->cloud_xyzi = d.frame.scan;
+            tick[i]->n_pts = d.frame.n_pts;
+        }
+        const auto t1 = clk::now();
+        driver->tick(tick);
+        const auto t2 = clk::now();
+        sec_synth += std::chrono::duration<double>(t1 - t0).count();
+        sec_pipeline += std::chrono::duration<double>(t2 - t1).count();
+        if (!o.quiet && (T % 100 == 0 || T == n_ticks - 1)) {
+            std::printf("tick %d: %d frames so far\n", T, driver->stats().frames);
+            std::fflush(stdout);
+        }
+    }
+    release();
+    const LockstepDriver::Stats& st = driver->stats();
+    std::string per_sequence;
+    for (int i = 0; i < N; ++i) {
+        const Drive& d = drives[i];
+        const auto& poses = driver->poses(i);
+        double se = 0., worst = 0.;
+        for (int t = 0; t < d.n_frames; ++t) {
+            const Vector3d e = poses[t].inverse().translation() - d.world->origin_veh[t].translation();
+            se += e.norm() * e.norm();
+            worst = std::max(worst, e.norm());
+        }
+        const double ate = std::sqrt(se / d.n_frames);
+        if (!o.poses_path.empty()) {
+            std::ofstream f(o.poses_path + "." + std::to_string(i));
+            driver->writeKittiTrajectory(i, f);
+        }
+        if (!o.gt_path.empty()) {
+            std::ofstream f(o.gt_path + "." + std::to_string(i));
+            const EigenPose cv = d.cam->getEigenPose();
+            for (int t = 0; t < d.n_frames; ++t) kitti_io::writePoseRow(f, cv * d.world->origin_veh[t] * cv.inverse());
+        }
+        const StreamDriver::Stats& ss = driver->sequenceStats(i);
+        std::printf("limo_stream: sequence %d (seed %llu, first tick %d): %d frames, %d keyframes, %d solves, %d landmark selections on the device, ATE rmse %.4f m (max %.4f m)\n", i,
+                    (unsigned long long)(o.seed + (uint64_t)i), d.first_tick, ss.frames, ss.keyframes, ss.solves, driver->adjuster(i).device_selections_, ate, worst);
+        char buf[512];
+        std::snprintf(buf, sizeof(buf),
+                      "%s{\"seed\": %llu, \"first_tick\": %d, \"frames\": %d, \"keyframes\": %d, \"solves\": %d, \"five_point_calls\": %d, \"five_point_device_calls\": %d, "
+                      "\"select_device_calls\": %d, \"ate_rmse\": %.6f, \"ate_max\": %.6f}",
+                      i ? ", " : "", (unsigned long long)(o.seed + (uint64_t)i), d.first_tick, ss.frames, ss.keyframes, ss.solves, ss.five_point_calls, ss.five_point_device_calls,
+                      driver->adjuster(i).device_selections_, ate, worst);
+        per_sequence += buf;
+    }
+    auto stage = [](const char* name, const LockstepDriver::Stage& s, bool last = false) {
+        char buf[384];
+        std::snprintf(buf, sizeof(buf), "\"%s\": {\"batched_calls\": %ld, \"items\": %ld, \"max_items\": %d, \"fallback_calls\": %ld, \"ms_host\": %.3f, \"ms_abi\": %.3f}%s", name,
+                      s.batched_calls, s.items, s.max_items, s.fallback_calls, 1e3 * s.sec_host, 1e3 * s.sec_abi, last ? "" : ", ");
+        return std::string(buf);
+    };
+    std::printf("limo_stream: %d sequences in lock step on %d host threads: %d frames in %d ticks, %.2f ms per tick -> %.1f frames/s over all sequences; input synthesis %.1f ms per tick\n", N,
+                driver->hostThreads(), st.frames, st.ticks, 1e3 * sec_pipeline / std::max(1, st.ticks), st.frames / sec_pipeline, 1e3 * sec_synth / std::max(1, st.ticks));
+    // the JSON line (scripts/bench_lockstep.py, tests/test_lockstep_cpu.py, tests/test_gpu_lockstep.py read it): one line, the last one
+    std::printf("{\"sequences\": %d, \"host_threads\": %d, \"ticks\": %d, \"frames\": %d, \"frames_per_s\": %.3f, \"ms_pipeline\": %.3f, \"ms_synthesis\": %.3f, \"stages\": {%s%s%s%s%s%s}, "
+                "\"landmarks_initialised\": %ld, \"five_point_host\": %ld, \"select_host\": %ld, \"ms_host_finish\": %.3f, \"per_sequence\": [%s]}\n",
+                N, driver->hostThreads(), st.ticks, st.frames, st.frames / sec_pipeline, 1e3 * sec_pipeline, 1e3 * sec_synth, stage("depth", st.depth).c_str(),
+                stage("five_point", st.five_point).c_str(), stage("pose_only", st.pose_only).c_str(), stage("landmark_init", st.landmark_init).c_str(),
+                stage("select", st.select).c_str(), stage("solve", st.solve, true).c_str(), st.landmarks_initialised, st.five_point_host, st.select_host, 1e3 * st.sec_host_finish,
+                per_sequence.c_str());
+    (void)total_frames;
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    int n_frames = 200, n_feat = 1500, n_az = 2000, window = 5, misannounce_every = 0;
+    uint64_t seed = 7;
+    std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path;
+    bool use_depth = true, quiet = false, five_point_prior = false, progress = false;
+    int five_point_where = -1;  // 0: host, 1: device, -1: StreamParams' default
+    int select_where = -1;      // landmark selection of solve(): the same
+    StreamParams::DepthAhead depth_ahead = StreamParams::DepthAhead::Thread;
+    double min_flow = -1., time_between_keyframes = -1.;
+    LockstepOptions lockstep;
+    bool single_only = false;  // an option the lock-step drive does not have
+    for (int i = 1; i < argc; ++i) {
+        auto arg = [&](const char* name) { return !std::strcmp(argv[i], name) && i + 1 < argc; };
+        if (arg("--frames")) n_frames = std::atoi(argv[++i]);
+        else if (arg("--features")) n_feat = std::atoi(argv[++i]);
+        else if (arg("--az")) n_az = std::atoi(argv[++i]);
+        else if (arg("--seed")) seed = std::strtoull(argv[++i], nullptr, 10);
+        else if (arg("--window")) window = std::atoi(argv[++i]);
+        else if (arg("--sequences")) lockstep.sequences = std::atoi(argv[++i]);
+        else if (arg("--frames-step")) lockstep.frames_step = std::atoi(argv[++i]);
+        else if (arg("--stagger")) lockstep.stagger = std::atoi(argv[++i]);
+        else if (arg("--host-threads")) lockstep.host_threads = std::atoi(argv[++i]);
+        else if (arg("--perturb-rig")) lockstep.perturb_rig = std::atoi(argv[++i]);  // (testing aid, see run_lockstep)
+        else if (arg("--misannounce-every")) misannounce_every = std::atoi(argv[++i]), single_only = true;  // (testing aid, see the frame loop)
+        else if (arg("--min-flow")) min_flow = std::atof(argv[++i]);
+        else if (arg("--time-between-keyframes")) time_between_keyframes = std::atof(argv[++i]);
+        else if (arg("--poses")) poses_path = argv[++i];
+        else if (arg("--gt-poses")) gt_path = argv[++i];
+        else if (arg("--dump-velodyne")) dump_dir = argv[++i], single_only = true;
+        else if (arg("--velodyne")) replay_dir = argv[++i], single_only = true;
+        else if (arg("--depth-params")) depth_params_path = argv[++i];
+        else if (!std::strcmp(argv[i], "--no-depth")) use_depth = false;
+        else if (!std::strcmp(argv[i], "--no-prefetch")) depth_ahead = StreamParams::DepthAhead::None;
+        else if (arg("--depth-ahead")) {
+            const std::string m = argv[++i];
+            if (m != "thread" && m != "stream" && m != "none") {
+                std::fprintf(stderr, "limo_stream: --depth-ahead thread|stream|none\n");
+                return 2;
+            }
+            depth_ahead = m == "thread" ? StreamParams::DepthAhead::Thread : m == "stream" ? StreamParams::DepthAhead::Stream : StreamParams::DepthAhead::None;
+        }
+        else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
+        else if (!std::strcmp(argv[i], "--progress")) progress = single_only = true;
+        else if (!std::strcmp(argv[i], "--five-point-prior")) five_point_prior = true;  // the node's prior without tf (mono_lidar.cpp:157-186)
+        else if (!std::strcmp(argv[i], "--five-point-host")) five_point_where = 0;
+        else if (!std::strcmp(argv[i], "--five-point-device")) five_point_where = 1;
+        else if (!std::strcmp(argv[i], "--select-host")) select_where = 0;
+        else if (!std::strcmp(argv[i], "--select-device")) select_where = 1;
+        else {
+            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--five-point-host] [--five-point-device] [--select-host] [--select-device] [--quiet] [--progress] [--sequences N [--frames-step K] [--stagger S] [--host-threads T]]\n");
+            return 2;
+        }
+    }
+    using clk = std::chrono::steady_clock;
+    const bool in_lockstep = lockstep.sequences != 0 || lockstep.frames_step != 0 || lockstep.stagger != 0 || lockstep.host_threads != 0 || lockstep.perturb_rig >= 0;
+    if (in_lockstep && (lockstep.sequences < 1 || lockstep.frames_step < 0 || lockstep.stagger < 0 || lockstep.host_threads < 0 || single_only)) {
+        std::fprintf(stderr, "limo_stream: --frames-step, --stagger and --host-threads go with --sequences N (N >= 1, values >= 0); a lock-step drive has no --progress, "
+                             "--velodyne, --dump-velodyne or --misannounce-every\n");
+        return 2;
+    }
+    synth_world::World world(in_lockstep ? 1 : n_frames, seed);
+    world.n_az = n_az;
+    Camera::Ptr cam = std::make_shared<Camera>(world.f, Vector2d(world.cx, world.cy), world.cam_veh);
+    StreamParams sp;
+    sp.max_size_optimization_window = window;
+    sp.assign_depth = use_depth;
+    sp.depth_ahead = depth_ahead;
+    if (min_flow >= 0.) sp.min_median_flow = min_flow;
+    if (time_between_keyframes > 0.) sp.time_between_keyframes_sec = time_between_keyframes;
+    if (five_point_prior) sp.motion_prior = StreamParams::MotionPrior::FivePoint;
+    if (five_point_where >= 0) sp.five_point_on_device = five_point_where == 1;
+    if (select_where >= 0) sp.landmark_selection_on_device = select_where == 1;
+    sp.solver_time_sec = -1.;  // no wall-clock cap: the drive is reproducible
+    sp.image_width = (int)world.W;
+    sp.image_height = (int)world.H;
+    sp.height_over_ground = synth_world::World::kHeightOverGround;
+    if (in_lockstep) {  // (the depths of a tick are assigned inside the tick: --depth-ahead has nothing to run ahead of)
+        lockstep.n_frames = n_frames, lockstep.n_feat = n_feat, lockstep.n_az = n_az, lockstep.seed = seed;
+        lockstep.poses_path = poses_path, lockstep.gt_path = gt_path, lockstep.depth_params_path = depth_params_path, lockstep.quiet = quiet;
+        return run_lockstep(lockstep, sp);
+    }
+    StreamDriver driver(sp, cam, world.cam_lidar);
+    driver.adjuster().minimizer_progress_to_stdout_ = progress;
+    if (!depth_params_path.empty()) {
+        std::string err;
+        if (!depth_params_yaml::load(depth_params_path, &driver.depthParams(), &err)) {
+            std::fprintf(stderr, "limo_stream: --depth-params %s\n", err.c_str());
+            return 2;
+        }
+    }
+
+    Synth synth(world, seed, n_feat, replay_dir, dump_dir);
+    double sec_synth = 0., sec_pipeline = 0.;
+    size_t& n_points = synth.n_points;
+    Frame frames[2];
+    auto release = [&]() {
+        driver.cancelPrefetch();
+        for (Frame& fr : frames)
+            if (fr.scan) limo_host_free(fr.scan);
+    };
+    auto synthesize = [&](int t, Frame& out) -> bool { return synth.frame(t, out); };
     {
         const auto t0 = clk::now();
         if (n_frames > 0 && !synthesize(0, frames[0])) {

@@ -6,6 +6,7 @@
 #include "bundle_adjuster_keyframes.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <iterator>
 #include <chrono>
 
@@ -65,10 +66,13 @@ private:
 // Debugging aid: LIMO_KBA_DUMP=<dir>[:<first>[:<last>]] writes the flattened window of the solve() calls number first..last
 // (default: all) as <dir>/solve_NNNNNN.bin = int32 n_kf, n_cam, n_lm, n_obs, then the arrays of limo_ba_window in declaration
 // order (tests/window_io.py reads them back into a Window): how a window of a long drive becomes a test fixture.
-static void dump_window_if_asked(const limo_ba_window& w) {
+// The calls are numbered over the process (an atomic: adjusters of a lock-step drive are prepared on several threads); an adjuster with
+// a dump tag (BundleAdjusterKeyframes::dump_tag_ >= 0: sequence i of a LockstepDriver) numbers its own solves and writes
+// <dir>/solve_sII_NNNNNN.bin, so the files of a lock-step drive do not depend on how the threads interleave.
+static void dump_window_if_asked(const limo_ba_window& w, int tag, int& tagged_calls) {
     static const char* spec = std::getenv("LIMO_KBA_DUMP");
-    static int call = -1;
-    ++call;
+    static std::atomic<int> calls{0};
+    const int call = tag >= 0 ? tagged_calls++ : calls.fetch_add(1, std::memory_order_relaxed);
     if (!spec) return;
     std::string dir(spec);
     long first = 0, last = 1L << 40;
@@ -82,7 +86,10 @@ static void dump_window_if_asked(const limo_ba_window& w) {
     }
     if (call < first || call > last) return;
     char name[64];
-    std::snprintf(name, sizeof(name), "/solve_%06d.bin", call);
+    if (tag >= 0)
+        std::snprintf(name, sizeof(name), "/solve_s%02d_%06d.bin", tag, call);
+    else
+        std::snprintf(name, sizeof(name), "/solve_%06d.bin", call);
     std::FILE* f = std::fopen((dir + name).c_str(), "wb");
     if (!f) return;
     const int32_t head[4] = {w.n_kf, w.n_cam, w.n_lm, w.n_obs};
@@ -254,19 +261,35 @@ void BundleAdjusterKeyframes::push(const std::vector<Keyframe>& kfs) {
 
 void BundleAdjusterKeyframes::push(const Keyframe& kf) { push(Keyframe(kf)); }
 
+// push = preparePush + limo_landmark_init + commitPush (the split the lock-step driver needs: lockstep_driver.hpp makes ONE
+// limo_landmark_init call over the jobs of all its sequences)
 void BundleAdjusterKeyframes::push(Keyframe&& kf_in) {
+    Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    PushJob job;
+    preparePush(std::move(kf_in), job);
+    if (!job.ids.empty()) {
+        const int rc = limo_landmark_init(context(), (int32_t)job.ids.size(), job.off.data(), job.rays.data(), job.use_depth.data(), job.pos.data(), job.ok.data());
+        if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_landmark_init: ") + limo_last_error(ctx_));
+    }
+    commitPush(job);
+}
+
+// The keyframe enters the window; the rays of every landmark it introduces go into the job (pos / ok sized for the call's results).
+void BundleAdjusterKeyframes::preparePush(Keyframe&& kf_in, PushJob& job) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
     const TimestampNSec stamp = kf_in.timestamp_;
     const auto stored = std::make_shared<Keyframe>(std::move(kf_in));
     keyframes_[stamp] = stored;
     const Keyframe& kf = *stored;
     active_keyframe_ids_.insert(stamp);
+    job.kf = stored;
     // Every landmark this keyframe introduces is initialised in ONE device call (the reference does it one by one,
     // :289-330): depth back-projection where the keyframe measures a depth, N-view triangulation otherwise.
-    std::vector<LandmarkId> ids;
-    std::vector<int32_t> off{0};
-    std::vector<limo_ray> rays;
-    std::vector<uint8_t> use_depth;
+    std::vector<LandmarkId>& ids = job.ids;
+    std::vector<int32_t>& off = job.off;
+    std::vector<limo_ray>& rays = job.rays;
+    std::vector<uint8_t>& use_depth = job.use_depth;
+    ids.clear(), off.assign(1, 0), rays.clear(), use_depth.clear();
     // The rays of one (keyframe, camera) share pose and intrinsics: that part is formed once per view here, not once per ray (the
     // same statements on the same operands as make_ray - collectRays(..) below, which calculateLandmark still uses - so the same
     // bits); the new ids come in ascending order, so every active keyframe's measurements are walked by a finder of their own
@@ -334,14 +357,17 @@ void BundleAdjusterKeyframes::push(Keyframe&& kf_in) {
         use_depth.push_back(has_depth ? 1 : 0);
         off.push_back((int32_t)rays.size());
     }
-    if (!ids.empty()) {
-        std::vector<double> pos(3 * ids.size());
-        std::vector<uint8_t> ok(ids.size(), 0);
-        const int rc = limo_landmark_init(context(), (int32_t)ids.size(), off.data(), rays.data(), use_depth.data(), pos.data(), ok.data());
-        if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_landmark_init: ") + limo_last_error(ctx_));
-        for (size_t i = 0; i < ids.size(); ++i)
-            if (ok[i]) landmarks_[ids[i]] = std::make_shared<Landmark>(Vector3d(pos.data() + 3 * i), use_depth[i] != 0);
-    }
+    job.pos.assign(3 * ids.size(), 0.0);
+    job.ok.assign(ids.size(), 0);
+}
+
+// The landmarks the call could initialise are created; every landmark the keyframe measures and the window knows becomes active.
+void BundleAdjusterKeyframes::commitPush(PushJob& job) {
+    Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    const Keyframe& kf = *job.kf;
+    const std::vector<LandmarkId>& ids = job.ids;
+    for (size_t i = 0; i < ids.size(); ++i)
+        if (job.ok[i]) landmarks_[ids[i]] = std::make_shared<Landmark>(Vector3d(job.pos.data() + 3 * i), job.use_depth[i] != 0);
     // (measurements and active ids are both in id order: every insertion gets the place of the one before it as its hint)
     SortedFinder<decltype(landmarks_)> now_known(landmarks_);
     auto hint = active_landmark_ids_.begin();
@@ -552,9 +578,8 @@ void BundleAdjusterKeyframes::deactivateKeyframes(int min_num_connecting_landmar
 }
 
 // ------------------------------------------------------------------------------------------ flattening
-namespace {
-
-struct Flat {
+// (the type the jobs of the split-phase entry points own: declared in the header, known only here)
+struct FlatWindow {
     std::vector<double> kf_pose, kf_dir, kf_dist, cam, lm_pos, lm_w;
     std::vector<int32_t> kf_fix, obs_kf, obs_lm, obs_cam;
     std::vector<uint8_t> lm_gp;
@@ -655,6 +680,10 @@ struct Flat {
     }
 };
 
+namespace {
+
+using Flat = FlatWindow;
+
 std::string report_string(const limo_ba_report& r, const char* what) {
     static const char* term[] = {"CONVERGENCE", "NO_CONVERGENCE", "FAILURE"};
     std::stringstream ss;
@@ -678,11 +707,55 @@ void BundleAdjusterKeyframes::setDeviceSelection(const limo_select_params* param
     select_params_.n_add = (int32_t)select_add_.size();
 }
 
-// The active landmarks minus the selector's outliers as a limo_select_pool (keyframes and observations by the merge passes of Flat),
-// limo_landmark_select, and the result handed to the selector.  false: the call did not return LIMO_OK - nothing has changed.
-bool BundleAdjusterKeyframes::selectOnDevice(const LandmarkView& active_lms, const std::map<KeyframeId, Keyframe::ConstPtr>& active_kfs) {
-    Flat F;
-    std::vector<uint64_t> kf_stamp, lm_id;
+namespace {
+limo_ba_options window_options(const BundleAdjusterKeyframes::OutlierRejectionOptions& r, int min_landmarks_for_trimming, double solver_time_sec) {
+    limo_ba_options o;
+    limo_ba_default_options(&o);
+    o.depth_thres = r.depth_thres;
+    o.reprojection_thres = r.reprojection_thres;
+    o.depth_quantile = r.depth_quantile;
+    o.reprojection_quantile = r.reprojection_quantile;
+    o.num_trim_rounds = r.num_iterations;
+    o.min_landmarks_for_trimming = min_landmarks_for_trimming;
+    o.max_solver_time_sec = solver_time_sec;
+    return o;
+}
+BundleAdjusterKeyframes::LastReport last_report_of(const limo_ba_report& rep) {
+    BundleAdjusterKeyframes::LastReport r;
+    r.termination = rep.termination, r.num_solves = rep.num_solves, r.iterations_total = rep.iterations_total, r.n_trimmed_landmarks = rep.n_trimmed_landmarks;
+    r.n_depth_blocks = rep.n_depth_blocks, r.n_repr_blocks = rep.n_repr_blocks, r.n_gp_blocks = rep.n_gp_blocks;
+    r.initial_cost = rep.initial_cost, r.final_cost = rep.final_cost, r.time_sec = rep.time_sec;
+    return r;
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ selection in front of solve()
+// prepareSelection: the active landmarks and keyframes as the selector reads them and - with device selection on, where the library has
+// limo_landmark_select - the active landmarks minus the selector's outliers as a limo_select_pool (keyframes and observations by the
+// merge passes of FlatWindow); job.on_device says whether there is a pool to hand to limo_landmark_select[_batch] with job.params and
+// job.out.  commitSelection(job, true) hands the call's result to the selector; (job, false) - no pool, or the call did not return
+// LIMO_OK - runs the host selector.  Either way selected_landmark_ids_ is the selection afterwards.
+void BundleAdjusterKeyframes::prepareSelection(SelectJob& job) {
+    Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    if (keyframes_.size() < 3) throw NotEnoughKeyframesException(keyframes_.size(), 3);
+    // (getActiveLandmarkConstPtrs() as a sorted vector: the selector's schemes read it in this form, no map is built for them)
+    LandmarkView& active_lms = job.active_lms;
+    active_lms.clear();
+    {
+        active_lms.reserve(active_landmark_ids_.size());
+        SortedFinder<decltype(landmarks_)> known(landmarks_);
+        for (const auto& id : active_landmark_ids_) {
+            auto it = known.find(id);
+            if (it != landmarks_.cend()) active_lms.push_back({id, it->second});
+        }
+    }
+    job.active_kfs = getActiveKeyframeConstPtrs();
+    job.on_device = false;
+    if (!device_selection_ || &limo_landmark_select == nullptr) return;
+    job.flat = std::make_shared<FlatWindow>();
+    FlatWindow& F = *job.flat;
+    std::vector<uint64_t>&kf_stamp = job.kf_stamp, &lm_id = job.lm_id;
+    kf_stamp.clear(), lm_id.clear();
     // (a camera is a column of the flattened table by its object, a camera of the host schemes by its id: the same thing as long as
     // every id names one object in the window)
     std::map<CameraId, const Camera*> by_id;
@@ -692,13 +765,14 @@ bool BundleAdjusterKeyframes::selectOnDevice(const LandmarkView& active_lms, con
         F.add_keyframe(kf);
         kf_stamp.push_back(kf.timestamp_);
         for (const auto& c : kf.cameras_) {
-            if (!by_id.emplace(c.first, c.second.get()).first->second || by_id.at(c.first) != c.second.get()) return false;
-            if (by_object.emplace(c.second.get(), c.first).first->second != c.first) return false;
+            if (!by_id.emplace(c.first, c.second.get()).first->second || by_id.at(c.first) != c.second.get()) return;
+            if (by_object.emplace(c.second.get(), c.first).first->second != c.first) return;
         }
     }
-    if (F.kfs.size() != active_kfs.size()) return false;  // (select() would be given other keyframes than the window holds)
+    if (F.kfs.size() != job.active_kfs.size()) return;  // (select() would be given other keyframes than the window holds)
     std::vector<std::pair<LandmarkId, int>> lm_index;
-    std::vector<uint8_t> has_depth;
+    std::vector<uint8_t>& has_depth = job.has_depth;
+    has_depth.clear();
     const std::set<LandmarkId>& outliers = landmark_selector_->getOutliers();
     auto io = outliers.cbegin();
     F.reserve_landmarks(active_lms.size());
@@ -712,53 +786,44 @@ bool BundleAdjusterKeyframes::selectOnDevice(const LandmarkView& active_lms, con
         has_depth.push_back(el.second->has_measured_depth ? 1 : 0);
     }
     for (size_t k = 0; k < F.kfs.size(); ++k) F.add_observations((int)k, *F.kfs[k], lm_index);
-    limo_select_pool w;
+    limo_select_pool& w = job.pool;
     w.n_kf = (int32_t)F.kfs.size(), w.n_cam = (int32_t)F.cam_index.size(), w.n_lm = (int32_t)lm_id.size(), w.n_obs = (int32_t)F.obs_kf.size();
     w.kf_pose = F.kf_pose.data(), w.kf_stamp = kf_stamp.data(), w.cam = F.cam.data();
     w.lm_id = lm_id.data(), w.lm_pos = F.lm_pos.data(), w.lm_has_depth = has_depth.data(), w.lm_is_ground = F.lm_gp.data();
     w.obs_kf = F.obs_kf.data(), w.obs_lm = F.obs_lm.data(), w.obs_cam = F.obs_cam.data();
     w.obs_u = F.u.data(), w.obs_v = F.v.data(), w.obs_d = F.d.data();
     select_params_.add = select_add_.empty() ? nullptr : select_add_.data();
-    std::vector<uint8_t> out(lm_id.size() + 1);
-    if (limo_landmark_select(context(), &w, &select_params_, out.data()) != LIMO_OK) return false;
+    job.params = &select_params_;
+    job.out.assign(lm_id.size() + 1, 0);
+    job.on_device = true;
+}
+
+void BundleAdjusterKeyframes::commitSelection(SelectJob& job, bool device_ok) {
+    Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    if (!(device_ok && job.on_device)) {
+        selected_landmark_ids_ = landmark_selector_->select(job.active_lms, job.active_kfs);
+        return;
+    }
     using Category = LandmarkCategorizatonInterface::Category;
+    const std::vector<uint64_t>& lm_id = job.lm_id;
+    const std::vector<uint8_t>& out = job.out;
     std::vector<LandmarkId> selection;
     std::vector<std::pair<LandmarkId, Category>> categories;
     for (size_t i = 0; i < lm_id.size(); ++i) {
         if ((out[i] & 7) != 0) selection.push_back(lm_id[i]);
         if ((out[i] & 3) != 0) categories.push_back({(LandmarkId)lm_id[i], (out[i] & 3) == 1 ? Category::NearField : (out[i] & 3) == 2 ? Category::MiddleField : Category::FarField});
     }
-    landmark_selector_->acceptSelection(active_lms, active_kfs, selection, std::move(categories));
-    return true;
+    landmark_selector_->acceptSelection(job.active_lms, job.active_kfs, selection, std::move(categories));
+    selected_landmark_ids_ = landmark_selector_->getLastSelection();
+    ++device_selections_;
 }
 
-std::string BundleAdjusterKeyframes::solve() {
+// ------------------------------------------------------------------------------------------ solve = selection, then prepareSolve + limo_ba_solve + commitSolve
+// prepareSolve: the active keyframes and the selected landmarks as job.window (a limo_ba_window over buffers the job owns) and job.opts.
+void BundleAdjusterKeyframes::prepareSolve(WindowJob& job) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
-    if (keyframes_.size() < 3) throw NotEnoughKeyframesException(keyframes_.size(), 3);
-    using clk = std::chrono::steady_clock;
-    static const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;  // where the host time of solve() goes
-    const auto t_s0 = clk::now();
-    // (getActiveLandmarkConstPtrs() as a sorted vector: the selector's schemes read it in this form, no map is built for them)
-    LandmarkView active_lms;
-    {
-        active_lms.reserve(active_landmark_ids_.size());
-        SortedFinder<decltype(landmarks_)> known(landmarks_);
-        for (const auto& id : active_landmark_ids_) {
-            auto it = known.find(id);
-            if (it != landmarks_.cend()) active_lms.push_back({id, it->second});
-        }
-    }
-    const auto active_kfs = getActiveKeyframeConstPtrs();
-    const auto t_s0b = clk::now();
-    if (device_selection_ && &limo_landmark_select != nullptr && selectOnDevice(active_lms, active_kfs)) {
-        selected_landmark_ids_ = landmark_selector_->getLastSelection();
-        ++device_selections_;
-    } else {
-        selected_landmark_ids_ = landmark_selector_->select(active_lms, active_kfs);
-    }
-    const auto t_s1 = clk::now();
-
-    Flat F;
+    job.flat = std::make_shared<FlatWindow>();
+    FlatWindow& F = *job.flat;
     for (const auto& id : active_keyframe_ids_) F.add_keyframe(*keyframes_.at(id));
     std::vector<std::pair<LandmarkId, int>> lm_index;  // (selected ids come in id order: sorted as built)
     F.reserve_landmarks(selected_landmark_ids_.size());
@@ -775,46 +840,60 @@ std::string BundleAdjusterKeyframes::solve() {
     }
     for (size_t k = 0; k < F.kfs.size(); ++k) F.add_observations((int)k, *F.kfs[k], lm_index);
     F.finish();
-
-    limo_ba_options o;
-    limo_ba_default_options(&o);
-    o.depth_thres = outlier_rejection_options_.depth_thres;
-    o.reprojection_thres = outlier_rejection_options_.reprojection_thres;
-    o.depth_quantile = outlier_rejection_options_.depth_quantile;
-    o.reprojection_quantile = outlier_rejection_options_.reprojection_quantile;
-    o.num_trim_rounds = outlier_rejection_options_.num_iterations;
-    o.min_landmarks_for_trimming = 100;  // :741 (compared with selected_landmark_ids_.size())
-    o.max_solver_time_sec = solver_time_sec;
-    limo_ba_report rep;
-    limo_ctx* ctx = context();
-    dump_window_if_asked(F.w);
-    setIterationLog(ctx);
-    const auto t_s2 = clk::now();
-    const int rc = limo_ba_solve(ctx, &F.w, &o, &rep);
-    const auto t_s3 = clk::now();
-    if (rc == LIMO_ERR_NOT_ENOUGH_KF) throw NotEnoughKeyframesException(F.kfs.size(), 3);
-    if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_solve: ") + limo_last_error(ctx));
-    collectIterations(ctx, "solve");
-    F.write_back(true);
-    last_report_ = {rep.termination, rep.num_solves, rep.iterations_total, rep.n_trimmed_landmarks, rep.n_depth_blocks,
-                    rep.n_repr_blocks, rep.n_gp_blocks, rep.initial_cost, rep.final_cost, rep.time_sec};
-    if (shim_trace) {
-        auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        std::fprintf(stderr, "[shim] solve: %zu active landmarks, %zu selected, %d LM iterations in %d solves: active maps %.0f us, selection %.0f us, flatten %.0f us, limo_ba_solve %.0f us, write-back %.0f us\n",
-                     active_landmark_ids_.size(), selected_landmark_ids_.size(), rep.iterations_total, rep.num_solves, us(t_s0, t_s0b), us(t_s0b, t_s1), us(t_s1, t_s2),
-                     us(t_s2, t_s3), us(t_s3, clk::now()));
-    }
-    return report_string(rep, "solve");
+    job.window = &F.w;
+    job.has_prior = false;
+    job.opts = window_options(outlier_rejection_options_, 100, solver_time_sec);  // :741 (compared with selected_landmark_ids_.size())
+    job.report = limo_ba_report{};
+    dump_window_if_asked(F.w, dump_tag_, dump_calls_);
 }
 
-std::string BundleAdjusterKeyframes::adjustPoseOnly(Keyframe& kf) {
+// commitSolve: poses, planes and landmarks of the solved window back into the objects, job.report into last_report_; the report string.
+std::string BundleAdjusterKeyframes::commitSolve(WindowJob& job) {
+    job.flat->write_back(true);
+    last_report_ = last_report_of(job.report);
+    return report_string(job.report, "solve");
+}
+
+std::string BundleAdjusterKeyframes::solve() {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
     using clk = std::chrono::steady_clock;
-    static const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;
-    const auto t_p0 = clk::now();
+    static const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;  // where the host time of solve() goes
+    const auto t_s0 = clk::now();
+    SelectJob sel;
+    prepareSelection(sel);
+    const bool on_device = sel.on_device && limo_landmark_select(context(), &sel.pool, sel.params, sel.out.data()) == LIMO_OK;
+    commitSelection(sel, on_device);
+    const auto t_s1 = clk::now();
+
+    WindowJob job;
+    prepareSolve(job);
+    limo_ba_report& rep = job.report;
+    limo_ctx* ctx = context();
+    setIterationLog(ctx);
+    const auto t_s2 = clk::now();
+    const int rc = limo_ba_solve(ctx, job.window, &job.opts, &rep);
+    const auto t_s3 = clk::now();
+    if (rc == LIMO_ERR_NOT_ENOUGH_KF) throw NotEnoughKeyframesException(job.flat->kfs.size(), 3);
+    if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_solve: ") + limo_last_error(ctx));
+    collectIterations(ctx, "solve");
+    std::string summary = commitSolve(job);
+    if (shim_trace) {
+        auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        std::fprintf(stderr, "[shim] solve: %zu active landmarks, %zu selected, %d LM iterations in %d solves: active maps + selection %.0f us, flatten %.0f us, limo_ba_solve %.0f us, write-back %.0f us\n",
+                     active_landmark_ids_.size(), selected_landmark_ids_.size(), rep.iterations_total, rep.num_solves, us(t_s0, t_s1), us(t_s1, t_s2),
+                     us(t_s2, t_s3), us(t_s3, clk::now()));
+    }
+    return summary;
+}
+
+// ------------------------------------------------------------------------------------------ adjustPoseOnly = preparePoseOnly + limo_ba_adjust_pose_only + commitPoseOnly
+// preparePoseOnly: the frame against the landmarks of the last selection as job.window (n_kf = 1), the speed prior of the last two
+// active keyframes (job.has_prior) and job.opts.
+void BundleAdjusterKeyframes::preparePoseOnly(Keyframe& kf, WindowJob& job) {
+    Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
     selected_landmark_ids_ = landmark_selector_->getLastSelection();  // :828
-    const auto t_p1 = clk::now();
-    Flat F;
+    job.flat = std::make_shared<FlatWindow>();
+    FlatWindow& F = *job.flat;
     F.add_keyframe(kf);
     std::vector<std::pair<LandmarkId, int>> lm_index;  // (selected ids come in id order: sorted as built)
     F.reserve_landmarks(selected_landmark_ids_.size());
@@ -831,8 +910,10 @@ std::string BundleAdjusterKeyframes::adjustPoseOnly(Keyframe& kf) {
     }
     F.add_observations(0, kf, lm_index);
     F.finish();
+    job.window = &F.w;
 
-    limo_speed_prior prior;
+    limo_speed_prior& prior = job.prior;
+    prior = limo_speed_prior{};
     prior.speed_weight = 0.0;
     if (active_keyframe_ids_.size() > 2) {  // :835-853
         auto sorted = getSortedActiveKeyframePtrs();
@@ -850,31 +931,38 @@ std::string BundleAdjusterKeyframes::adjustPoseOnly(Keyframe& kf) {
             for (int i = 0; i < 7; ++i) prior.pose_before[i] = k0.pose_[i];
         }
     }
-    limo_ba_options o;
-    limo_ba_default_options(&o);
-    o.depth_thres = outlier_rejection_options_.depth_thres;
-    o.reprojection_thres = outlier_rejection_options_.reprojection_thres;
-    o.depth_quantile = outlier_rejection_options_.depth_quantile;
-    o.reprojection_quantile = outlier_rejection_options_.reprojection_quantile;
-    o.num_trim_rounds = outlier_rejection_options_.num_iterations;
-    o.min_landmarks_for_trimming = 30;  // :865
-    o.max_solver_time_sec = solver_time_sec;
-    limo_ba_report rep;
+    job.has_prior = prior.speed_weight > 0.0;
+    job.opts = window_options(outlier_rejection_options_, 30, solver_time_sec);  // :865
+    job.report = limo_ba_report{};
+}
+
+// commitPoseOnly: the refined pose (and plane) back into the frame's keyframe, job.report into last_report_; the report string.
+std::string BundleAdjusterKeyframes::commitPoseOnly(WindowJob& job) {
+    job.flat->write_back(false);
+    last_report_ = last_report_of(job.report);
+    return report_string(job.report, "adjustPoseOnly");
+}
+
+std::string BundleAdjusterKeyframes::adjustPoseOnly(Keyframe& kf) {
+    Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    using clk = std::chrono::steady_clock;
+    static const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;
+    const auto t_p1 = clk::now();
+    WindowJob job;
+    preparePoseOnly(kf, job);
+    limo_ba_report& rep = job.report;
     limo_ctx* ctx = context();
     setIterationLog(ctx);
     const auto t_p2 = clk::now();
-    const int rc = limo_ba_adjust_pose_only(ctx, &F.w, prior.speed_weight > 0.0 ? &prior : nullptr, &o, &rep);
+    const int rc = limo_ba_adjust_pose_only(ctx, job.window, job.has_prior ? &job.prior : nullptr, &job.opts, &rep);
     const auto t_p3 = clk::now();
     if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_adjust_pose_only: ") + limo_last_error(ctx));
     collectIterations(ctx, "adjustPoseOnly");
-    F.write_back(false);
-    last_report_ = {rep.termination, rep.num_solves, rep.iterations_total, rep.n_trimmed_landmarks, rep.n_depth_blocks,
-                    rep.n_repr_blocks, rep.n_gp_blocks, rep.initial_cost, rep.final_cost, rep.time_sec};
-    std::string summary = report_string(rep, "adjustPoseOnly");
+    std::string summary = commitPoseOnly(job);
     if (shim_trace) {
         auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        std::fprintf(stderr, "[shim] adjustPoseOnly: %d landmarks, %d observations: selection copy %.0f us, flatten + prior %.0f us, limo_ba_adjust_pose_only %.0f us, write-back + summary %.0f us\n",
-                     F.w.n_lm, F.w.n_obs, us(t_p0, t_p1), us(t_p1, t_p2), us(t_p2, t_p3), us(t_p3, clk::now()));
+        std::fprintf(stderr, "[shim] adjustPoseOnly: %d landmarks, %d observations: selection copy + flatten + prior %.0f us, limo_ba_adjust_pose_only %.0f us, write-back + summary %.0f us\n",
+                     job.window->n_lm, job.window->n_obs, us(t_p1, t_p2), us(t_p2, t_p3), us(t_p3, clk::now()));
     }
     return summary;
 }

@@ -16,6 +16,8 @@
 
 namespace keyframe_bundle_adjustment {
 
+struct FlatWindow;  // a window flattened into the arrays of the C-ABI (bundle_adjuster_keyframes.cpp)
+
 class BundleAdjusterKeyframes {
 public:
     using UPtr = std::unique_ptr<BundleAdjusterKeyframes>;
@@ -93,6 +95,52 @@ public:
     void setDeviceSelection(const limo_select_params* params);
     int device_selections_ = 0;  // solve() calls whose selection limo_landmark_select made
 
+    // Split-phase forms of push, adjustPoseOnly, the selection in front of solve and solve (not in the reference).  Each method above is
+    // prepare + ONE C-ABI call + commit; a caller that drives several adjusters in lock step (lockstep_driver.hpp) prepares them all,
+    // makes one batched call over the jobs (limo_landmark_init over the concatenated rays, limo_ba_adjust_pose_only_batch,
+    // limo_landmark_select_batch, limo_ba_batch_create / _solve / _download) and commits each.  A job owns every buffer its C-ABI
+    // arguments point into; prepare and commit never touch a limo_ctx, so adjusters of different sequences may be prepared and committed
+    // on different threads while one thread makes the calls.  The caller checks the call's return code before it commits.
+    struct PushJob {  // limo_landmark_init(ids.size(), off, rays, use_depth, pos, ok); ids.empty(): no call
+        Keyframe::Ptr kf;
+        std::vector<LandmarkId> ids;
+        std::vector<int32_t> off{0};
+        std::vector<limo_ray> rays;
+        std::vector<uint8_t> use_depth;
+        std::vector<double> pos;   // [3 * ids.size()]  result
+        std::vector<uint8_t> ok;   // [ids.size()]      result
+    };
+    void preparePush(Keyframe&& kf, PushJob& job);
+    void commitPush(PushJob& job);
+    struct WindowJob {  // limo_ba_adjust_pose_only(window, has_prior ? &prior : NULL, &opts, &report) / limo_ba_solve(window, &opts, &report)
+        std::shared_ptr<FlatWindow> flat;  // the buffers behind `window`
+        limo_ba_window* window = nullptr;
+        limo_speed_prior prior{};
+        bool has_prior = false;
+        limo_ba_options opts{};
+        limo_ba_report report{};           // result
+    };
+    void preparePoseOnly(Keyframe& kf, WindowJob& job);
+    std::string commitPoseOnly(WindowJob& job);
+    struct SelectJob {  // on_device: limo_landmark_select(&pool, params, out.data()); else there is nothing to call
+        LandmarkView active_lms;
+        std::map<KeyframeId, Keyframe::ConstPtr> active_kfs;
+        bool on_device = false;
+        std::shared_ptr<FlatWindow> flat;  // the buffers behind `pool`, with the three below
+        std::vector<uint64_t> kf_stamp, lm_id;
+        std::vector<uint8_t> has_depth;
+        limo_select_pool pool{};
+        const limo_select_params* params = nullptr;  // (this adjuster's: valid until its next setDeviceSelection)
+        std::vector<uint8_t> out;          // result
+    };
+    void prepareSelection(SelectJob& job);                   // throws NotEnoughKeyframesException as solve() does
+    void commitSelection(SelectJob& job, bool device_ok);    // device_ok = false: the host selector runs
+    void prepareSolve(WindowJob& job);                       // (after commitSelection: flattens selected_landmark_ids_)
+    std::string commitSolve(WindowJob& job);
+    // LIMO_KBA_DUMP files of this adjuster are named solve_sII_NNNNNN.bin with II = dump_tag_ and its own count (>= 0: a sequence of a
+    // lock-step drive); -1: solve_NNNNNN.bin, counted over the process as before
+    int dump_tag_ = -1;
+
 public:
     std::map<KeyframeId, Keyframe::Ptr> keyframes_;
     std::map<LandmarkId, Landmark::Ptr> landmarks_;
@@ -117,7 +165,7 @@ private:
     void setIterationLog(limo_ctx* ctx);      // before the solve: the context's switch follows minimizer_progress_to_stdout_
     void collectIterations(limo_ctx* ctx, const char* what);  // behind it: last_iterations_ and the table
     std::vector<limo_ba_iteration> last_iterations_;
-    bool selectOnDevice(const LandmarkView& active_lms, const std::map<KeyframeId, Keyframe::ConstPtr>& active_kfs);
+    int dump_calls_ = 0;
     bool device_selection_ = false;
     limo_select_params select_params_{};
     std::vector<limo_select_add> select_add_;

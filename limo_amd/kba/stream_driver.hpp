@@ -13,6 +13,7 @@
 //     -> pose of the frame in KITTI form             (:281-294: camera_0 <- camera_t, 12 numbers per row)
 // The very first frame is a Pose-fixed keyframe at the identity (:305-326).
 // Everything numerical happens behind the C-ABI; this file is host-side control flow only.
+// N sequences of one rig at once: lockstep_driver.hpp (the same stages, one batched call per stage; it shares stream_detail below).
 #pragma once
 #include <array>
 #include <chrono>
@@ -93,6 +94,253 @@ struct StreamParams {
     std::vector<int> ground_labels{6, 7, 8, 9, 10};  // cityscapes labels treated as ground (labels_["ground"])
 };
 
+// The per-sequence pieces of a frame that StreamDriver (one sequence, one call per stage) and LockstepDriver (lockstep_driver.hpp: N
+// sequences, one batched call per stage) both run: stated once here, so the two drivers cannot drift apart.
+namespace stream_detail {
+
+// the node's wiring of keyframe selection and landmark selection (mono_lidar.cpp:396-430) for one sequence's adjuster
+inline void configureSequence(const StreamParams& p, BundleAdjusterKeyframes& ba, KeyframeSelector& selector) {
+    ba.set_solver_time(p.solver_time_sec);
+    selector.addScheme(KeyframeRejectionSchemeFlow::createConst(p.min_median_flow));
+    selector.addScheme(KeyframeSelectionSchemePose::createConst(p.critical_rotation_difference));
+    selector.addScheme(KeyframeSparsificationSchemeTime::createConst(p.time_between_keyframes_sec * 1e9));
+    LandmarkSparsificationSchemeVoxel::Parameters vp;
+    vp.max_num_landmarks_near = p.max_number_landmarks_near_bin;
+    vp.max_num_landmarks_middle = p.max_number_landmarks_middle_bin;
+    vp.max_num_landmarks_far = p.max_number_landmarks_far_bin;
+    vp.voxel_size_xyz = p.voxel_size_xyz;
+    vp.roi_far_xyz = {{p.roi_far, p.roi_far, p.roi_far}};
+    vp.roi_middle_xyz = {{p.roi_middle, p.roi_middle, p.roi_middle}};
+    ba.landmark_selector_->addScheme(LandmarkSparsificationSchemeVoxel::createConst(vp));
+    LandmarkSelectionSchemeAddDepth::Parameters ap;  // "depth assurance" (:409-426)
+    if (p.add_depth_landmarks_newest > 0)
+        ap.params_per_keyframe.push_back(std::make_tuple(0, p.add_depth_landmarks_newest, [](const Landmark::ConstPtr& lm) { return lm->has_measured_depth; },
+                                                         [](const Measurement& m, const Vector3d&) { return m.d; }));
+    for (int i = 0; i < p.max_size_optimization_window && p.add_ground_landmarks_per_keyframe > 0; ++i)
+        ap.params_per_keyframe.push_back(std::make_tuple(i, p.add_ground_landmarks_per_keyframe, [](const Landmark::ConstPtr& lm) { return lm->is_ground_plane; },
+                                                         [](const Measurement&, const Vector3d& local) { return (float)local.norm(); }));
+    ba.landmark_selector_->addScheme(LandmarkSelectionSchemeAddDepth::createConst(ap));
+    if (p.landmark_selection_on_device) {  // the same wiring as limo_select_params (the host schemes above stay: they take over when the call is refused)
+        limo_select_params sp{};
+        for (int i = 0; i < 3; ++i) sp.voxel_size_xyz[i] = p.voxel_size_xyz[i];
+        sp.roi_far = p.roi_far, sp.roi_middle = p.roi_middle;
+        sp.max_near = p.max_number_landmarks_near_bin, sp.max_middle = p.max_number_landmarks_middle_bin, sp.max_far = p.max_number_landmarks_far_bin;
+        std::vector<limo_select_add> add;
+        if (p.add_depth_landmarks_newest > 0) add.push_back({0, p.add_depth_landmarks_newest, LIMO_SELECT_HAS_DEPTH, LIMO_SELECT_KEY_MEASURED_DEPTH});
+        for (int i = 0; i < p.max_size_optimization_window && p.add_ground_landmarks_per_keyframe > 0; ++i)
+            add.push_back({i, p.add_ground_landmarks_per_keyframe, LIMO_SELECT_IS_GROUND, LIMO_SELECT_KEY_RANGE});
+        sp.n_add = (int32_t)add.size(), sp.add = add.data();
+        ba.setDeviceSelection(&sp);
+    }
+}
+
+// pixel coordinates and ground flags of the newest point of every track, as limo_depth_estimate wants them
+inline void stageFeatures(const StreamParams& p, const Tracklets& ts, std::vector<float>& uv, std::vector<uint8_t>& ground) {
+    const size_t n = ts.tracks.size();
+    uv.resize(2 * n);
+    ground.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        uv[2 * i] = ts.tracks[i].feature_points[0].u;
+        uv[2 * i + 1] = ts.tracks[i].feature_points[0].v;
+        ground[i] = 0;
+        for (int l : p.ground_labels) ground[i] |= ts.tracks[i].label == l;
+    }
+}
+
+// The depths a driver assigned to the tracks of its sequence in the last frames (per track a ring, newest at head - 1).
+// A frame may come here twice (announced to the depth thread, then handed to process() with another message for the same stamp, or
+// announced and never processed): the statistics count a stamp once and the history REPLACES the entry of a stamp it already holds.
+struct DepthHistory {
+    // the statistics count this message's stamp (false: it was the last one recorded)
+    bool counts(const Tracklets& ts) const { return !(counted_any_ && !ts.stamps.empty() && counted_stamp_ == ts.stamps.front()); }
+    // Remembers this frame's depth per track (sweep_depth[i] where the sweep was used and the caller knew none, else the message's) and
+    // fills the history points from the memory: the depth of EVERY point of every track, in message order, into `out`.
+    void record(const Tracklets& ts, const float* sweep_depth /* [tracks] or null */, std::vector<float>& out, int& features_with_depth) {
+        const size_t n = ts.tracks.size();
+        const bool counted = !counts(ts);
+        const TimestampNSec stamp = ts.stamps.front();
+        out.clear();
+        for (size_t i = 0; i < n; ++i) {
+            const Tracklet& tr = ts.tracks[i];
+            if (tr.feature_points.empty()) continue;
+            const float d0 = (sweep_depth && tr.feature_points[0].d < 0.f) ? sweep_depth[i] : tr.feature_points[0].d;  // (a depth the caller knows stays)
+            out.push_back(d0);
+            History& h = history_[tr.id];
+            if (h.n > 0 && h.stamp[(h.head - 1) & (History::kDepth - 1)] == stamp) {
+                h.d[(h.head - 1) & (History::kDepth - 1)] = d0;
+            } else {
+                h.stamp[h.head] = stamp;
+                h.d[h.head] = d0;
+                h.head = (h.head + 1) & (History::kDepth - 1);
+                h.n = std::min<int>(History::kDepth, h.n + 1);
+            }
+            for (size_t k = 1; k < tr.feature_points.size(); ++k) {
+                float dk = tr.feature_points[k].d;
+                if (dk < 0.f && k < ts.stamps.size()) {
+                    // (a track seen in consecutive frames has the entry of stamps[k] k places behind the newest: looked at first; stamps
+                    // are unique inside a history, so the scan finds the same entry or none)
+                    const int e = (h.head - 1 - (int)k) & (History::kDepth - 1);
+                    if ((int)k < h.n && h.stamp[e] == ts.stamps[k]) {
+                        dk = h.d[e];
+                    } else {
+                        for (int j = 0; j < h.n; ++j) {
+                            const int e2 = (h.head - 1 - j) & (History::kDepth - 1);
+                            if (h.stamp[e2] == ts.stamps[k]) dk = h.d[e2];
+                        }
+                    }
+                }
+                out.push_back(dk);
+            }
+            if (!counted) features_with_depth += d0 > 0.f;
+        }
+        counted_any_ = true;
+        counted_stamp_ = stamp;
+    }
+    void forgetEndedTracks(const Tracklets& ts) {  // every 64 frames
+        if (++frames_since_gc_ < 64) return;
+        frames_since_gc_ = 0;
+        const TimestampNSec oldest = ts.stamps.back();
+        for (auto it = history_.begin(); it != history_.end();)
+            it = it->second.stamp[(it->second.head - 1) & (History::kDepth - 1)] < oldest ? history_.erase(it) : std::next(it);
+    }
+
+private:
+    struct History {
+        static constexpr int kDepth = 16;
+        TimestampNSec stamp[kDepth];
+        float d[kDepth];
+        int head = 0, n = 0;
+    };
+    std::unordered_map<unsigned long, History> history_;
+    int frames_since_gc_ = 0;
+    TimestampNSec counted_stamp_ = 0;  // the last frame whose features went into the statistics (record is idempotent per stamp)
+    bool counted_any_ = false;
+};
+
+inline void applyDepths(Tracklets& ts, const std::vector<float>& d) {
+    size_t j = 0;
+    for (auto& tr : ts.tracks)
+        for (auto& fp : tr.feature_points) fp.d = d[j++];
+}
+
+// a product of estimated transforms: back onto SO(3) (convert() does not normalise, definitions.cpp:14-28)
+inline EigenPose normalisedPrior(const EigenPose& prior) {
+    Pose q = convert(prior);
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) q[i] /= n;
+    return convert(q);
+}
+
+// the last frame's pose and motion of a sequence: the constant-velocity prior, and what every frame leaves behind
+struct MotionState {
+    EigenPose last_pose = EigenPose::Identity(), last_motion = EigenPose::Identity();
+    bool have_last = false, have_motion = false;
+    TimestampNSec last_stamp = 0;
+    // constant velocity from the last two poses; before there are two: straight ahead at prior_speed
+    EigenPose constantVelocityPrior(const StreamParams& p, TimestampNSec stamp) const {
+        if (have_motion) return last_motion * last_pose;
+        EigenPose m = EigenPose::Identity();
+        m.t[0] = -p.prior_speed * (convert(stamp) - convert(last_stamp));  // new vehicle <- old vehicle
+        return m * last_pose;
+    }
+    void advance(const EigenPose& pose, TimestampNSec stamp) {
+        if (have_last) last_motion = pose * last_pose.inverse();
+        have_motion = have_last;
+        last_pose = pose;
+        last_stamp = stamp;
+        have_last = true;
+    }
+};
+
+// five_point::motionUnscaled (five_point.hpp:650-671, helpers::getMotionUnscaled, general_helpers.hpp:209-231) in three steps, so that
+// the estimator of its middle line can be the host's, limo_five_point or one frame of limo_five_point_batch: matches and the mean-flow
+// gate (fivePointQuery), the estimate (query.estimate says whether one is wanted), the scaling by speed x dt and the frame changes
+// (fivePointUnscaled).
+struct FivePointQuery {
+    std::vector<Vector2d> last_points, cur_points;
+    EigenPose cam_t0_t1 = EigenPose::Identity();  // camera at t0 <- camera at t1: what stands without an estimate
+    bool estimate = false;
+};
+inline void fivePointQuery(const Tracklets& tracklets, TimestampNSec stamp_last_kf, TimestampNSec stamp_cur, FivePointQuery& q) {
+    q.last_points.clear(), q.cur_points.clear();
+    five_point::matches(tracklets, stamp_last_kf, stamp_cur, {23, 24, 25, 26}, q.last_points, q.cur_points);
+    q.cam_t0_t1 = EigenPose::Identity();
+    q.cam_t0_t1.t[2] = 1.;
+    q.estimate = !q.last_points.empty() && five_point::meanFlow(q.last_points, q.cur_points) >= 5.;
+    if (!q.estimate && !q.last_points.empty()) q.cam_t0_t1.t[2] = 0.;  // "not enough flow": calcMotion5Point zeroes the translation before it returns (:118-121)
+}
+// (calcMotion5Point: findEssentialMat(points1 = cur, points0 = last), recoverPose(E, cur, last): x_last = R x_cur + t)
+inline five_point::Motion fivePointOnHost(const FivePointQuery& q, const Camera& camera, uint64_t seed) {
+    return five_point::estimateMotion(q.cur_points, q.last_points, camera.focal_length, camera.principal_point, 0.999, 2.0, seed);
+}
+inline limo_five_point_frame fivePointFrame(const FivePointQuery& q, uint64_t seed) {
+    static_assert(sizeof(Vector2d) == 2 * sizeof(double), "Vector2d is two doubles: a point list is the [n*2] array of the C-ABI");
+    limo_five_point_frame fr;
+    fr.n = (int32_t)std::min(q.cur_points.size(), q.last_points.size());
+    fr.pts_a = fr.n ? &q.cur_points[0].v[0] : nullptr;
+    fr.pts_b = fr.n ? &q.last_points[0].v[0] : nullptr;
+    fr.seed = seed;
+    return fr;
+}
+inline five_point::Motion fivePointMotion(const limo_five_point_motion& mo) {
+    five_point::Motion m;
+    m.ok = mo.ok != 0;
+    m.inliers = mo.inliers;
+    m.in_front = mo.in_front;
+    m.samples = mo.samples;
+    for (int i = 0; i < 9; ++i) {
+        m.E[i] = mo.E[i];
+        m.R[i] = mo.R[i];
+    }
+    for (int i = 0; i < 3; ++i) m.t[i] = mo.t[i];
+    return m;
+}
+inline EigenPose fivePointUnscaled(const StreamParams& p, const Camera& camera, const FivePointQuery& q, const five_point::Motion* m, TimestampNSec stamp_last_kf,
+                                   TimestampNSec stamp_cur) {
+    EigenPose cam_t0_t1 = q.cam_t0_t1;
+    if (m && m->ok) {
+        for (int i = 0; i < 9; ++i) cam_t0_t1.R[i] = m->R[i];
+        for (int i = 0; i < 3; ++i) cam_t0_t1.t[i] = m->t[i];
+    }
+    const double dt = convert(stamp_cur) - convert(stamp_last_kf);
+    const double n = std::sqrt(cam_t0_t1.t[0] * cam_t0_t1.t[0] + cam_t0_t1.t[1] * cam_t0_t1.t[1] + cam_t0_t1.t[2] * cam_t0_t1.t[2]);
+    for (int i = 0; i < 3; ++i) cam_t0_t1.t[i] = cam_t0_t1.t[i] / std::max(0.0001, n) * p.prior_speed * dt;
+    const EigenPose T_camera_vehicle = camera.getEigenPose();
+    return T_camera_vehicle.inverse() * cam_t0_t1.inverse() * T_camera_vehicle;
+}
+// mono_lidar.cpp:157-186: the unscaled motion since the last keyframe gets the length speed of the last two keyframes x time since the
+// last one (prior_speed, already applied, while there is only one keyframe) and is applied to the last keyframe's pose.
+inline EigenPose fivePointPrior(const BundleAdjusterKeyframes& ba, TimestampNSec stamp, EigenPose motion) {
+    const Keyframe& last_kf = ba.getKeyframe();
+    const auto kfs = ba.getSortedActiveKeyframePtrs();
+    if (kfs.size() > 1) {
+        const Keyframe &k1 = *kfs[kfs.size() - 1], &k0 = *kfs[kfs.size() - 2];
+        const double speed = (k1.getEigenPose() * k0.getEigenPose().inverse()).translation().norm() / (convert(k1.timestamp_) - convert(k0.timestamp_));
+        const double n = std::sqrt(motion.t[0] * motion.t[0] + motion.t[1] * motion.t[1] + motion.t[2] * motion.t[2]);
+        for (int i = 0; i < 3; ++i) motion.t[i] = motion.t[i] / std::max(0.0001, n) * speed * (convert(stamp) - convert(k1.timestamp_));
+    }
+    return motion * (kfs.empty() ? last_kf.getEigenPose() : kfs.back()->getEigenPose());
+}
+
+// bundle adjustment every time_between_keyframes, whether or not THIS frame became a keyframe (:245-246)
+inline bool solveDue(const StreamParams& p, const BundleAdjusterKeyframes& ba, double now_sec, double last_solved_sec) {
+    return ba.keyframes_.size() > 2 && now_sec - last_solved_sec > 0.98 * p.time_between_keyframes_sec;
+}
+
+// LIMO_STREAM_TRACE=1: one line per adjustPoseOnly / solve with the resulting pose at full precision (two drives on
+// different back ends are compared call by call with it)
+inline void trace(const BundleAdjusterKeyframes& ba, const char* what, TimestampNSec stamp, const Pose& p, double cost) {
+    static const bool on = std::getenv("LIMO_STREAM_TRACE") != nullptr;
+    if (on) {
+        uint64_t h = 1469598103934665603ull;  // FNV-1a over the selected ids: two drives select the same SET iff the hashes agree
+        for (const auto& id : ba.selected_landmark_ids_) h = (h ^ (uint64_t)id) * 1099511628211ull;
+        std::fprintf(stderr, "trace %s %llu cost %.17g pose %.17g %.17g %.17g %.17g %.17g %.17g %.17g selected %zu set %016llx\n", what,
+                     (unsigned long long)stamp, cost, p[0], p[1], p[2], p[3], p[4], p[5], p[6], ba.selected_landmark_ids_.size(), (unsigned long long)h);
+    }
+}
+
+}  // namespace stream_detail
+
 class StreamDriver {
 public:
     struct Stats {
@@ -107,38 +355,7 @@ public:
     };
 
     StreamDriver(const StreamParams& p, Camera::Ptr camera, const EigenPose& T_camera_lidar) : p_(p), camera_(camera), T_cam_lidar_(T_camera_lidar) {
-        ba_.set_solver_time(p.solver_time_sec);
-        selector_.addScheme(KeyframeRejectionSchemeFlow::createConst(p.min_median_flow));
-        selector_.addScheme(KeyframeSelectionSchemePose::createConst(p.critical_rotation_difference));
-        selector_.addScheme(KeyframeSparsificationSchemeTime::createConst(p.time_between_keyframes_sec * 1e9));
-        LandmarkSparsificationSchemeVoxel::Parameters vp;
-        vp.max_num_landmarks_near = p.max_number_landmarks_near_bin;
-        vp.max_num_landmarks_middle = p.max_number_landmarks_middle_bin;
-        vp.max_num_landmarks_far = p.max_number_landmarks_far_bin;
-        vp.voxel_size_xyz = p.voxel_size_xyz;
-        vp.roi_far_xyz = {{p.roi_far, p.roi_far, p.roi_far}};
-        vp.roi_middle_xyz = {{p.roi_middle, p.roi_middle, p.roi_middle}};
-        ba_.landmark_selector_->addScheme(LandmarkSparsificationSchemeVoxel::createConst(vp));
-        LandmarkSelectionSchemeAddDepth::Parameters ap;  // "depth assurance" (:409-426)
-        if (p.add_depth_landmarks_newest > 0)
-            ap.params_per_keyframe.push_back(std::make_tuple(0, p.add_depth_landmarks_newest, [](const Landmark::ConstPtr& lm) { return lm->has_measured_depth; },
-                                                             [](const Measurement& m, const Vector3d&) { return m.d; }));
-        for (int i = 0; i < p.max_size_optimization_window && p.add_ground_landmarks_per_keyframe > 0; ++i)
-            ap.params_per_keyframe.push_back(std::make_tuple(i, p.add_ground_landmarks_per_keyframe, [](const Landmark::ConstPtr& lm) { return lm->is_ground_plane; },
-                                                             [](const Measurement&, const Vector3d& local) { return (float)local.norm(); }));
-        ba_.landmark_selector_->addScheme(LandmarkSelectionSchemeAddDepth::createConst(ap));
-        if (p.landmark_selection_on_device) {  // the same wiring as limo_select_params (the host schemes above stay: they take over when the call is refused)
-            limo_select_params sp{};
-            for (int i = 0; i < 3; ++i) sp.voxel_size_xyz[i] = p.voxel_size_xyz[i];
-            sp.roi_far = p.roi_far, sp.roi_middle = p.roi_middle;
-            sp.max_near = p.max_number_landmarks_near_bin, sp.max_middle = p.max_number_landmarks_middle_bin, sp.max_far = p.max_number_landmarks_far_bin;
-            std::vector<limo_select_add> add;
-            if (p.add_depth_landmarks_newest > 0) add.push_back({0, p.add_depth_landmarks_newest, LIMO_SELECT_HAS_DEPTH, LIMO_SELECT_KEY_MEASURED_DEPTH});
-            for (int i = 0; i < p.max_size_optimization_window && p.add_ground_landmarks_per_keyframe > 0; ++i)
-                add.push_back({i, p.add_ground_landmarks_per_keyframe, LIMO_SELECT_IS_GROUND, LIMO_SELECT_KEY_RANGE});
-            sp.n_add = (int32_t)add.size(), sp.add = add.data();
-            ba_.setDeviceSelection(&sp);
-        }
+        stream_detail::configureSequence(p, ba_, selector_);
         int dev = 0;  // LIMO_DEVICE: the GPU of this sequence (one process per GPU and sequence, scripts/stream_replicas.py)
         if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
         if (limo_ctx_create(dev, &ctx_) != LIMO_OK) throw std::runtime_error("StreamDriver: no HIP device (limo_ctx_create)");
@@ -222,7 +439,7 @@ public:
         const auto t_begin = clk::now();
         waitForDepthThread();  // (it may be writing into `message`)
         Tracklets tracklets(std::move(message));
-        if (tracklets.stamps.empty()) return last_pose_;  // (:98-104)
+        if (tracklets.stamps.empty()) return motion_.last_pose;  // (:98-104)
         // what the depth thread prepared belongs to this message iff stamp, track count and point count agree (a copy of the announced
         // message is as good as the object itself; anything else is assigned here and the prepared depths are dropped)
         size_t n_points = 0;
@@ -256,13 +473,8 @@ public:
             is_keyframe = true;
         } else {
             EigenPose prior = external_prior ? *external_prior
-                              : p_.motion_prior == StreamParams::MotionPrior::FivePoint ? fivePointPrior(stamp, tracklets) : constantVelocityPrior(stamp);
-            {   // a product of estimated transforms: back onto SO(3) (convert() does not normalise, definitions.cpp:14-28)
-                Pose q = convert(prior);
-                const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-                for (int i = 0; i < 4; ++i) q[i] /= n;
-                prior = convert(q);
-            }
+                              : p_.motion_prior == StreamParams::MotionPrior::FivePoint ? fivePointPrior(stamp, tracklets) : motion_.constantVelocityPrior(p_, stamp);
+            prior = stream_detail::normalisedPrior(prior);
             const auto t_kf = clk::now();
             auto cur = std::make_shared<Keyframe>(stamp, tracklets, camera_, prior, Keyframe::FixationStatus::None, ground_plane);
             cur->freezeMeasurements();  // (as above: built once per keyframe, kept for its life in the window)
@@ -289,8 +501,7 @@ public:
             stats_.sec_push += std::chrono::duration<double>(clk::now() - t1).count();
             is_keyframe = !selected.empty();
             const double now_sec = convert(stamp);
-            // bundle adjustment every time_between_keyframes, whether or not THIS frame became a keyframe (:245-246)
-            if (ba_.keyframes_.size() > 2 && now_sec - last_solved_sec_ > 0.98 * p_.time_between_keyframes_sec) {
+            if (stream_detail::solveDue(p_, ba_, now_sec, last_solved_sec_)) {
                 const auto t_w = clk::now();
                 ba_.deactivateKeyframes(p_.min_number_connecting_landmarks, 3, p_.max_size_optimization_window);
                 const auto t_w1 = clk::now();
@@ -311,11 +522,7 @@ public:
             // the optimised pose if the frame became a keyframe, its prior otherwise (:281-294)
             if (ba_.getKeyframe().timestamp_ == stamp) pose = ba_.getKeyframe().getEigenPose();
         }
-        if (have_last_) last_motion_ = pose * last_pose_.inverse();
-        have_motion_ = have_last_;
-        last_pose_ = pose;
-        last_stamp_ = stamp;
-        have_last_ = true;
+        motion_.advance(pose, stamp);
         ++stats_.frames;
         stats_.keyframes += is_keyframe;
         poses_.push_back(pose);
@@ -345,69 +552,29 @@ public:
     limo_depth_params& depthParams() { return depth_params_; }
 
 private:
-    // LIMO_STREAM_TRACE=1: one line per adjustPoseOnly / solve with the resulting pose at full precision (two drives on
-    // different back ends are compared call by call with it)
-    void trace(const char* what, TimestampNSec stamp, const Pose& p, double cost) const {
-        static const bool on = std::getenv("LIMO_STREAM_TRACE") != nullptr;
-        if (on) {
-            uint64_t h = 1469598103934665603ull;  // FNV-1a over the selected ids: two drives select the same SET iff the hashes agree
-            for (const auto& id : ba_.selected_landmark_ids_) h = (h ^ (uint64_t)id) * 1099511628211ull;
-            std::fprintf(stderr, "trace %s %llu cost %.17g pose %.17g %.17g %.17g %.17g %.17g %.17g %.17g selected %zu set %016llx\n", what,
-                         (unsigned long long)stamp, cost, p[0], p[1], p[2], p[3], p[4], p[5], p[6], ba_.selected_landmark_ids_.size(), (unsigned long long)h);
-        }
-    }
+    void trace(const char* what, TimestampNSec stamp, const Pose& p, double cost) const { stream_detail::trace(ba_, what, stamp, p, cost); }
     // mono_lidar.cpp:157-186: direction of the motion since the last keyframe from the five-point algorithm (straight ahead
     // when the image flow is too small for it), length = speed of the last two keyframes x time since the last one
-    // (prior_speed while there is only one keyframe), applied to the last keyframe's pose.
+    // (prior_speed while there is only one keyframe), applied to the last keyframe's pose.  The steps are stream_detail's; the estimator
+    // of the middle one is chosen by fivePointOnDevice().
     EigenPose fivePointPrior(TimestampNSec stamp, const Tracklets& tracklets) {
-        const Keyframe& last_kf = ba_.getKeyframe();
-        EigenPose motion = motionUnscaled(stamp, last_kf.timestamp_, tracklets, (uint64_t)stamp);
-        const auto kfs = ba_.getSortedActiveKeyframePtrs();
-        if (kfs.size() > 1) {
-            const Keyframe &k1 = *kfs[kfs.size() - 1], &k0 = *kfs[kfs.size() - 2];
-            const double speed = (k1.getEigenPose() * k0.getEigenPose().inverse()).translation().norm() / (convert(k1.timestamp_) - convert(k0.timestamp_));
-            const double n = std::sqrt(motion.t[0] * motion.t[0] + motion.t[1] * motion.t[1] + motion.t[2] * motion.t[2]);
-            for (int i = 0; i < 3; ++i) motion.t[i] = motion.t[i] / std::max(0.0001, n) * speed * (convert(stamp) - convert(k1.timestamp_));
-        }
-        return motion * (kfs.empty() ? last_kf.getEigenPose() : kfs.back()->getEigenPose());
-    }
-    // five_point::motionUnscaled (five_point.hpp:650-671, helpers::getMotionUnscaled, general_helpers.hpp:209-231) with the estimator of
-    // its middle line chosen by fivePointOnDevice(): matches, the mean-flow gate, the scaling by speed x dt and the frame changes are
-    // its statements, written here once for both estimators.
-    EigenPose motionUnscaled(TimestampNSec stamp_cur, TimestampNSec stamp_last_kf, const Tracklets& tracklets, uint64_t seed) {
-        std::vector<Vector2d> last_points, cur_points;
-        five_point::matches(tracklets, stamp_last_kf, stamp_cur, {23, 24, 25, 26}, last_points, cur_points);
-        EigenPose cam_t0_t1 = EigenPose::Identity();  // camera at t0 <- camera at t1
-        cam_t0_t1.t[2] = 1.;
-        if (!last_points.empty() && five_point::meanFlow(last_points, cur_points) >= 5.) {
-            // calcMotion5Point: findEssentialMat(points1 = cur, points0 = last), recoverPose(E, cur, last): x_last = R x_cur + t
+        const TimestampNSec stamp_last_kf = ba_.getKeyframe().timestamp_;
+        stream_detail::fivePointQuery(tracklets, stamp_last_kf, stamp, five_point_query_);
+        if (five_point_query_.estimate) {
             const auto t0 = std::chrono::steady_clock::now();
             const bool on_device = fivePointOnDevice();
-            const five_point::Motion m = on_device ? estimateMotionOnDevice(cur_points, last_points, seed)
-                                                   : five_point::estimateMotion(cur_points, last_points, camera_->focal_length, camera_->principal_point,
-                                                                                0.999, 2.0, seed);
+            last_five_point_ = on_device ? estimateMotionOnDevice(five_point_query_, (uint64_t)stamp) : stream_detail::fivePointOnHost(five_point_query_, *camera_, (uint64_t)stamp);
             ++stats_.five_point_calls;
             stats_.five_point_device_calls += on_device;
             stats_.sec_five_point += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            last_five_point_ = m;
-            if (m.ok) {
-                for (int i = 0; i < 9; ++i) cam_t0_t1.R[i] = m.R[i];
-                for (int i = 0; i < 3; ++i) cam_t0_t1.t[i] = m.t[i];
-            }
-        } else if (!last_points.empty()) {
-            cam_t0_t1.t[2] = 0.;  // "not enough flow": calcMotion5Point zeroes the translation before it returns (:118-121)
         }
-        const double dt = convert(stamp_cur) - convert(stamp_last_kf);
-        const double n = std::sqrt(cam_t0_t1.t[0] * cam_t0_t1.t[0] + cam_t0_t1.t[1] * cam_t0_t1.t[1] + cam_t0_t1.t[2] * cam_t0_t1.t[2]);
-        for (int i = 0; i < 3; ++i) cam_t0_t1.t[i] = cam_t0_t1.t[i] / std::max(0.0001, n) * p_.prior_speed * dt;
-        const EigenPose T_camera_vehicle = camera_->getEigenPose();
-        return T_camera_vehicle.inverse() * cam_t0_t1.inverse() * T_camera_vehicle;
+        const EigenPose motion = stream_detail::fivePointUnscaled(p_, *camera_, five_point_query_, five_point_query_.estimate ? &last_five_point_ : nullptr, stamp_last_kf, stamp);
+        return stream_detail::fivePointPrior(ba_, stamp, motion);
     }
     bool fivePointOnDevice() const { return p_.five_point_on_device && &limo_five_point != nullptr && &limo_five_point_default_params != nullptr; }
     // limo_five_point with the arguments motionUnscaled gives estimateMotion (probability 0.999, 2 px, 1000 samples).  It runs on a
     // context of its own: the driver's first context belongs to the depth thread while a frame is in flight (DepthAhead::Thread).
-    five_point::Motion estimateMotionOnDevice(const std::vector<Vector2d>& pts_a, const std::vector<Vector2d>& pts_b, uint64_t seed) {
-        static_assert(sizeof(Vector2d) == 2 * sizeof(double), "Vector2d is two doubles: a point list is the [n*2] array of the C-ABI");
+    five_point::Motion estimateMotionOnDevice(const stream_detail::FivePointQuery& q, uint64_t seed) {
         if (!five_point_ctx_) {
             int dev = 0;
             if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
@@ -415,46 +582,13 @@ private:
         }
         limo_five_point_params prm;
         limo_five_point_default_params(&prm);
-        limo_five_point_frame fr;
-        fr.n = (int32_t)std::min(pts_a.size(), pts_b.size());
-        fr.pts_a = fr.n ? &pts_a[0].v[0] : nullptr;
-        fr.pts_b = fr.n ? &pts_b[0].v[0] : nullptr;
-        fr.seed = seed;
+        const limo_five_point_frame fr = stream_detail::fivePointFrame(q, seed);
         limo_five_point_motion mo;
         const int rc = limo_five_point(five_point_ctx_, &fr, camera_->focal_length, camera_->principal_point[0], camera_->principal_point[1], &prm, &mo, nullptr);
         if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_five_point: ") + limo_last_error(five_point_ctx_));
-        five_point::Motion m;
-        m.ok = mo.ok != 0;
-        m.inliers = mo.inliers;
-        m.in_front = mo.in_front;
-        m.samples = mo.samples;
-        for (int i = 0; i < 9; ++i) {
-            m.E[i] = mo.E[i];
-            m.R[i] = mo.R[i];
-        }
-        for (int i = 0; i < 3; ++i) m.t[i] = mo.t[i];
-        return m;
+        return stream_detail::fivePointMotion(mo);
     }
-    // constant velocity from the last two poses; before there are two: straight ahead at prior_speed
-    EigenPose constantVelocityPrior(TimestampNSec stamp) const {
-        if (have_motion_) return last_motion_ * last_pose_;
-        EigenPose m = EigenPose::Identity();
-        m.t[0] = -p_.prior_speed * (convert(stamp) - convert(last_stamp_));  // new vehicle <- old vehicle
-        return m * last_pose_;
-    }
-
-    // pixel coordinates and ground flags of the newest point of every track, as limo_depth_estimate wants them
-    void stageFeatures(const Tracklets& ts) {
-        const size_t n = ts.tracks.size();
-        uv_.resize(2 * n);
-        ground_.resize(n);
-        for (size_t i = 0; i < n; ++i) {
-            uv_[2 * i] = ts.tracks[i].feature_points[0].u;
-            uv_[2 * i + 1] = ts.tracks[i].feature_points[0].v;
-            ground_[i] = 0;
-            for (int l : p_.ground_labels) ground_[i] |= ts.tracks[i].label == l;
-        }
-    }
+    void stageFeatures(const Tracklets& ts) { stream_detail::stageFeatures(p_, ts, uv_, ground_); }
 
     // ---- the depth thread (StreamParams::DepthAhead::Thread): one job at a time = assignDepth of the announced frame
     enum class JobState { Idle, Pending, Running, Exit };
@@ -535,11 +669,7 @@ private:
     // other core's cache, which cost as much as the thread saved.)
     void computeDepths(const Tracklets& ts, const float* cloud, size_t n_pts, std::vector<float>& out) {
         const size_t n = ts.tracks.size();
-        // A frame may come here twice (announced to the depth thread, then handed to process() with another message for the same
-        // stamp, or announced and never processed): the statistics count a stamp once and the per-track history REPLACES the
-        // entry of a stamp it already holds instead of pushing a second one.
-        const bool counted = counted_any_ && !ts.stamps.empty() && counted_stamp_ == ts.stamps.front();
-        if (!counted) stats_.features += (int)n;
+        if (history_.counts(ts)) stats_.features += (int)n;
         const bool from_sweep = p_.assign_depth && cloud && n_pts && n;
         if (from_sweep) {
             depth_.assign(n, -1.f);
@@ -560,56 +690,11 @@ private:
         }
         // remember this frame's depth per track, fill the history points from the memory (ring of the last frames)
         const auto t_hist = std::chrono::steady_clock::now();
-        const TimestampNSec stamp = ts.stamps.front();
-        out.clear();
-        for (size_t i = 0; i < n; ++i) {
-            const Tracklet& tr = ts.tracks[i];
-            if (tr.feature_points.empty()) continue;
-            const float d0 = (from_sweep && tr.feature_points[0].d < 0.f) ? depth_[i] : tr.feature_points[0].d;  // (a depth the caller knows stays)
-            out.push_back(d0);
-            History& h = history_[tr.id];
-            if (h.n > 0 && h.stamp[(h.head - 1) & (History::kDepth - 1)] == stamp) {
-                h.d[(h.head - 1) & (History::kDepth - 1)] = d0;
-            } else {
-                h.stamp[h.head] = stamp;
-                h.d[h.head] = d0;
-                h.head = (h.head + 1) & (History::kDepth - 1);
-                h.n = std::min<int>(History::kDepth, h.n + 1);
-            }
-            for (size_t k = 1; k < tr.feature_points.size(); ++k) {
-                float dk = tr.feature_points[k].d;
-                if (dk < 0.f && k < ts.stamps.size()) {
-                    // (a track seen in consecutive frames has the entry of stamps[k] k places behind the newest: looked at first; stamps
-                    // are unique inside a history, so the scan finds the same entry or none)
-                    const int e = (h.head - 1 - (int)k) & (History::kDepth - 1);
-                    if ((int)k < h.n && h.stamp[e] == ts.stamps[k]) {
-                        dk = h.d[e];
-                    } else {
-                        for (int j = 0; j < h.n; ++j) {
-                            const int e2 = (h.head - 1 - j) & (History::kDepth - 1);
-                            if (h.stamp[e2] == ts.stamps[k]) dk = h.d[e2];
-                        }
-                    }
-                }
-                out.push_back(dk);
-            }
-            if (!counted) stats_.features_with_depth += d0 > 0.f;
-        }
-        counted_any_ = true;
-        counted_stamp_ = stamp;
+        history_.record(ts, from_sweep ? depth_.data() : nullptr, out, stats_.features_with_depth);
         stats_.sec_depth_history += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_hist).count();
-        if (++frames_since_gc_ >= 64) {  // forget tracks that ended
-            frames_since_gc_ = 0;
-            const TimestampNSec oldest = ts.stamps.back();
-            for (auto it = history_.begin(); it != history_.end();)
-                it = it->second.stamp[(it->second.head - 1) & (History::kDepth - 1)] < oldest ? history_.erase(it) : std::next(it);
-        }
+        history_.forgetEndedTracks(ts);
     }
-    static void applyDepths(Tracklets& ts, const std::vector<float>& d) {
-        size_t j = 0;
-        for (auto& tr : ts.tracks)
-            for (auto& fp : tr.feature_points) fp.d = d[j++];
-    }
+    static void applyDepths(Tracklets& ts, const std::vector<float>& d) { stream_detail::applyDepths(ts, d); }
 
     StreamParams p_;
     Camera::Ptr camera_;
@@ -619,14 +704,7 @@ private:
     limo_ctx* ctx_ = nullptr;
     limo_ctx* five_point_ctx_ = nullptr;  // of estimateMotionOnDevice, made at its first call
     limo_depth_params depth_params_;
-    struct History {  // the depths this driver assigned to a track in the last frames it was seen in (ring, newest at head - 1)
-        static constexpr int kDepth = 16;
-        TimestampNSec stamp[kDepth];
-        float d[kDepth];
-        int head = 0, n = 0;
-    };
-    std::unordered_map<unsigned long, History> history_;
-    int frames_since_gc_ = 0;
+    stream_detail::DepthHistory history_;  // the depths this driver assigned to a track in the last frames it was seen in
     std::vector<float> uv_, depth_, point_d_;
     std::vector<uint8_t> ground_;
     bool prefetch_open_ = false;  // prefetchDepth: a limo_depth_estimate_begin whose frame process() has not seen yet
@@ -640,8 +718,6 @@ private:
     bool job_has_stamp_ = false;  // identity of the job's frame, read from the message when the job starts
     TimestampNSec job_stamp_ = 0;
     size_t job_tracks_ = 0;
-    TimestampNSec counted_stamp_ = 0;  // the last frame whose features went into stats_ (computeDepths is idempotent per stamp)
-    bool counted_any_ = false;
     const float* job_cloud_ = nullptr;
     size_t job_n_pts_ = 0;
     std::exception_ptr job_error_;
@@ -652,9 +728,8 @@ private:
     const float* next_cloud_ = nullptr;
     size_t next_n_pts_ = 0;
     std::vector<EigenPose> poses_;
-    EigenPose last_pose_ = EigenPose::Identity(), last_motion_ = EigenPose::Identity();
-    bool have_last_ = false, have_motion_ = false;
-    TimestampNSec last_stamp_ = 0;
+    stream_detail::MotionState motion_;
+    stream_detail::FivePointQuery five_point_query_;
     double last_solved_sec_ = -1e30;
     std::string last_summary_;
     Stats stats_;

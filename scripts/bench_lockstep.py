@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Lock-step drive against single drives: aggregate frames/s of `limo_stream --sequences N` for N in 1, 4, 16, 64 with the default
+stage flags and with every stage on the device (--select-device --five-point-prior --five-point-device), against N single drives of
+the PARENT commit's limo_stream run one after another (the only way to run N sequences before the lock-step driver); and the single
+drive of this commit against the parent's, runs alternated, to show what the split-phase shim costs the single driver.
+
+  scripts/bench_lockstep.py --build-parent REV      (on the build machine: needs git) compiles REV's apps/limo_stream + shim against the
+                                                    liblimo_hip.so of the work tree into tests/cpp/_build/limo_stream_gpu_parent
+  scripts/bench_lockstep.py [--frames 200] [--sizes 1,4,16,64] [--repeats 3] [--out profiles/lockstep.json]   (on the GPU machine)
+
+The kernels are the same in both programs (this comparison is only fair while limo_amd/csrc is unchanged between REV and the work
+tree: --build-parent refuses otherwise).  Every process runs under its own time limit; a failing run ends the script.  The table goes to
+stdout, everything measured to --out as JSON."""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, "tests", "cpp", "_build")
+EXE = os.path.join(BUILD, "limo_stream_gpu")
+PARENT = os.path.join(BUILD, "limo_stream_gpu_parent")
+DEVICE_FLAGS = ["--select-device", "--five-point-prior", "--five-point-device"]
+STAGES = ("depth", "five_point", "pose_only", "landmark_init", "select", "solve")
+
+
+def build_parent(rev):
+    changed = subprocess.run(["git", "diff", "--stat", rev, "--", "limo_amd/csrc", "include/limo_hip.h"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
+    if changed:
+        sys.exit("the kernels differ between %s and the work tree: the two programs would not run the same library\n%s" % (rev, changed))
+    tmp = tempfile.mkdtemp(prefix="limo_parent.")
+    try:
+        tar = subprocess.Popen(["git", "archive", rev, "apps", "limo_amd/kba", "limo_amd/csrc", "include"], cwd=ROOT, stdout=subprocess.PIPE)
+        subprocess.check_call(["tar", "-x", "-C", tmp], stdin=tar.stdout)
+        assert tar.wait() == 0
+        libdir = os.path.join(ROOT, "limo_amd", "lib")
+        os.makedirs(BUILD, exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-pthread", "-w", "-o", PARENT, os.path.join(tmp, "apps", "limo_stream", "limo_stream.cpp"),
+                               os.path.join(tmp, "limo_amd", "kba", "bundle_adjuster_keyframes.cpp"), "-L" + libdir, "-llimo_hip", "-Wl,-rpath," + os.path.abspath(libdir)])
+    finally:
+        shutil.rmtree(tmp)
+    open(PARENT + ".rev", "w").write(subprocess.run(["git", "rev-parse", rev], cwd=ROOT, capture_output=True, text=True, check=True).stdout)
+    print(PARENT)
+
+
+def run(cmd, limit):
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
+    wall = time.perf_counter() - t0
+    if r.returncode != 0:
+        sys.exit("%s\nexit %d\n%s\n%s" % (" ".join(cmd), r.returncode, r.stdout[-2000:], r.stderr[-4000:]))
+    return r.stdout, wall
+
+
+def single(exe, frames, seed, flags, limit):
+    """One single drive: (fps of the pipeline as the program reports it, seconds of pipeline time, wall seconds of the process)."""
+    out, wall = run([exe, "--frames", str(frames), "--az", "2000", "--seed", str(seed), "--quiet"] + flags, limit)
+    kv = {l.split()[0]: float(l.split()[1]) for l in out.splitlines() if len(l.split()) == 2 and l.split()[0] in ("frames", "fps")}
+    return kv["fps"], kv["frames"] / kv["fps"], wall
+
+
+def lockstep(exe, n, frames, flags, limit):
+    out, wall = run([exe, "--sequences", str(n), "--frames", str(frames), "--az", "2000", "--seed", "7", "--quiet"] + flags, limit)
+    info = json.loads(out.strip().splitlines()[-1])
+    info["wall_s"] = wall
+    del info["per_sequence"]
+    return info
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--build-parent", metavar="REV")
+    ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--sizes", default="1,4,16,64")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--baseline-drives", type=int, default=4, help="single drives of the parent timed per flag set (seeds 7, 8, ...): N drives one after another take N x their mean")
+    ap.add_argument("--limit", type=int, default=240, help="time limit of one process, seconds")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lockstep.json"))
+    a = ap.parse_args()
+    if a.build_parent:
+        return build_parent(a.build_parent)
+    for exe in (EXE, PARENT):
+        if not os.path.exists(exe):
+            sys.exit("%s is missing (build(); scripts/bench_lockstep.py --build-parent REV)" % exe)
+    res = {"frames": a.frames, "parent_rev": open(PARENT + ".rev").read().strip() if os.path.exists(PARENT + ".rev") else None, "single": {}, "baseline": {}, "lockstep": []}
+    # 1. the single drive: this commit against the parent, alternated
+    runs = {"parent": [], "this": []}
+    for _ in range(a.repeats):
+        for name, exe in (("parent", PARENT), ("this", EXE)):
+            runs[name].append(single(exe, a.frames, 7, [], a.limit)[0])
+    res["single"] = {k: {"fps": v, "median": statistics.median(v)} for k, v in runs.items()}
+    print("single drive, %d frames, frames/s (alternated): parent %s | this commit %s" % (a.frames, " ".join("%.1f" % x for x in runs["parent"]), " ".join("%.1f" % x for x in runs["this"])))
+    # 2. the baseline: single drives of the parent, one after another (seconds of pipeline time per drive; N drives take N x that)
+    for name, flags in (("default", []), ("device", DEVICE_FLAGS)):
+        secs = [single(PARENT, a.frames, 7 + i, flags, a.limit)[1] for i in range(a.baseline_drives)]
+        res["baseline"][name] = {"pipeline_s_per_drive": secs, "frames_per_s": a.frames / statistics.mean(secs)}
+        print("baseline (%s flags): %d single drives of the parent one after another: %.1f frames/s" % (name, len(secs), res["baseline"][name]["frames_per_s"]))
+    # 3. the lock-step drive
+    print("%-8s %4s %10s %9s %9s | per tick, ms: %s | host finish" % ("flags", "N", "frames/s", "x base", "ms/tick", " ".join("%-13s" % s for s in STAGES)))
+    for name, flags in (("default", []), ("device", DEVICE_FLAGS)):
+        for n in [int(x) for x in a.sizes.split(",")]:
+            info = lockstep(EXE, n, a.frames, flags, a.limit)
+            info["flags"] = name
+            info["speedup_over_baseline"] = info["frames_per_s"] / res["baseline"][name]["frames_per_s"]
+            res["lockstep"].append(info)
+            ticks = max(1, info["ticks"])
+            per = " ".join("%5.2f+%-7.2f" % (info["stages"][s]["ms_host"] / ticks, info["stages"][s]["ms_abi"] / ticks) for s in STAGES)
+            print("%-8s %4d %10.1f %9.2f %9.2f | host+abi: %s | %.2f" % (name, n, info["frames_per_s"], info["speedup_over_baseline"], info["ms_pipeline"] / ticks, per,
+                                                                    info["ms_host_finish"] / ticks))
+            sys.stdout.flush()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(res, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
