@@ -252,7 +252,7 @@ int run_lockstep(const LockstepOptions& o, StreamParams sp) {
         if (!o.gt_path.empty()) {
             std::ofstream f(o.gt_path + "." + std::to_string(i));
             const EigenPose cv = d.cam->getEigenPose();
-            for (int t = 0; t < d.n_frames; ++t) kitti_io::writePoseRow(f, cv * d.world->origin_veh[t] * cv.inverse());
+            for (int t = 0; t < d.n_frames; ++t) kitti_io::writePoseRow(f, kitti_io::inCameraFrame(cv, d.world->origin_veh[t]));
         }
         const StreamDriver::Stats& ss = driver->sequenceStats(i);
         std::printf("limo_stream: sequence %d (seed %llu, first tick %d): %d frames, %d keyframes, %d solves, %d landmark selections on the device, ATE rmse %.4f m (max %.4f m)\n", i,
@@ -442,8 +442,8 @@ int main(int argc, char** argv) {
     {
         const EigenPose cv = cam->getEigenPose();
         for (int t = 0; t < n_frames; ++t) {
-            gt_rows.push_back(cv * world.origin_veh[t] * cv.inverse());
-            est_rows.push_back(cv * driver.poses()[t].inverse() * cv.inverse());
+            gt_rows.push_back(kitti_io::inCameraFrame(cv, world.origin_veh[t]));
+            est_rows.push_back(kitti_io::inCameraFrame(cv, driver.poses()[t].inverse()));
         }
         if (!gt_path.empty()) {
             std::ofstream f(gt_path);

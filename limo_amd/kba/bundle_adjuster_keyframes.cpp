@@ -194,23 +194,38 @@ BundleAdjusterKeyframes::~BundleAdjusterKeyframes() {
     if (ctx_) limo_ctx_destroy(ctx_);
 }
 
+limo_ctx* createContext() {
+    int dev = 0;
+    if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
+    limo_ctx* ctx = nullptr;
+    const int rc = limo_ctx_create(dev, &ctx);
+    if (rc != LIMO_OK)
+        throw std::runtime_error("limo_ctx_create failed (rc=" + std::to_string(rc) +
+                                 "): the keyframe BA hot path needs the HIP library and an MI355X; there is no CPU fallback");
+    return ctx;
+}
+void checkCall(limo_ctx* ctx, int rc, const char* what) {
+    if (rc != LIMO_OK) throw std::runtime_error(std::string(what) + ": " + limo_last_error(ctx));
+}
+
 limo_ctx* BundleAdjusterKeyframes::context() {
-    if (!ctx_) {
-        int dev = 0;
-        if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
-        const int rc = limo_ctx_create(dev, &ctx_);
-        if (rc != LIMO_OK)
-            throw std::runtime_error("limo_ctx_create failed (rc=" + std::to_string(rc) +
-                                     "): the keyframe BA hot path needs the HIP library and an MI355X; there is no CPU fallback");
-    }
+    if (!ctx_) ctx_ = createContext();
     return ctx_;
 }
+
+namespace {
+struct AddMicros {  // the time of its scope into a slot of BundleAdjusterKeyframes::shim_us_
+    double& us;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~AddMicros() { us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+};
+const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;
+}  // namespace
 
 // The iteration-log entry points are weak references: the shim also links against backends that serve the C-ABI without them (the
 // test backends tests/cpp/oracle_abi.cpp and emu_pipeline.cpp) - there the addresses are null and the shim behaves as "no log".
 #pragma weak limo_ctx_set_iteration_log
 #pragma weak limo_ctx_last_iteration_log
-#pragma weak limo_landmark_select  // (tests/cpp/oracle_abi.cpp and emu_pipeline.cpp have no device selection: solve() then selects on the host)
 
 void BundleAdjusterKeyframes::setIterationLog(limo_ctx* ctx) {
     last_iterations_.clear();
@@ -267,11 +282,14 @@ void BundleAdjusterKeyframes::push(Keyframe&& kf_in) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
     PushJob job;
     preparePush(std::move(kf_in), job);
-    if (!job.ids.empty()) {
-        const int rc = limo_landmark_init(context(), (int32_t)job.ids.size(), job.off.data(), job.rays.data(), job.use_depth.data(), job.pos.data(), job.ok.data());
-        if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_landmark_init: ") + limo_last_error(ctx_));
-    }
+    runPush(job);
     commitPush(job);
+}
+
+void BundleAdjusterKeyframes::runPush(PushJob& job) {
+    if (job.ids.empty()) return;
+    checkCall(context(), limo_landmark_init(context(), (int32_t)job.ids.size(), job.off.data(), job.rays.data(), job.use_depth.data(), job.pos.data(), job.ok.data()),
+              "limo_landmark_init");
 }
 
 // The keyframe enters the window; the rays of every landmark it introduces go into the job (pos / ok sized for the call's results).
@@ -735,8 +753,12 @@ BundleAdjusterKeyframes::LastReport last_report_of(const limo_ba_report& rep) {
 // merge passes of FlatWindow); job.on_device says whether there is a pool to hand to limo_landmark_select[_batch] with job.params and
 // job.out.  commitSelection(job, true) hands the call's result to the selector; (job, false) - no pool, or the call did not return
 // LIMO_OK - runs the host selector.  Either way selected_landmark_ids_ is the selection afterwards.
+// limo_landmark_select is a weak reference: tests/cpp/oracle_abi.cpp and emu_pipeline.cpp have no device selection (the address is null:
+// no job is on_device, the host selector runs).
+#pragma weak limo_landmark_select
 void BundleAdjusterKeyframes::prepareSelection(SelectJob& job) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    AddMicros t{shim_us_.select};
     if (keyframes_.size() < 3) throw NotEnoughKeyframesException(keyframes_.size(), 3);
     // (getActiveLandmarkConstPtrs() as a sorted vector: the selector's schemes read it in this form, no map is built for them)
     LandmarkView& active_lms = job.active_lms;
@@ -798,8 +820,14 @@ void BundleAdjusterKeyframes::prepareSelection(SelectJob& job) {
     job.on_device = true;
 }
 
+bool BundleAdjusterKeyframes::runSelection(SelectJob& job) {
+    AddMicros t{shim_us_.select};
+    return job.on_device && limo_landmark_select(context(), &job.pool, job.params, job.out.data()) == LIMO_OK;
+}
+
 void BundleAdjusterKeyframes::commitSelection(SelectJob& job, bool device_ok) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    AddMicros t{shim_us_.select};
     if (!(device_ok && job.on_device)) {
         selected_landmark_ids_ = landmark_selector_->select(job.active_lms, job.active_kfs);
         return;
@@ -822,6 +850,7 @@ void BundleAdjusterKeyframes::commitSelection(SelectJob& job, bool device_ok) {
 // prepareSolve: the active keyframes and the selected landmarks as job.window (a limo_ba_window over buffers the job owns) and job.opts.
 void BundleAdjusterKeyframes::prepareSolve(WindowJob& job) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    AddMicros t{shim_us_.prepare};
     job.flat = std::make_shared<FlatWindow>();
     FlatWindow& F = *job.flat;
     for (const auto& id : active_keyframe_ids_) F.add_keyframe(*keyframes_.at(id));
@@ -848,42 +877,43 @@ void BundleAdjusterKeyframes::prepareSolve(WindowJob& job) {
 }
 
 // commitSolve: poses, planes and landmarks of the solved window back into the objects, job.report into last_report_; the report string.
+void BundleAdjusterKeyframes::runSolve(WindowJob& job) {
+    limo_ctx* ctx = context();
+    setIterationLog(ctx);
+    int rc;
+    {
+        AddMicros t{shim_us_.call};
+        rc = limo_ba_solve(ctx, job.window, &job.opts, &job.report);
+    }
+    if (rc == LIMO_ERR_NOT_ENOUGH_KF) throw NotEnoughKeyframesException(job.flat->kfs.size(), 3);
+    checkCall(ctx, rc, "limo_ba_solve");
+    collectIterations(ctx, "solve");
+}
+
 std::string BundleAdjusterKeyframes::commitSolve(WindowJob& job) {
-    job.flat->write_back(true);
-    last_report_ = last_report_of(job.report);
+    double write_back = 0.;
+    {
+        AddMicros t{write_back};
+        job.flat->write_back(true);
+        last_report_ = last_report_of(job.report);
+    }
+    if (shim_trace)
+        std::fprintf(stderr, "[shim] solve: %zu active landmarks, %zu selected, %d LM iterations in %d solves: active maps + selection %.0f us, flatten %.0f us, limo_ba_solve %.0f us, write-back %.0f us\n",
+                     active_landmark_ids_.size(), selected_landmark_ids_.size(), job.report.iterations_total, job.report.num_solves, shim_us_.select, shim_us_.prepare,
+                     shim_us_.call, write_back);
+    shim_us_ = ShimTimes{};
     return report_string(job.report, "solve");
 }
 
 std::string BundleAdjusterKeyframes::solve() {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
-    using clk = std::chrono::steady_clock;
-    static const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;  // where the host time of solve() goes
-    const auto t_s0 = clk::now();
     SelectJob sel;
     prepareSelection(sel);
-    const bool on_device = sel.on_device && limo_landmark_select(context(), &sel.pool, sel.params, sel.out.data()) == LIMO_OK;
-    commitSelection(sel, on_device);
-    const auto t_s1 = clk::now();
-
+    commitSelection(sel, runSelection(sel));
     WindowJob job;
     prepareSolve(job);
-    limo_ba_report& rep = job.report;
-    limo_ctx* ctx = context();
-    setIterationLog(ctx);
-    const auto t_s2 = clk::now();
-    const int rc = limo_ba_solve(ctx, job.window, &job.opts, &rep);
-    const auto t_s3 = clk::now();
-    if (rc == LIMO_ERR_NOT_ENOUGH_KF) throw NotEnoughKeyframesException(job.flat->kfs.size(), 3);
-    if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_solve: ") + limo_last_error(ctx));
-    collectIterations(ctx, "solve");
-    std::string summary = commitSolve(job);
-    if (shim_trace) {
-        auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        std::fprintf(stderr, "[shim] solve: %zu active landmarks, %zu selected, %d LM iterations in %d solves: active maps + selection %.0f us, flatten %.0f us, limo_ba_solve %.0f us, write-back %.0f us\n",
-                     active_landmark_ids_.size(), selected_landmark_ids_.size(), rep.iterations_total, rep.num_solves, us(t_s0, t_s1), us(t_s1, t_s2),
-                     us(t_s2, t_s3), us(t_s3, clk::now()));
-    }
-    return summary;
+    runSolve(job);
+    return commitSolve(job);
 }
 
 // ------------------------------------------------------------------------------------------ adjustPoseOnly = preparePoseOnly + limo_ba_adjust_pose_only + commitPoseOnly
@@ -891,6 +921,7 @@ std::string BundleAdjusterKeyframes::solve() {
 // active keyframes (job.has_prior) and job.opts.
 void BundleAdjusterKeyframes::preparePoseOnly(Keyframe& kf, WindowJob& job) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
+    AddMicros t{shim_us_.prepare};
     selected_landmark_ids_ = landmark_selector_->getLastSelection();  // :828
     job.flat = std::make_shared<FlatWindow>();
     FlatWindow& F = *job.flat;
@@ -937,34 +968,38 @@ void BundleAdjusterKeyframes::preparePoseOnly(Keyframe& kf, WindowJob& job) {
 }
 
 // commitPoseOnly: the refined pose (and plane) back into the frame's keyframe, job.report into last_report_; the report string.
+void BundleAdjusterKeyframes::runPoseOnly(WindowJob& job) {
+    limo_ctx* ctx = context();
+    setIterationLog(ctx);
+    {
+        AddMicros t{shim_us_.call};
+        checkCall(ctx, limo_ba_adjust_pose_only(ctx, job.window, job.has_prior ? &job.prior : nullptr, &job.opts, &job.report), "limo_ba_adjust_pose_only");
+    }
+    collectIterations(ctx, "adjustPoseOnly");
+}
+
 std::string BundleAdjusterKeyframes::commitPoseOnly(WindowJob& job) {
-    job.flat->write_back(false);
-    last_report_ = last_report_of(job.report);
-    return report_string(job.report, "adjustPoseOnly");
+    double write_back = 0.;
+    std::string summary;
+    {
+        AddMicros t{write_back};
+        job.flat->write_back(false);
+        last_report_ = last_report_of(job.report);
+        summary = report_string(job.report, "adjustPoseOnly");
+    }
+    if (shim_trace)
+        std::fprintf(stderr, "[shim] adjustPoseOnly: %d landmarks, %d observations: selection copy + flatten + prior %.0f us, limo_ba_adjust_pose_only %.0f us, write-back + summary %.0f us\n",
+                     job.window->n_lm, job.window->n_obs, shim_us_.prepare, shim_us_.call, write_back);
+    shim_us_ = ShimTimes{};
+    return summary;
 }
 
 std::string BundleAdjusterKeyframes::adjustPoseOnly(Keyframe& kf) {
     Keyframe::MeasurementTableScope table_scope;  // (measurement tables are trusted inside one public call: keyframe.hpp)
-    using clk = std::chrono::steady_clock;
-    static const bool shim_trace = std::getenv("LIMO_SHIM_TRACE") != nullptr;
-    const auto t_p1 = clk::now();
     WindowJob job;
     preparePoseOnly(kf, job);
-    limo_ba_report& rep = job.report;
-    limo_ctx* ctx = context();
-    setIterationLog(ctx);
-    const auto t_p2 = clk::now();
-    const int rc = limo_ba_adjust_pose_only(ctx, job.window, job.has_prior ? &job.prior : nullptr, &job.opts, &rep);
-    const auto t_p3 = clk::now();
-    if (rc != LIMO_OK) throw std::runtime_error(std::string("limo_ba_adjust_pose_only: ") + limo_last_error(ctx));
-    collectIterations(ctx, "adjustPoseOnly");
-    std::string summary = commitPoseOnly(job);
-    if (shim_trace) {
-        auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        std::fprintf(stderr, "[shim] adjustPoseOnly: %d landmarks, %d observations: selection copy + flatten + prior %.0f us, limo_ba_adjust_pose_only %.0f us, write-back + summary %.0f us\n",
-                     job.window->n_lm, job.window->n_obs, us(t_p1, t_p2), us(t_p2, t_p3), us(t_p3, clk::now()));
-    }
-    return summary;
+    runPoseOnly(job);
+    return commitPoseOnly(job);
 }
 
 }  // namespace keyframe_bundle_adjustment

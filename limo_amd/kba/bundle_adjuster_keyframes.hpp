@@ -18,6 +18,12 @@ namespace keyframe_bundle_adjustment {
 
 struct FlatWindow;  // a window flattened into the arrays of the C-ABI (bundle_adjuster_keyframes.cpp)
 
+// For every caller of the C-ABI here (this shim, stream_driver.hpp, lockstep_driver.hpp).  createContext: a context on the GPU that
+// LIMO_DEVICE names (default 0: one process per GPU, scripts/stream_replicas.py); throws where there is none - the hot path needs the
+// HIP library and an MI355X, there is no CPU fallback.  checkCall: throws "<what>: <limo_last_error>" unless rc is LIMO_OK.
+limo_ctx* createContext();
+void checkCall(limo_ctx* ctx, int rc, const char* what);
+
 class BundleAdjusterKeyframes {
 public:
     using UPtr = std::unique_ptr<BundleAdjusterKeyframes>;
@@ -96,11 +102,13 @@ public:
     int device_selections_ = 0;  // solve() calls whose selection limo_landmark_select made
 
     // Split-phase forms of push, adjustPoseOnly, the selection in front of solve and solve (not in the reference).  Each method above is
-    // prepare + ONE C-ABI call + commit; a caller that drives several adjusters in lock step (lockstep_driver.hpp) prepares them all,
-    // makes one batched call over the jobs (limo_landmark_init over the concatenated rays, limo_ba_adjust_pose_only_batch,
-    // limo_landmark_select_batch, limo_ba_batch_create / _solve / _download) and commits each.  A job owns every buffer its C-ABI
-    // arguments point into; prepare and commit never touch a limo_ctx, so adjusters of different sequences may be prepared and committed
-    // on different threads while one thread makes the calls.  The caller checks the call's return code before it commits.
+    // prepare + run + commit.  run... makes the job's ONE C-ABI call on this adjuster's own context, with all that belongs to the call:
+    // the iteration log, the exceptions, the host selector where the device refuses the pool.  A caller that drives several adjusters
+    // in lock step (lockstep_driver.hpp) prepares them all, makes one batched call over the jobs in place of the run... pieces
+    // (limo_landmark_init over the concatenated rays, limo_ba_adjust_pose_only_batch, limo_landmark_select_batch, limo_ba_batch_create /
+    // _solve / _download), checks its return code and commits each.  A job owns every buffer its C-ABI arguments point into; prepare
+    // and commit never touch a limo_ctx, so adjusters of different sequences may be prepared and committed on different threads while one
+    // thread makes the calls.
     struct PushJob {  // limo_landmark_init(ids.size(), off, rays, use_depth, pos, ok); ids.empty(): no call
         Keyframe::Ptr kf;
         std::vector<LandmarkId> ids;
@@ -111,6 +119,7 @@ public:
         std::vector<uint8_t> ok;   // [ids.size()]      result
     };
     void preparePush(Keyframe&& kf, PushJob& job);
+    void runPush(PushJob& job);
     void commitPush(PushJob& job);
     struct WindowJob {  // limo_ba_adjust_pose_only(window, has_prior ? &prior : NULL, &opts, &report) / limo_ba_solve(window, &opts, &report)
         std::shared_ptr<FlatWindow> flat;  // the buffers behind `window`
@@ -121,6 +130,7 @@ public:
         limo_ba_report report{};           // result
     };
     void preparePoseOnly(Keyframe& kf, WindowJob& job);
+    void runPoseOnly(WindowJob& job);
     std::string commitPoseOnly(WindowJob& job);
     struct SelectJob {  // on_device: limo_landmark_select(&pool, params, out.data()); else there is nothing to call
         LandmarkView active_lms;
@@ -134,8 +144,10 @@ public:
         std::vector<uint8_t> out;          // result
     };
     void prepareSelection(SelectJob& job);                   // throws NotEnoughKeyframesException as solve() does
+    bool runSelection(SelectJob& job);                       // the device made the selection: commitSelection's device_ok
     void commitSelection(SelectJob& job, bool device_ok);    // device_ok = false: the host selector runs
     void prepareSolve(WindowJob& job);                       // (after commitSelection: flattens selected_landmark_ids_)
+    void runSolve(WindowJob& job);                           // throws NotEnoughKeyframesException as solve() does
     std::string commitSolve(WindowJob& job);
     // LIMO_KBA_DUMP files of this adjuster are named solve_sII_NNNNNN.bin with II = dump_tag_ and its own count (>= 0: a sequence of a
     // lock-step drive); -1: solve_NNNNNN.bin, counted over the process as before
@@ -165,6 +177,11 @@ private:
     void setIterationLog(limo_ctx* ctx);      // before the solve: the context's switch follows minimizer_progress_to_stdout_
     void collectIterations(limo_ctx* ctx, const char* what);  // behind it: last_iterations_ and the table
     std::vector<limo_ba_iteration> last_iterations_;
+    // LIMO_SHIM_TRACE=1: where the host time of adjustPoseOnly() / solve() goes.  Every half and piece adds its microseconds here;
+    // commitPoseOnly / commitSolve print the line and start over (a call somebody else made, a batched one, shows as 0 us).
+    struct ShimTimes {
+        double select = 0., prepare = 0., call = 0.;
+    } shim_us_;
     int dump_calls_ = 0;
     bool device_selection_ = false;
     limo_select_params select_params_{};

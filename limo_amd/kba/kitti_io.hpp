@@ -50,6 +50,9 @@ inline std::string velodynePath(const std::string& dir, int frame) {
     return dir + name;
 }
 
+// a motion of the vehicle (origin <- vehicle at t) as the pose files hold it: camera_0 <- camera_t = T_cam_veh * m * T_cam_veh^-1
+inline EigenPose inCameraFrame(const EigenPose& T_cam_veh, const EigenPose& m) { return T_cam_veh * m * T_cam_veh.inverse(); }
+// one row of a pose file: the first three rows of camera_0 <- camera_t, row-major, 12 numbers
 inline void writePoseRow(std::ostream& os, const EigenPose& m) {
     char buf[512];
     std::snprintf(buf, sizeof(buf), "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g", m.R[0], m.R[1], m.R[2], m.t[0], m.R[3],

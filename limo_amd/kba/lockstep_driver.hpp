@@ -1,5 +1,5 @@
-// lockstep_driver.hpp — N sequences of one sensor rig driven in lock step: the stages of StreamDriver::process (stream_driver.hpp), in
-// the same order, with ONE device call per stage and tick for all the sequences that need it:
+// lockstep_driver.hpp — N sequences of one sensor rig driven in lock step: the phases of a frame (stream_detail::Sequence, sequence.hpp)
+// that StreamDriver (stream_driver.hpp) runs for one sequence, with ONE device call per stage and tick for all the sequences that want it:
 //   frames of the tick
 //     -> limo_depth_estimate_batch                    the sweeps of the tick (feature staging, depth history: per sequence, host)
 //     -> motion prior                                 external, constant velocity (host), or the five-point prior: matches and gate
@@ -10,33 +10,24 @@
 //     -> for the sequences whose solve is due: window cut + labels (host), limo_landmark_select_batch
 //        (StreamParams::landmark_selection_on_device; off: the host selector per sequence), limo_ba_batch_create / _solve / _download
 //     -> pose of the frame, motion, statistics
-// A sequence without a frame in a tick sits out; sequences may start late, end early and solve on different ticks.  Every sequence
-// keeps its own adjuster, keyframe selector, depth history, motion state, statistics and pose list; the per-sequence pieces of a frame
-// are stream_detail's (stream_driver.hpp), the halves around each device call BundleAdjusterKeyframes' prepare / commit.  What the
-// batched entry points promise (include/limo_hip.h: "window / frame / pool i gets the bytes of its single call") makes the pose rows of
-// sequence i those of a StreamDriver given the same frames, byte for byte.
-// Threads: the per-sequence host phases (Keyframe object, prepare, commit, host selection) run on `host_threads` threads, one sequence
-// on one thread at a time; only the thread that calls tick() calls the C-ABI, on the driver's one context.  No result depends on
-// host_threads.
-// The batched symbols are weak references, as limo_five_point is in stream_driver.hpp: where the library behind the C-ABI lacks one
-// (the test backends tests/cpp/emu_pipeline.cpp and oracle_abi.cpp) that stage loops over the single call.  Stats counts both.
+// A sequence without a frame in a tick sits out; sequences may start late, end early and solve on different ticks.  Every sequence is
+// a stream_detail::Sequence of its own: the policy of a frame is that type's, this file holds the calls.  What the batched entry points
+// promise (include/limo_hip.h: "window / frame / pool i gets the bytes of its single call") makes the pose rows of sequence i those of
+// a StreamDriver given the same frames, byte for byte.
+// Threads: the phases run on `host_threads` threads, one sequence on one thread at a time (no phase touches a limo_ctx); only the
+// thread that calls tick() calls the C-ABI, on the driver's one context.  No result depends on host_threads.
+// Where the library behind the C-ABI lacks a batched entry point, that stage loops over the single call.  Stats counts both.
 // Not here: the depth assignment one frame ahead (there is no begin / end form of the batch call), the iteration table
 // (BundleAdjusterKeyframes::minimizer_progress_to_stdout_), different rigs or parameters per sequence, several GPUs.
 #pragma once
+#include <condition_variable>
 #include <functional>
+#include <memory>
+#include <mutex>
 #include <optional>
+#include <thread>
 
-#include "stream_driver.hpp"
-
-#pragma weak limo_depth_estimate_batch
-#pragma weak limo_five_point_batch
-#pragma weak limo_ba_adjust_pose_only_batch
-#pragma weak limo_landmark_select
-#pragma weak limo_landmark_select_batch
-#pragma weak limo_ba_batch_create
-#pragma weak limo_ba_batch_solve
-#pragma weak limo_ba_batch_download
-#pragma weak limo_ba_batch_destroy
+#include "sequence.hpp"
 
 namespace keyframe_bundle_adjustment {
 
@@ -127,8 +118,23 @@ private:
 
 }  // namespace lockstep_detail
 
+// The batched entry points are weak references, as limo_five_point is in stream_driver.hpp: where the library behind the C-ABI lacks one
+// (the test backends tests/cpp/emu_pipeline.cpp and oracle_abi.cpp) its address is null and tick() loops over the single call.
+#pragma weak limo_depth_estimate_batch
+#pragma weak limo_five_point
+#pragma weak limo_five_point_default_params
+#pragma weak limo_five_point_batch
+#pragma weak limo_ba_adjust_pose_only_batch
+#pragma weak limo_landmark_select
+#pragma weak limo_landmark_select_batch
+#pragma weak limo_ba_batch_create
+#pragma weak limo_ba_batch_solve
+#pragma weak limo_ba_batch_download
+#pragma weak limo_ba_batch_destroy
+
 class LockstepDriver {
 public:
+    using Sequence = stream_detail::Sequence;
     struct Rig {  // what the batched depth and selection calls take ONE of: every sequence must bring the same
         Camera::Ptr camera;
         EigenPose T_camera_lidar;
@@ -169,17 +175,10 @@ public:
                                             " differs from sequence 0's (camera intrinsics, camera <- vehicle or camera <- lidar): the batched depth and selection "
                                             "calls take one rig; drive it with a StreamDriver of its own");
         }
-        for (size_t i = 0; i < rigs.size(); ++i) {
-            seqs_.push_back(std::make_unique<Seq>());
-            Seq& s = *seqs_.back();
-            s.camera = rigs[i].camera;
-            s.ba.dump_tag_ = (int)i;
-            stream_detail::configureSequence(p, s.ba, s.selector);
-        }
+        const bool five_point_device = p.five_point_on_device && &limo_five_point_default_params != nullptr && (&limo_five_point_batch != nullptr || &limo_five_point != nullptr);
+        for (size_t i = 0; i < rigs.size(); ++i) seqs_.push_back(std::make_unique<Sequence>(p_, rigs[i].camera, five_point_device, (int)i));
         T_cam_lidar_ = convert(rigs[0].T_camera_lidar);
-        int dev = 0;  // LIMO_DEVICE: the GPU of this driver
-        if (const char* e = std::getenv("LIMO_DEVICE")) dev = std::atoi(e);
-        if (limo_ctx_create(dev, &ctx_) != LIMO_OK) throw std::runtime_error("LockstepDriver: no HIP device (limo_ctx_create)");
+        ctx_ = createContext();
         limo_depth_default_params(&depth_params_);
     }
     ~LockstepDriver() {
@@ -192,163 +191,87 @@ public:
     int hostThreads() const { return host_threads_; }
 
     // One tick: frames[i] is sequence i's frame, or empty (the sequence sits out).  The tracklets are taken over (depths are filled in).
+    // Six stages, each: a phase of stream_detail::Sequence over the sequences of the tick (on the pool), the jobs of those that want the
+    // stage's call gathered, the ONE batched call (or, without the entry point, the single calls), the results back into the jobs.
     void tick(std::vector<std::optional<Frame>>& frames) {
-        using clk = std::chrono::steady_clock;
-        auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
+        using stream_detail::Timed;
         if (frames.size() != seqs_.size()) throw std::invalid_argument("LockstepDriver::tick: one (optional) frame per sequence");
-        const auto t_begin = clk::now();
-        std::vector<Seq*> act;
+        const auto t_begin = std::chrono::steady_clock::now();
+        std::vector<Sequence*> act;
         for (size_t i = 0; i < seqs_.size(); ++i) {
-            Seq& s = *seqs_[i];
             if (!frames[i] || frames[i]->tracklets.stamps.empty()) continue;  // (an empty message: :98-104)
-            s.tracklets = std::move(frames[i]->tracklets);
-            s.cloud = frames[i]->cloud_xyzi;
-            s.n_pts = frames[i]->n_pts;
-            s.has_external = frames[i]->has_external_prior;
-            s.external = frames[i]->external_prior;
+            Frame& f = *frames[i];
+            seqs_[i]->take(std::move(f.tracklets), f.cloud_xyzi, f.n_pts, f.has_external_prior ? &f.external_prior : nullptr);
             frames[i].reset();
-            act.push_back(&s);
+            act.push_back(seqs_[i].get());
         }
         ++stats_.ticks;
         if (act.empty()) return;
-        auto host = [&](std::vector<Seq*>& which, double& sec, const std::function<void(Seq&)>& fn) {
-            const auto t0 = clk::now();
-            pool_.run(which.size(), [&](size_t k) { fn(*which[k]); });
-            sec += since(t0);
-        };
+        const Camera& cam = *seqs_[0]->camera;  // (one rig)
+        const double f = cam.focal_length, cx = cam.principal_point[0], cy = cam.principal_point[1];
 
-        // ---- 1. depth: staging per sequence, one call over the sweeps of the tick, history per sequence
-        host(act, stats_.depth.sec_host, [&](Seq& s) {
-            s.stamp = s.tracklets.stamps.front();
-            s.want_five_point = s.want_pose_only = s.want_push = s.want_solve = false;
-            s.is_keyframe = false;
-            const size_t n = s.tracklets.tracks.size();
-            s.from_sweep = p_.assign_depth && s.cloud && s.n_pts && n;
-            if (s.from_sweep) {
-                s.depth.assign(n, -1.f);
-                stream_detail::stageFeatures(p_, s.tracklets, s.uv, s.ground);
-            }
-        });
+        // ---- 1. depth: one call over the sweeps of the tick
+        host(act, stats_.depth.sec_host, [](Sequence& s, size_t) { s.stageDepth(); });
         {
-            std::vector<Seq*> sweep;
-            for (Seq* s : act)
-                if (s->from_sweep) sweep.push_back(s);
-            const auto t0 = clk::now();
-            const Camera& cam = *seqs_[0]->camera;
+            const auto sweep = those(act, &Sequence::wantsSweep);
+            Timed t(stats_.depth.sec_abi);
             if (sweep.empty()) {
             } else if (&limo_depth_estimate_batch != nullptr) {
                 std::vector<limo_depth_frame> fr;
-                for (Seq* s : sweep) fr.push_back({s->cloud, s->n_pts, s->uv.data(), s->tracklets.tracks.size(), s->ground.data(), s->depth.data()});
-                check(limo_depth_estimate_batch(ctx_, (int32_t)fr.size(), fr.data(), T_cam_lidar_.data(), cam.focal_length, cam.principal_point[0], cam.principal_point[1],
-                                                p_.image_width, p_.image_height, &depth_params_, 0u),
+                for (Sequence* s : sweep) fr.push_back(s->depthFrame(s->tracklets, s->cloud, s->n_pts));
+                check(limo_depth_estimate_batch(ctx_, (int32_t)fr.size(), fr.data(), T_cam_lidar_.data(), f, cx, cy, p_.image_width, p_.image_height, &depth_params_, 0u),
                       "limo_depth_estimate_batch");
                 batched(stats_.depth, sweep.size());
             } else {
-                for (Seq* s : sweep) {
-                    check(limo_depth_estimate(ctx_, s->cloud, s->n_pts, T_cam_lidar_.data(), cam.focal_length, cam.principal_point[0], cam.principal_point[1], p_.image_width,
-                                              p_.image_height, s->uv.data(), s->tracklets.tracks.size(), s->ground.data(), &depth_params_, s->depth.data()),
+                for (Sequence* s : sweep) {
+                    const limo_depth_frame fr = s->depthFrame(s->tracklets, s->cloud, s->n_pts);
+                    check(limo_depth_estimate(ctx_, fr.cloud_xyzi, fr.n_pts, T_cam_lidar_.data(), f, cx, cy, p_.image_width, p_.image_height, fr.feat_uv, fr.n_feat,
+                                              fr.feat_is_ground, &depth_params_, fr.depth_out),
                           "limo_depth_estimate");
                     ++stats_.depth.fallback_calls;
                 }
             }
-            stats_.depth.sec_abi += since(t0);
         }
 
-        // ---- 2. prior.  The first frame of a sequence is a Pose-fixed keyframe at the origin (:305-326): its push is prepared here.
-        const bool five_point_prior = p_.motion_prior == StreamParams::MotionPrior::FivePoint;
-        const bool five_point_device = p_.five_point_on_device && &limo_five_point_default_params != nullptr && (&limo_five_point_batch != nullptr || &limo_five_point != nullptr);
-        host(act, stats_.five_point.sec_host, [&](Seq& s) {
-            if (s.history.counts(s.tracklets)) s.stats.features += (int)s.tracklets.tracks.size();
-            s.history.record(s.tracklets, s.from_sweep ? s.depth.data() : nullptr, s.point_d, s.stats.features_with_depth);
-            s.history.forgetEndedTracks(s.tracklets);
-            stream_detail::applyDepths(s.tracklets, s.point_d);
-            s.first = s.ba.keyframes_.empty();
-            s.pose = EigenPose::Identity();
-            Plane ground_plane;
-            ground_plane.distance = p_.height_over_ground;
-            if (s.first) {
-                Keyframe first(s.stamp, s.tracklets, s.camera, EigenPose::Identity(), Keyframe::FixationStatus::Pose, ground_plane);
-                first.freezeMeasurements();  // (this driver owns its keyframes and never edits their measurements_: the table may outlive the call)
-                s.ba.preparePush(std::move(first), s.push);
-                s.want_push = s.is_keyframe = true;
-            } else if (s.has_external) {
-                s.prior = s.external;
-            } else if (five_point_prior) {
-                s.stamp_last_kf = s.ba.getKeyframe().timestamp_;
-                stream_detail::fivePointQuery(s.tracklets, s.stamp_last_kf, s.stamp, s.five_point_query);
-                if (s.five_point_query.estimate) {
-                    ++s.stats.five_point_calls;
-                    if (five_point_device)
-                        s.want_five_point = true;
-                    else
-                        s.last_five_point = stream_detail::fivePointOnHost(s.five_point_query, *s.camera, (uint64_t)s.stamp);
-                }
-            } else {
-                s.prior = s.motion.constantVelocityPrior(p_, s.stamp);
-            }
+        // ---- 2. depth history and prior; the five-point estimates through one call
+        host(act, stats_.five_point.sec_host, [](Sequence& s, size_t) {
+            s.recordDepth();
+            s.applyDepths();
+            s.choosePrior();
         });
         {
-            std::vector<Seq*> est;
-            for (Seq* s : act) {
-                if (s->want_five_point) est.push_back(s);
-                stats_.five_point_host += !s->first && !s->has_external && five_point_prior && s->five_point_query.estimate && !s->want_five_point;
-            }
-            const auto t0 = clk::now();
+            const auto est = those(act, &Sequence::wantsFivePoint);
+            for (const Sequence* s : act) stats_.five_point_host += s->estimatedOnHost();
+            Timed t(stats_.five_point.sec_abi);
             if (!est.empty()) {
-                const Camera& cam = *seqs_[0]->camera;
                 limo_five_point_params prm;
                 limo_five_point_default_params(&prm);
                 std::vector<limo_five_point_frame> fr;
-                for (Seq* s : est) fr.push_back(stream_detail::fivePointFrame(s->five_point_query, (uint64_t)s->stamp));
+                for (Sequence* s : est) fr.push_back(s->fivePointFrame());
                 std::vector<limo_five_point_motion> mo(est.size());
                 if (&limo_five_point_batch != nullptr) {
-                    check(limo_five_point_batch(ctx_, (int32_t)fr.size(), fr.data(), cam.focal_length, cam.principal_point[0], cam.principal_point[1], &prm, mo.data()),
-                          "limo_five_point_batch");
+                    check(limo_five_point_batch(ctx_, (int32_t)fr.size(), fr.data(), f, cx, cy, &prm, mo.data()), "limo_five_point_batch");
                     batched(stats_.five_point, est.size());
                 } else {
                     for (size_t k = 0; k < est.size(); ++k) {
-                        check(limo_five_point(ctx_, &fr[k], cam.focal_length, cam.principal_point[0], cam.principal_point[1], &prm, &mo[k], nullptr), "limo_five_point");
+                        check(limo_five_point(ctx_, &fr[k], f, cx, cy, &prm, &mo[k], nullptr), "limo_five_point");
                         ++stats_.five_point.fallback_calls;
                     }
                 }
-                for (size_t k = 0; k < est.size(); ++k) {
-                    est[k]->last_five_point = stream_detail::fivePointMotion(mo[k]);
-                    ++est[k]->stats.five_point_device_calls;
-                }
+                for (size_t k = 0; k < est.size(); ++k) est[k]->acceptFivePoint(mo[k]);
             }
-            stats_.five_point.sec_abi += since(t0);
         }
 
-        // ---- 3. Keyframe(prior) per sequence, one pose-only call for every frame without an external prior (:192-211)
-        std::vector<Seq*> later;  // the sequences past their first frame
-        for (Seq* s : act)
-            if (!s->first) later.push_back(s);
-        host(later, stats_.pose_only.sec_host, [&](Seq& s) {
-            if (!s.has_external && five_point_prior) {
-                const EigenPose motion = stream_detail::fivePointUnscaled(p_, *s.camera, s.five_point_query, s.five_point_query.estimate ? &s.last_five_point : nullptr,
-                                                                          s.stamp_last_kf, s.stamp);
-                s.prior = stream_detail::fivePointPrior(s.ba, s.stamp, motion);
-            }
-            s.prior = stream_detail::normalisedPrior(s.prior);
-            Plane ground_plane;
-            ground_plane.distance = p_.height_over_ground;
-            s.cur = std::make_shared<Keyframe>(s.stamp, s.tracklets, s.camera, s.prior, Keyframe::FixationStatus::None, ground_plane);
-            s.cur->freezeMeasurements();  // (as above: built once per keyframe, kept for its life in the window)
-            if (!s.has_external) {  // a prior without scale is always refined against the fixed landmarks of the last selection
-                s.ba.preparePoseOnly(*s.cur, s.pose_job);
-                s.want_pose_only = true;
-            }
-        });
+        // ---- 3. Keyframe(prior) per sequence, one pose-only call for every frame that wants one
+        host(act, stats_.pose_only.sec_host, [](Sequence& s, size_t) { s.buildKeyframe(); });
         {
-            std::vector<Seq*> ref;
-            for (Seq* s : later)
-                if (s->want_pose_only) ref.push_back(s);
-            const auto t0 = clk::now();
+            const auto ref = those(act, &Sequence::wantsPoseOnly);
+            Timed t(stats_.pose_only.sec_abi);
             if (ref.empty()) {
             } else if (&limo_ba_adjust_pose_only_batch != nullptr) {
                 std::vector<limo_ba_window> ws;
                 std::vector<limo_speed_prior> priors;
-                for (Seq* s : ref) {
+                for (Sequence* s : ref) {
                     ws.push_back(*s->pose_job.window);
                     priors.push_back(s->pose_job.prior);  // (speed_weight 0: "no prior for this window")
                 }
@@ -357,46 +280,31 @@ public:
                 for (size_t k = 0; k < ref.size(); ++k) ref[k]->pose_job.report = reports[k];
                 batched(stats_.pose_only, ref.size());
             } else {
-                for (Seq* s : ref) {
+                for (Sequence* s : ref) {
                     BundleAdjusterKeyframes::WindowJob& j = s->pose_job;
                     check(limo_ba_adjust_pose_only(ctx_, j.window, j.has_prior ? &j.prior : nullptr, &j.opts, &j.report), "limo_ba_adjust_pose_only");
                     ++stats_.pose_only.fallback_calls;
                 }
             }
-            stats_.pose_only.sec_abi += since(t0);
         }
 
-        // ---- 4. keyframe selection per sequence (:218-222), the pushes of all sequences through one limo_landmark_init (:231-233)
-        host(later, stats_.landmark_init.sec_host, [&](Seq& s) {
-            if (s.want_pose_only) {
-                s.ba.commitPoseOnly(s.pose_job);
-                stream_detail::trace(s.ba, "pose-only", s.stamp, s.cur->pose_, s.ba.last_report_.final_cost);
-            }
-            s.pose = s.cur->getEigenPose();
-            const auto selected = s.selector.select({s.cur}, s.ba.getActiveKeyframePtrs());
-            if (!selected.empty()) {
-                if (selected.size() != 1 || *selected.begin() != s.cur) throw std::logic_error("LockstepDriver: the keyframe selector returned a frame it was not given");
-                s.ba.preparePush(std::move(*s.cur), s.push);  // (this frame's keyframe object is not looked at again: handed over)
-                s.want_push = s.is_keyframe = true;
-            }
-        });
+        // ---- 4. keyframe selection per sequence, the pushes of all sequences through one limo_landmark_init
+        host(act, stats_.landmark_init.sec_host, [](Sequence& s, size_t) { s.selectKeyframe(); });
         {
-            std::vector<Seq*> pushes;
+            const auto pushes = those(act, &Sequence::wantsPush);
             size_t n_lm = 0, n_rays = 0;
-            for (Seq* s : act)
-                if (s->want_push) {
-                    pushes.push_back(s);
-                    n_lm += s->push.ids.size();
-                    n_rays += s->push.rays.size();
-                }
-            const auto t0 = clk::now();
+            for (Sequence* s : pushes) {
+                n_lm += s->push.ids.size();
+                n_rays += s->push.rays.size();
+            }
+            Timed t(stats_.landmark_init.sec_abi);
             if (n_lm > 0) {  // (a push that introduces no landmark makes no call in the single driver either)
                 std::vector<int32_t> off{0};
                 std::vector<limo_ray> rays;
                 std::vector<uint8_t> use_depth, ok(n_lm, 0);
                 std::vector<double> pos(3 * n_lm, 0.0);
                 off.reserve(n_lm + 1), rays.reserve(n_rays), use_depth.reserve(n_lm);
-                for (Seq* s : pushes) {
+                for (Sequence* s : pushes) {
                     const BundleAdjusterKeyframes::PushJob& j = s->push;
                     const int32_t base = (int32_t)rays.size();
                     for (size_t l = 0; l < j.ids.size(); ++l) off.push_back(base + j.off[l + 1]);
@@ -405,7 +313,7 @@ public:
                 }
                 check(limo_landmark_init(ctx_, (int32_t)n_lm, off.data(), rays.data(), use_depth.data(), pos.data(), ok.data()), "limo_landmark_init");
                 size_t at = 0;
-                for (Seq* s : pushes) {
+                for (Sequence* s : pushes) {
                     BundleAdjusterKeyframes::PushJob& j = s->push;
                     std::copy(pos.begin() + 3 * at, pos.begin() + 3 * (at + j.ids.size()), j.pos.begin());
                     std::copy(ok.begin() + at, ok.begin() + at + j.ids.size(), j.ok.begin());
@@ -414,66 +322,43 @@ public:
                 batched(stats_.landmark_init, pushes.size());
                 stats_.landmarks_initialised += (long)n_lm;
             }
-            stats_.landmark_init.sec_abi += since(t0);
         }
 
-        // ---- 5. window stage of the sequences whose solve is due (:245-263): cut + labels, selection, solve
-        host(act, stats_.select.sec_host, [&](Seq& s) {
-            if (s.want_push) s.ba.commitPush(s.push);
-            s.push.kf.reset();
-            if (s.first) return;
-            s.now_sec = convert(s.stamp);
-            if (!stream_detail::solveDue(p_, s.ba, s.now_sec, s.last_solved_sec)) return;
-            s.ba.deactivateKeyframes(p_.min_number_connecting_landmarks, 3, p_.max_size_optimization_window);
-            s.ba.updateLabels(s.tracklets, p_.shrubbery_weight);
-            s.ba.prepareSelection(s.select);
-            s.want_solve = true;
-            if (!s.select.on_device) {  // the host selector: no call to wait for
-                s.ba.commitSelection(s.select, false);
-                s.ba.prepareSolve(s.solve_job);
-            }
-        });
-        std::vector<Seq*> due, pools;
-        for (Seq* s : act)
-            if (s->want_solve) {
-                due.push_back(s);
-                if (s->select.on_device)
-                    pools.push_back(s);
-                else
-                    ++stats_.select_host;
-            }
+        // ---- 5. window stage of the sequences whose solve is due: cut + labels, selection, solve
+        host(act, stats_.select.sec_host, [](Sequence& s, size_t) { s.enterWindow(); });
+        const auto due = those(act, &Sequence::wantsSolve), pools = those(act, &Sequence::wantsSelection);
+        stats_.select_host += (long)(due.size() - pools.size());
         if (!pools.empty()) {
-            const auto t0 = clk::now();
-            bool done = false;
-            if (&limo_landmark_select_batch != nullptr) {
-                std::vector<limo_select_pool> ps;
-                std::vector<uint8_t*> outs;
-                for (Seq* s : pools) {
-                    ps.push_back(s->select.pool);
-                    outs.push_back(s->select.out.data());
+            std::vector<uint8_t> ok(pools.size(), 0);
+            {
+                Timed t(stats_.select.sec_abi);
+                if (&limo_landmark_select_batch != nullptr) {
+                    std::vector<limo_select_pool> ps;
+                    std::vector<uint8_t*> outs;
+                    for (Sequence* s : pools) {
+                        ps.push_back(s->select.pool);
+                        outs.push_back(s->select.out.data());
+                    }
+                    // (every sequence's parameters say the same: one StreamParams)
+                    if (limo_landmark_select_batch(ctx_, (int32_t)ps.size(), ps.data(), pools[0]->select.params, outs.data()) == LIMO_OK) {
+                        batched(stats_.select, pools.size());
+                        ok.assign(pools.size(), 1);
+                    }
                 }
-                // (every sequence's parameters say the same: one StreamParams)
-                done = limo_landmark_select_batch(ctx_, (int32_t)ps.size(), ps.data(), pools[0]->select.params, outs.data()) == LIMO_OK;
-                if (done) batched(stats_.select, pools.size());
-                for (Seq* s : pools) s->select_ok = done;
+                if (!ok[0])  // no batched entry point, or a pool the device does not take (above 64 keyframes or 8 cameras): pool by pool
+                    for (size_t k = 0; k < pools.size(); ++k) {
+                        ok[k] = limo_landmark_select(ctx_, &pools[k]->select.pool, pools[k]->select.params, pools[k]->select.out.data()) == LIMO_OK;
+                        ++stats_.select.fallback_calls;
+                        stats_.select_host += !ok[k];
+                    }
             }
-            if (!done)  // no batched entry point, or a pool the device does not take (above 64 keyframes or 8 cameras): pool by pool
-                for (Seq* s : pools) {
-                    s->select_ok = limo_landmark_select(ctx_, &s->select.pool, s->select.params, s->select.out.data()) == LIMO_OK;
-                    ++stats_.select.fallback_calls;
-                    stats_.select_host += !s->select_ok;
-                }
-            stats_.select.sec_abi += since(t0);
-            host(pools, stats_.solve.sec_host, [&](Seq& s) {
-                s.ba.commitSelection(s.select, s.select_ok);
-                s.ba.prepareSolve(s.solve_job);
-            });
+            host(pools, stats_.solve.sec_host, [&](Sequence& s, size_t k) { s.selectionDone(ok[k] != 0); });
         }
         if (!due.empty()) {
-            const auto t0 = clk::now();
+            Timed t(stats_.solve.sec_abi);
             if (&limo_ba_batch_create != nullptr && &limo_ba_batch_solve != nullptr && &limo_ba_batch_download != nullptr && &limo_ba_batch_destroy != nullptr) {
                 std::vector<limo_ba_window> ws;
-                for (Seq* s : due) ws.push_back(*s->solve_job.window);
+                for (Sequence* s : due) ws.push_back(*s->solve_job.window);
                 std::vector<limo_ba_report> reports(due.size());
                 limo_ba_batch* b = nullptr;
                 check(limo_ba_batch_create(ctx_, (int32_t)ws.size(), ws.data(), &b), "limo_ba_batch_create");
@@ -489,86 +374,32 @@ public:
                 for (size_t k = 0; k < due.size(); ++k) due[k]->solve_job.report = reports[k];
                 batched(stats_.solve, due.size());
             } else {
-                for (Seq* s : due) {
+                for (Sequence* s : due) {
                     BundleAdjusterKeyframes::WindowJob& j = s->solve_job;
                     check(limo_ba_solve(ctx_, j.window, &j.opts, &j.report), "limo_ba_solve");
                     ++stats_.solve.fallback_calls;
                 }
             }
-            stats_.solve.sec_abi += since(t0);
         }
 
-        // ---- 6. book-keeping: the optimised pose if the frame became a keyframe, its prior otherwise (:281-294)
-        host(act, stats_.sec_host_finish, [&](Seq& s) {
-            if (s.want_solve) {
-                s.last_summary = s.ba.commitSolve(s.solve_job);
-                ++s.stats.solves;
-                stream_detail::trace(s.ba, "solve", s.stamp, s.ba.getKeyframe().pose_, s.ba.last_report_.final_cost);
-                s.stats.solves_on_non_keyframes += !s.is_keyframe;
-                s.last_solved_sec = s.now_sec;
-            }
-            if (!s.first && s.ba.getKeyframe().timestamp_ == s.stamp) s.pose = s.ba.getKeyframe().getEigenPose();
-            s.motion.advance(s.pose, s.stamp);
-            ++s.stats.frames;
-            s.stats.keyframes += s.is_keyframe;
-            s.poses.push_back(s.pose);
-            s.cur.reset();
-            s.pose_job.flat.reset(), s.solve_job.flat.reset(), s.select.flat.reset();
-        });
+        // ---- 6. the solved windows back, pose of the frame, motion, statistics
+        host(act, stats_.sec_host_finish, [](Sequence& s, size_t) { s.finishFrame(); });
         stats_.frames += (int)act.size();
-        stats_.sec_total += since(t_begin);
+        stats_.sec_total += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     }
 
-    // KITTI odometry rows of sequence i (StreamDriver::writeKittiTrajectory)
-    void writeKittiTrajectory(size_t i, std::ostream& os) const {
-        const Seq& s = *seqs_.at(i);
-        const EigenPose cv = s.camera->getEigenPose();
-        for (const auto& pose_kf_origin : s.poses) {
-            const EigenPose m = cv * pose_kf_origin.inverse() * cv.inverse();
-            char buf[512];
-            std::snprintf(buf, sizeof(buf), "%.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g %.12g", m.R[0], m.R[1], m.R[2], m.t[0], m.R[3], m.R[4],
-                          m.R[5], m.t[1], m.R[6], m.R[7], m.R[8], m.t[2]);
-            os << buf << "\n";
-        }
-    }
+    // KITTI odometry rows of sequence i: those of a StreamDriver given the same frames
+    void writeKittiTrajectory(size_t i, std::ostream& os) const { seqs_.at(i)->writeKittiTrajectory(os); }
 
     BundleAdjusterKeyframes& adjuster(size_t i) { return seqs_.at(i)->ba; }
     const std::vector<EigenPose>& poses(size_t i) const { return seqs_.at(i)->poses; }
-    const StreamDriver::Stats& sequenceStats(size_t i) const { return seqs_.at(i)->stats; }  // (the counts; the seconds are the driver's, per stage)
+    // (the counts; its seconds are the host phases' own statements - the calls are this driver's, per stage)
+    const StreamStats& sequenceStats(size_t i) const { return seqs_.at(i)->stats; }
     const std::string& lastSummary(size_t i) const { return seqs_.at(i)->last_summary; }
     const Stats& stats() const { return stats_; }
     limo_depth_params& depthParams() { return depth_params_; }
 
 private:
-    struct Seq {
-        Camera::Ptr camera;
-        BundleAdjusterKeyframes ba;
-        KeyframeSelector selector;
-        stream_detail::DepthHistory history;
-        stream_detail::MotionState motion;
-        StreamDriver::Stats stats;
-        std::vector<EigenPose> poses;
-        double last_solved_sec = -1e30;
-        std::string last_summary;
-        five_point::Motion last_five_point;
-        std::vector<float> uv, depth, point_d;
-        std::vector<uint8_t> ground;
-        // the frame of this tick
-        Tracklets tracklets;
-        const float* cloud = nullptr;
-        size_t n_pts = 0;
-        bool has_external = false, from_sweep = false, first = false, is_keyframe = false;
-        bool want_five_point = false, want_pose_only = false, want_push = false, want_solve = false, select_ok = false;
-        EigenPose external, prior, pose;
-        TimestampNSec stamp = 0, stamp_last_kf = 0;
-        double now_sec = 0.;
-        Keyframe::Ptr cur;
-        stream_detail::FivePointQuery five_point_query;
-        BundleAdjusterKeyframes::PushJob push;
-        BundleAdjusterKeyframes::WindowJob pose_job, solve_job;
-        BundleAdjusterKeyframes::SelectJob select;
-    };
-
     static bool sameRig(const Rig& a, const Rig& b) {
         if (!a.camera || !b.camera) return false;
         bool same = a.camera->focal_length == b.camera->focal_length && a.camera->principal_point[0] == b.camera->principal_point[0] &&
@@ -578,9 +409,20 @@ private:
         for (int i = 0; i < 3; ++i) same = same && a.T_camera_lidar.t[i] == b.T_camera_lidar.t[i];
         return same;
     }
-    void check(int rc, const char* what) const {
-        if (rc != LIMO_OK) throw std::runtime_error(std::string(what) + ": " + limo_last_error(ctx_));
+    // a phase over `which` on the pool: fn(sequence, its index in `which`)
+    template <class Phase>
+    void host(const std::vector<Sequence*>& which, double& sec, Phase fn) {
+        stream_detail::Timed t(sec);
+        pool_.run(which.size(), [&](size_t k) { fn(*which[k], k); });
     }
+    // the sequences whose last phase left a job for the stage's call
+    static std::vector<Sequence*> those(const std::vector<Sequence*>& act, bool (Sequence::*wants)() const) {
+        std::vector<Sequence*> out;
+        for (Sequence* s : act)
+            if ((s->*wants)()) out.push_back(s);
+        return out;
+    }
+    void check(int rc, const char* what) const { checkCall(ctx_, rc, what); }
     static void batched(Stage& st, size_t items) {
         ++st.batched_calls;
         st.items += (long)items;
@@ -590,7 +432,7 @@ private:
     StreamParams p_;
     int host_threads_ = 1;
     lockstep_detail::HostPool pool_;  // (after host_threads_: built from it)
-    std::vector<std::unique_ptr<Seq>> seqs_;
+    std::vector<std::unique_ptr<Sequence>> seqs_;  // (after p_: they refer to it)
     Pose T_cam_lidar_;
     limo_ctx* ctx_ = nullptr;
     limo_depth_params depth_params_;

@@ -53,7 +53,7 @@ def main():
     rows = []
     for n_lm in [int(s) for s in a.sizes.split(",")]:
         for n_kf in [int(s) for s in a.windows.split(",")]:
-            # the node's wiring (stream_driver.hpp:110-125): budgets 200 / 200 / 100, the 50 nearest ground landmarks of every keyframe of the window
+            # the node's wiring (sequence.hpp: configureSequence): budgets 200 / 200 / 100, the 50 nearest ground landmarks of every keyframe of the window
             p = lsc.params(add=[(i, 50, _ffi.SELECT_IS_GROUND, _ffi.SELECT_KEY_RANGE) for i in range(n_kf)])
             pool = lsc.make_pool(n_lm + n_kf, n_lm, n_kf)
             w, keep = _ffi.select_pool(pool)

@@ -7,6 +7,9 @@ drive of this commit against the parent's, runs alternated, to show what the spl
   scripts/bench_lockstep.py --build-parent REV      (on the build machine: needs git) compiles REV's apps/limo_stream + shim against the
                                                     liblimo_hip.so of the work tree into tests/cpp/_build/limo_stream_gpu_parent
   scripts/bench_lockstep.py [--frames 200] [--sizes 1,4,16,64] [--repeats 3] [--out profiles/lockstep.json]   (on the GPU machine)
+  scripts/bench_lockstep.py --against-parent [--frames 200] [--repeats 3] [--out ...]   (on the GPU machine) for a change of the drivers'
+                                                    host side when REV already has the lock-step driver: the parent's `--sequences N` too,
+                                                    alternated with this commit's, and the single drives with both flag sets
 
 The kernels are the same in both programs (this comparison is only fair while limo_amd/csrc is unchanged between REV and the work
 tree: --build-parent refuses otherwise).  Every process runs under its own time limit; a failing run ends the script.  The table goes to
@@ -72,9 +75,41 @@ def lockstep(exe, n, frames, flags, limit):
     return info
 
 
+def against_parent(a):
+    """Host-side changes of the drivers, this commit against a parent that HAS the lock-step driver: per row the parent, the parent
+    again and this commit, alternated, a.repeats runs each.  The two parent series are the same program: all their runs together give
+    the box's spread (half their range over their median), and this commit's median has to lie within it of the parent's."""
+    rows = [("single, default flags", lambda exe: single(exe, a.frames, 7, [], a.limit)[0]),
+            ("single, every stage on the device", lambda exe: single(exe, a.frames, 7, DEVICE_FLAGS, a.limit)[0])]
+    rows += [("lock step, N = %d, default flags" % n, lambda exe, n=n: lockstep(exe, n, a.frames, [], a.limit)) for n in (1, 16)]
+    res = {"frames": a.frames, "parent_rev": open(PARENT + ".rev").read().strip() if os.path.exists(PARENT + ".rev") else None, "rows": []}
+    for name, drive in rows:
+        runs = {"parent": [], "parent_again": [], "this": []}
+        for _ in range(a.repeats):
+            for series, exe in (("parent", PARENT), ("parent_again", PARENT), ("this", EXE)):
+                runs[series].append(drive(exe))
+        fps = {k: [r["frames_per_s"] if isinstance(r, dict) else r for r in v] for k, v in runs.items()}
+        both = fps["parent"] + fps["parent_again"]
+        parent = statistics.median(both)
+        spread = (max(both) - min(both)) / 2 / parent
+        delta = statistics.median(fps["this"]) / parent - 1
+        row = {"row": name, "frames_per_s": fps, "median_parent": parent, "median_this": statistics.median(fps["this"]), "spread": spread, "delta": delta, "within_spread": abs(delta) <= spread}
+        if isinstance(runs["this"][0], dict):  # where the host time of a tick goes, per stage: median of the runs, ms per tick
+            row["ms_host_per_tick"] = {k: {s: statistics.median(r["stages"][s]["ms_host"] / max(1, r["ticks"]) for r in runs[k]) for s in STAGES} for k in runs}
+        res["rows"].append(row)
+        print("%-36s parent %s | again %s | this %s | medians %.1f -> %.1f (%+.1f %%), spread of the parent +-%.1f %%: %s" % (
+            name, " ".join("%.1f" % x for x in fps["parent"]), " ".join("%.1f" % x for x in fps["parent_again"]), " ".join("%.1f" % x for x in fps["this"]), parent,
+            row["median_this"], 100 * delta, 100 * spread, "within" if row["within_spread"] else "OUTSIDE"))
+        sys.stdout.flush()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(res, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--build-parent", metavar="REV")
+    ap.add_argument("--against-parent", action="store_true", help="the single and the lock-step drive (N = 1, 16) of this commit against the parent's, alternated, with the box's spread")
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--sizes", default="1,4,16,64")
     ap.add_argument("--repeats", type=int, default=3)
@@ -87,6 +122,8 @@ def main():
     for exe in (EXE, PARENT):
         if not os.path.exists(exe):
             sys.exit("%s is missing (build(); scripts/bench_lockstep.py --build-parent REV)" % exe)
+    if a.against_parent:
+        return against_parent(a)
     res = {"frames": a.frames, "parent_rev": open(PARENT + ".rev").read().strip() if os.path.exists(PARENT + ".rev") else None, "single": {}, "baseline": {}, "lockstep": []}
     # 1. the single drive: this commit against the parent, alternated
     runs = {"parent": [], "this": []}

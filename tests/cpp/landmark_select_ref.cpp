@@ -1,5 +1,5 @@
 // landmark_select_ref.cpp — the checker of limo_landmark_select: Keyframe / Landmark / Camera objects built from a flat pool, and
-// LandmarkSelector with cheirality + voxel + add-depth exactly as StreamDriver wires them (limo_amd/kba/stream_driver.hpp:110-125,
+// LandmarkSelector with cheirality + voxel + add-depth exactly as StreamDriver wires them (limo_amd/kba/sequence.hpp: configureSequence,
 // bundle_adjuster_keyframes.cpp:184), behind a C entry point with the C-ABI's output byte.  Built by tests/landmark_select_common.py
 // with -ffp-contract=off.  test_landmark_select_core.cpp includes this file.
 #include <algorithm>

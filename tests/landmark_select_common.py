@@ -116,7 +116,7 @@ def quat_R(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-# the node's must-have wiring in small (stream_driver.hpp:118-124): the nearest landmarks with a measured depth in the oldest keyframe, the
+# the node's must-have wiring in small (sequence.hpp: configureSequence): the nearest landmarks with a measured depth in the oldest keyframe, the
 # nearest ground landmarks of the first four keyframes of the window
 ADD = [(0, 5, _ffi.SELECT_HAS_DEPTH, _ffi.SELECT_KEY_MEASURED_DEPTH)] + [(i, 6, _ffi.SELECT_IS_GROUND, _ffi.SELECT_KEY_RANGE) for i in range(4)]
 
