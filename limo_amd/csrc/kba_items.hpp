@@ -1319,8 +1319,30 @@ KBA_HD int cam_max_reg_rows(int nc) {  // upper bound of reg_row_count for a win
     const int nkf = nc / kCamSlots;
     return 1 + (nkf > 0 ? (nkf - 1) * 5 + 3 * nkf : 0) + 3;
 }
-// scratch of cam_assemble: H (nc x nc) | regulariser rows, aliased by the ground-plane staging | dense regulariser
-// rows, aliased by the views' raw camera-side totals of the first phase and by the reduction tree of the last
+// H_cc is block tridiagonal over the keyframes: observation and ground-plane terms touch one keyframe's kCamSlots slots, a
+// regulariser row at most two neighbouring keyframes.  cam_assemble keeps exactly that band: the upper triangles of the n_kf
+// diagonal blocks (55 entries each, row by row), then the n_kf - 1 blocks (k, k + 1) in full (100 each, row-major).
+constexpr int kCamDiag = kCamSlots * (kCamSlots + 1) / 2, kCamOff = kCamSlots * kCamSlots;
+KBA_HD int cam_bt_count(int nc) {
+    const int nkf = nc / kCamSlots;
+    return nkf > 0 ? kCamDiag * nkf + kCamOff * (nkf - 1) : 0;
+}
+// Place of H[a][b] in the band; an entry below the diagonal is read at its mirror image.  -1: outside the band (an exact zero).
+KBA_HD int cam_bt_index(int nc, int a, int b) {
+    if (a > b) {
+        const int t = a;
+        a = b;
+        b = t;
+    }
+    const int ka = a / kCamSlots, kb = b / kCamSlots, ia = a - ka * kCamSlots, ib = b - kb * kCamSlots;
+    if (ka == kb) return ka * kCamDiag + ia * kCamSlots - ia * (ia - 1) / 2 + (ib - ia);
+    if (kb == ka + 1) return (nc / kCamSlots) * kCamDiag + ka * kCamOff + ia * kCamSlots + ib;
+    return -1;
+}
+// scratch of cam_assemble: H (the band, cam_bt_count) | g_c, Jacobi scale (nc each), free slot -> slot (nc ints) | regulariser
+// rows, aliased by the ground-plane staging | dense regulariser rows, aliased by the views' raw camera-side totals of the first
+// phase and by the reduction tree of the last
+KBA_HD int cam_assemble_head(int nc) { return cam_bt_count(nc) + 2 * nc + (nc + 1) / 2; }
 KBA_HD int cam_assemble_union(int nc) {
     const int rows = (int)((sizeof(RegRow) * cam_max_reg_rows(nc) + 7) / 8);
     const int gp = kGpChunk * 12;
@@ -1332,29 +1354,35 @@ KBA_HD int cam_assemble_scratch(int nc, int nt, int n_view) {
     const int red = coop_red_doubles(6, nt);
     const int raw = n_view * kLinPartial;
     const int third = red > dense ? red : dense;
-    return nc * nc + cam_assemble_union(nc) + (raw > third ? raw : third);
+    return cam_assemble_head(nc) + cam_assemble_union(nc) + (raw > third ? raw : third);
 }
 // Windows whose scratch exceeds this many bytes work in global memory (WinDesc::cam_scr_off) instead of LDS (160 KB / CU).
 constexpr int kCamLdsCapBytes = 150 * 1024;
 KBA_HD int cam_solve_scratch(int nc, int nt, int nf = -1) {
     if (nf < 0) nf = nc;  // (nf: free slots of the compact system, <= nc)
-    return nf * (nf + 1) + nf + nc + (nf + 1) / 2 + 1 + coop_red_doubles(3, nt) + nf * (nf + 1) / 2 + nf;  // A | y | dl | fl | red | Hs
+    return nf * (nf + 1) + nf + nc + coop_red_doubles(3, nt) + nf * (nf + 1) / 2 + nf;  // A | y | dl | red | Hs
 }
 
 // Workgroup-per-window: assemble the camera-camera normal equations H_cc, g_c at the linearisation point, the
-// Jacobi scaling of the camera columns, cost / gradient-norm / |x| reductions.
+// Jacobi scaling of the camera columns, cost / gradient-norm / |x| reductions.  What it hands to cam_solve (the window's
+// region of bv.Hcc): the entries of the scaled, undamped system S_c H S_c | S_c g_c that the solve reads - upper triangle of the
+// free slots + rhs, in the solve's own enumeration (schur_need_decode), back to back.
 // scratch: see cam_assemble_scratch.
 KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch) {
     const WinDesc& wd = bv.win[w];
-    const int nc = wd.nc;
-    double* H = scratch;
-    double* gps = scratch + nc * nc;  // ground-plane staging, reused by the regulariser rows afterwards
+    const int nc = wd.nc, nbt = cam_bt_count(nc);
+    double* H = scratch;      // the block tridiagonal (cam_bt_index)
+    double* gc = H + nbt;     // g_c, assembled here and stored once
+    double* sc = gc + nc;     // Jacobi scale of the slots
+    int* fl = reinterpret_cast<int*>(sc + nc);  // free slot (compact index) -> slot
+    double* gps = scratch + cam_assemble_head(nc);  // ground-plane staging, reused by the regulariser rows afterwards
     RegRow* rows = reinterpret_cast<RegRow*>(gps);
     double* dense = gps + cam_assemble_union(nc);  // dense regulariser rows, reused by the reductions afterwards
     double* red = dense;
-    double* gc = bv.gc + (int64_t)wd.cam0;
+    const uint8_t* cm = bv.cmask + (int64_t)wd.cam0;
+    const bool compute_scale = bv.st[w].compute_scale != 0;
     KBA_TICK(0);
-    for (int i = tid; i < nc * nc; i += nt) H[i] = 0.0;
+    for (int i = tid; i < nbt; i += nt) H[i] = 0.0;
     for (int i = tid; i < nc; i += nt) gc[i] = 0.0;
     // Ground-plane rows are staged through LDS in chunks (coalesced plane reads).  The first chunk is fetched here, ahead of
     // the observation sums: its memory round trip runs under theirs instead of after them.
@@ -1379,6 +1407,15 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     //     (cam_raw_entry: the view's Rc enters here, once per window instead of once per pair); one lane per (keyframe, entry):
     //     single writer, fixed order.
     double* raw = dense;  // [n_view][kLinPartial]: the dense regulariser rows only move in behind phase (2)
+    // What the hand-over at the end needs from memory - free slot -> slot, and the Jacobi scale where an earlier linearisation's is
+    // kept: one lane per slot where the workgroup covers the slots, fetched here so that the trip runs under the observation sums'
+    const bool slots_once = nc <= nt;
+    int ci0 = -1;
+    double sc0 = 1.0;
+    if (slots_once && tid < nc) {
+        ci0 = bv.cslot[wd.cam0 + tid];
+        if (!compute_scale) sc0 = bv.scale_c[wd.cam0 + tid];
+    }
     for (int e = tid; e < wd.n_view * kLinPartial; e += nt) {
         const double* lp = bv.lv_part + wd.lvpart_off + e;
         const int64_t stride = (int64_t)wd.n_view * kLinPartial;
@@ -1393,6 +1430,18 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         }
         for (; b < wd.n_lblk; ++b) acc += lp[b * stride];
         raw[e] = acc;
+    }
+    if (slots_once) {
+        if (tid < nc) {
+            if (ci0 >= 0) fl[ci0] = tid;
+            if (!compute_scale) sc[tid] = sc0;
+        }
+    } else {
+        for (int i = tid; i < nc; i += nt) {
+            const int ci = bv.cslot[wd.cam0 + i];
+            if (ci >= 0) fl[ci] = i;
+            if (!compute_scale) sc[i] = bv.scale_c[wd.cam0 + i];
+        }
     }
     KBA_SYNC();
     for (int e = tid; e < wd.n_kf * 27; e += nt) {
@@ -1409,8 +1458,7 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
                 ++a;
             }
             const int bb = a + rem;
-            H[(kl * kCamSlots + a) * nc + kl * kCamSlots + bb] += acc;
-            if (bb != a) H[(kl * kCamSlots + bb) * nc + kl * kCamSlots + a] += acc;
+            H[cam_bt_index(nc, kl * kCamSlots + a, kl * kCamSlots + bb)] += acc;
         } else {
             gc[kl * kCamSlots + (q - 21)] += acc;
         }
@@ -1425,12 +1473,13 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         for (int e = tid; e < wd.n_kf * 110; e += nt) {
             const int kl = e / 110, q = e % 110;
             const int a = q < 100 ? q / 10 : q - 100, bb = q < 100 ? q % 10 : 10;
-            const int lo = bb == 10 ? a : (a < bb ? a : bb), hi = bb == 10 ? 10 : (a < bb ? bb : a);
+            if (a > bb) continue;  // (the band keeps the upper triangle of a diagonal block)
+            const int lo = a, hi = bb;
             const int idx = hi == 10 ? 55 + lo : lo * 10 - lo * (lo - 1) / 2 + (hi - lo);
             double acc = 0.0;
             for (int sh = 0; sh < bv.gp_red_P; ++sh) acc += bv.gp_red[((int64_t)sh * bv.TK + wd.kf0 + kl) * kGpRed + idx];
             if (bb < 10)
-                H[(kl * kCamSlots + a) * nc + kl * kCamSlots + bb] += acc;
+                H[cam_bt_index(nc, kl * kCamSlots + a, kl * kCamSlots + bb)] += acc;
             else
                 gc[kl * kCamSlots + a] += acc;
         }
@@ -1469,9 +1518,9 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {  // f64 16x16x4 C / D layout: row = (lane >> 4) + 4 r, column = lane & 15
                     const int a = kq + 4 * r;
-                    if (a < 10 && li < 10)
-                        H[(kl * kCamSlots + a) * nc + kl * kCamSlots + li] += acc[r];
-                    else if (a < 10 && li == 10)
+                    if (a < 10 && li < 10) {
+                        if (a <= li) H[cam_bt_index(nc, kl * kCamSlots + a, kl * kCamSlots + li)] += acc[r];  // (the tile is symmetric)
+                    } else if (a < 10 && li == 10)
                         gc[kl * kCamSlots + a] += acc[r];
                 }
             }
@@ -1480,6 +1529,7 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         for (int e = tid; e < wd.n_kf * 110; e += nt) {
             const int kl = e / 110, q = e % 110;
             const int a = q < 100 ? q / 10 : q - 100, bb = q < 100 ? q % 10 : 10;
+            if (a > bb) continue;  // (the band keeps the upper triangle of a diagonal block)
             // rows are sorted by keyframe: this keyframe owns [kf_gp0, kf_gp0 + kf_ngp), clipped to the chunk
             int lo = bv.kf_gp0[wd.kf0 + kl] - g0, hi = lo + bv.kf_ngp[wd.kf0 + kl];
             lo = lo < 0 ? 0 : lo;
@@ -1487,7 +1537,7 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
             double acc = 0.0;
             for (int g = lo; g < hi; ++g) acc += gps[g * 12 + a] * gps[g * 12 + bb];
             if (bb < 10)
-                H[(kl * kCamSlots + a) * nc + kl * kCamSlots + bb] += acc;
+                H[cam_bt_index(nc, kl * kCamSlots + a, kl * kCamSlots + bb)] += acc;
             else
                 gc[kl * kCamSlots + a] += acc;
         }
@@ -1536,21 +1586,22 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     }
     KBA_SYNC();
     KBA_TICK(3);
-    // ... then every entry of the block tridiagonal of H (diagonal blocks, then the blocks (k, k+1) and their mirror
-    //     images) is owned by one lane, which adds the rows' products in row order: no serial pass over the rows,
-    //     same sum per entry for any lane count.
+    // ... then every entry of the band of H (upper triangles of the diagonal blocks, then the blocks (k, k+1)) is owned
+    //     by one lane, which adds the rows' products in row order: no serial pass over the rows, same sum per entry for
+    //     any lane count.
     for (int e = tid; e < (2 * wd.n_kf - 1) * kCamSlots * kCamSlots; e += nt) {
         const int blk = e / (kCamSlots * kCamSlots), q = e % (kCamSlots * kCamSlots);
         const int ka = blk < wd.n_kf ? blk : blk - wd.n_kf, kb = blk < wd.n_kf ? blk : ka + 1;
         const int a = ka * kCamSlots + q / kCamSlots, b = kb * kCamSlots + q % kCamSlots;
-        double acc = H[a * nc + b];
+        if (a > b) continue;  // (the band keeps the upper triangle of a diagonal block)
+        const int at = cam_bt_index(nc, a, b);
+        double acc = H[at];
         reg_rows_of_block(wd, ka, kb, [&](int lo, int cnt, int base) {
             const double* da = dense + lo * kRegDense + 2 + a - base * kCamSlots;
             const double* db = dense + lo * kRegDense + 2 + b - base * kCamSlots;
             for (int i = 0; i < cnt; ++i) acc += da[i * kRegDense] * db[i * kRegDense];
         });
-        H[a * nc + b] = acc;
-        if (ka != kb) H[b * nc + a] = acc;
+        H[at] = acc;
     }
     for (int a = tid; a < nc; a += nt) {
         double acc = gc[a];
@@ -1563,19 +1614,37 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     }
     KBA_SYNC();
     KBA_TICK(4);
-    // (4) mask constant / absent slots
-    const uint8_t* cm = bv.cmask + (int64_t)wd.cam0;
-    for (int i = tid; i < nc * nc; i += nt) {
-        if (!cm[i / nc] || !cm[i % nc]) H[i] = 0.0;
+    // (4) constant / absent slots: g_c is masked; H is not - the solve enumerates free slots only, so a masked row or column
+    //     of H is never handed over - and the Jacobi scale of such a slot is one
+    for (int i = tid; i < nc; i += nt) {
+        const double g = cm[i] ? gc[i] : 0.0;
+        gc[i] = g;
+        bv.gc[wd.cam0 + i] = g;
+        if (compute_scale) {
+            const double s = (cm[i] && c.jacobi_scaling) ? 1.0 / (1.0 + sqrt(H[cam_bt_index(nc, i, i)])) : 1.0;
+            sc[i] = s;
+            bv.scale_c[wd.cam0 + i] = s;
+        }
     }
-    for (int i = tid; i < nc; i += nt)
-        if (!cm[i]) gc[i] = 0.0;
     KBA_SYNC();
-    double* Hg = bv.Hcc + wd.hcc_off;
-    for (int i = tid; i < nc * nc; i += nt) Hg[i] = H[i];
-    if (bv.st[w].compute_scale) {
-        for (int i = tid; i < nc; i += nt)
-            bv.scale_c[wd.cam0 + i] = (cm[i] && c.jacobi_scaling) ? 1.0 / (1.0 + sqrt(H[i * nc + i])) : 1.0;
+    // ... and the hand-over: entry i of the solve's enumeration of [S_c H S_c | S_c g_c] at double i of the window's region,
+    //     consecutive lanes consecutive doubles.  An entry outside the band is the zero its product was.
+    {
+        double* Hg = bv.Hcc + wd.hcc_off;
+        const int nf = wd.nf, n_need = schur_need_count(nf);
+        for (int i = tid; i < n_need; i += nt) {
+            int ca, cb;
+            schur_need_decode(i, nf, ca, cb);
+            const int a = fl[ca];
+            double v;
+            if (cb < nf) {
+                const int b = fl[cb], e = cam_bt_index(nc, a, b);
+                v = e >= 0 ? sc[a] * sc[b] * H[e] : 0.0;
+            } else {
+                v = sc[a] * gc[a];
+            }
+            Hg[i] = v;
+        }
     }
     KBA_TICK(5);
     // (5) reductions
@@ -1647,22 +1716,23 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
 }
 
 // Workgroup-per-window: S = S_c H S_c + D^2 - sum Schur slabs, rhs = S_c g_c - sum slabs; dense Cholesky; camera
-// step, camera candidate, camera parts of the step reductions.  scratch: S (nc*nc) | v (3*nc) | red (nt).
+// step, camera candidate, camera parts of the step reductions.  S_c H S_c and S_c g_c arrive scaled and packed from cam_assemble (the
+// head of the window's Hcc region, entry i of the enumeration below at double i).  scratch: see cam_solve_scratch.
 KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch, int* flag) {
     // Works on the COMPACT system of the nf free slots.  scratch: A (nf x (nf+1), the rhs is column nf) | y (nf) |
-    // dl (nc) | fl (nf ints) | red (nt).
+    // dl (nc) | red (nt) | Hs.
     const WinDesc& wd = bv.win[w];
     const int nc = wd.nc, nf = wd.nf, nfp = wd.nf_pad, lda = nf + 1;
     double* A = scratch;
     double* y = A + nf * lda;
     double* dl = y + nf;
-    int* fl = reinterpret_cast<int*>(dl + nc);
-    double* red = dl + nc + (nf + 1) / 2 + 1;
+    double* red = dl + nc;
     // Hs: the entries of the scaled, UNDAMPED camera system and rhs (S_c H S_c | S_c g_c; upper triangle + rhs in the order of the
-    // assembly below) - what the model cost change of the step needs, kept from the assembly instead of read again from memory
+    // assembly below) - what the model cost change of the step needs: the hand-over entries as they were loaded for the assembly
+    // below, kept in LDS instead of read from memory a second time
     double* Hs = red + coop_red_doubles(3, nt);
     const double radius = bv.st[w].radius;
-    const double* Hg = bv.Hcc + wd.hcc_off;
+    const double* Hg = bv.Hcc + wd.hcc_off;  // cam_assemble's hand-over: those entries, in this order
     const double* sc = bv.scale_c + wd.cam0;
     const int32_t* cs = bv.cslot + wd.cam0;
     double* yc = bv.yc + wd.cam0;
@@ -1670,9 +1740,6 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     const int slab = c.schur_packed ? schur_need_pad(nf) : nfp * nfp;
     const int nfq = wd.nfq;
     KBA_TICK(8);
-    for (int a = tid; a < nc; a += nt)
-        if (cs[a] >= 0) fl[cs[a]] = a;
-    KBA_SYNC();
     // ---- assemble [S | rhs]: S = S_c H S_c + D^2 - sum slabs (upper triangle), rhs = S_c g_c - sum slabs
     // partial slabs of the Schur workgroups, or (landmark-sharded solve) the per-shard sums of them
     const double* sp = c.schur_nslab > 0 ? bv.S_red + wd.sred_off : bv.S_part + wd.spart_off;
@@ -1713,18 +1780,9 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
             if (i >= n_need) continue;
             int ca, cb;
             schur_need_decode(i, nf, ca, cb);
-            const int a = fl[ca];
-            double s_e;
-            if (cb < nf) {
-                const int b = fl[cb];
-                double v = sc[a] * sc[b] * Hg[a * nc + b];
-                Hs[i] = v;
-                if (ca == cb) v += fmin(fmax(v, c.min_lm_diagonal), c.max_lm_diagonal) / radius;
-                s_e = v;
-            } else {
-                s_e = sc[a] * bv.gc[wd.cam0 + a];
-                Hs[i] = s_e;
-            }
+            double s_e = Hg[i];  // (one coalesced load, on its way together with the slab entries below)
+            Hs[i] = s_e;
+            if (ca == cb) s_e += fmin(fmax(s_e, c.min_lm_diagonal), c.max_lm_diagonal) / radius;
             // (packed slabs - of a sharded solve's S_red, ground-plane slabs of S_part - hold exactly these entries in this order)
             off[e] = (c.schur_packed || pk) ? i : (int)schur_need_offset(ca, cb, nf, nfq, nfp);
             if (pk) off_pl[e] = slab_packed_read(false, ca, cb, nf, nfq);

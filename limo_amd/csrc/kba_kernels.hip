@@ -1355,7 +1355,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) 
 #ifdef KBA_PROFILE_TICKS
         if (w == 0 && threadIdx.x == 0)
             for (int l = 0; l < 2; ++l)
-                printf("[ticks cam_assemble %s lane] observation blocks %lld, ground-plane rows %lld, regulariser rows %lld, their sums %lld, mask + store %lld, reductions %lld\n",
+                printf("[ticks cam_assemble %s lane] observation blocks %lld, ground-plane rows %lld, regulariser rows %lld, their sums %lld, scale + hand-over %lld, reductions %lld\n",
                        l ? "last" : "first", kba_ticks[l][1] - kba_ticks[l][0], kba_ticks[l][2] - kba_ticks[l][1], kba_ticks[l][3] - kba_ticks[l][2],
                        kba_ticks[l][4] - kba_ticks[l][3], kba_ticks[l][5] - kba_ticks[l][4], kba_ticks[l][6] - kba_ticks[l][5]);
 #endif
@@ -2041,7 +2041,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
 #ifdef KBA_PROFILE_TICKS  // (debug build: the phase stamps cam_assemble / cam_solve took in their LAST call, shader clocks)
     if (w == 0 && g == 0 && tid == 0)
         for (int l = 0; l < 2; ++l) {
-            printf("[coop ticks cam_assemble %s lane] observation blocks %lld, ground-plane rows %lld, regulariser rows %lld, their sums %lld, mask + store %lld, reductions %lld\n",
+            printf("[coop ticks cam_assemble %s lane] observation blocks %lld, ground-plane rows %lld, regulariser rows %lld, their sums %lld, scale + hand-over %lld, reductions %lld\n",
                    l ? "last" : "first", kba_ticks[l][1] - kba_ticks[l][0], kba_ticks[l][2] - kba_ticks[l][1], kba_ticks[l][3] - kba_ticks[l][2],
                    kba_ticks[l][4] - kba_ticks[l][3], kba_ticks[l][5] - kba_ticks[l][4], kba_ticks[l][6] - kba_ticks[l][5]);
             printf("[coop ticks cam_solve %s lane] slab sum %lld, cholesky %lld, back-substitution %lld, step %lld (of it: model cost change %lld), reduction %lld\n", l ? "last" : "first",

@@ -87,7 +87,9 @@ struct WinDesc {
                               // (the constant landmarks of a pose-only window are not counted: no fixed cost, no Schur blocks at all)
     double scale_w, scale_s0; // PoseRegularization weight and target
     double speed_w, speed_dt, speed_vel[3], speed_Rb[9], speed_tb[3];  // SpeedRegularizationVector2 (pose-only)
-    int64_t hcc_off;          // offset (doubles) of this window's nc x nc matrix in the Hcc buffer
+    int64_t hcc_off;          // offset (doubles) of this window's region in the Hcc buffer.  The region keeps a stride of nc * nc doubles
+                              // (the packer's prefix sums and the emulator tests count on it); its head holds what cam_assemble hands
+                              // to cam_solve: schur_need_count(nf) <= nc * nc doubles (kba_items.hpp:cam_assemble)
     int64_t spart_off;        // offset of this window's Schur partial slabs
     int64_t sred_off;         // offset of this window's per-shard contributions in the consumer's S_red: n_shards x schur_need_pad(nf)
                               // (a shard's own block holds one of them at sred_off / n_shards)
@@ -313,7 +315,7 @@ struct BatchView {
     double* lm_Li;              // planes [6][SL]  Bt = L^-1 S of the damped landmark block (V' + D^2) = L L^T (lm_damp_store)
     double* lblk_part;          // [n_lblk*8]: gmax, xnorm2, mcc, step2, cand2, fail, -, -
     // --- camera side
-    double *Hcc, *gc;           // per window nc*nc (hcc_off) ; [TK*10]
+    double *Hcc, *gc;           // per window: the hand-over S_c H S_c | S_c g_c of the free slots, packed, at the head of a region of nc*nc (hcc_off) ; [TK*10] masked g_c
     double *scale_c, *yc, *delta_c;  // [TK*10]
     double *S_part;             // Schur partial slabs
     double *S_red;              // landmark-sharded solve: one slab per (window, shard) = sum of the shard's partial slabs
