@@ -277,6 +277,17 @@ int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]);
  *   info[3]  launches of the solve in which three-panel ground-plane waves ran: for the wide groups, next to the narrow waves in
  *            the same launch; for every group in a batch that classified nothing and under KBA_SCHUR_GP_WIDE=1 (info[2] is 0 then) */
 int limo_ctx_last_schur_gp_info(const limo_ctx* ctx, int64_t info[4]);
+/* Which form the camera launches (k_cam_assemble, k_cam_solve) of the last limo_ba_batch_solve on this context took: 128 lanes per
+ * window or 256, the same bits either way.  The launch sequence picks per launch (128 lanes where the launch lists more windows than
+ * 256-lane workgroups fit the device at once, and the batch allows it); KBA_CAM_LANES=128 / 256 forces one form where allowed.  The
+ * one-launch paths (info[0] of limo_ctx_last_solve_info 1, 2) count nothing here.
+ *   info[0]  launches of k_cam_assemble with 128 lanes,  info[1]  with 256
+ *   info[2]  launches of k_cam_solve with 128 lanes,     info[3]  with 256
+ *   info[4..7]  workgroups per compute unit at the batch's LDS sizes: k_cam_assemble 128 / 256 lanes, k_cam_solve 128 / 256 lanes
+ *   info[8]  windows of the batch whose camera system works in global memory (12 keyframes and up): one of them keeps every camera
+ *            launch of the batch at 256 lanes
+ * (A call of its own because all eight entries of limo_ctx_last_solve_info are taken; added without an ABI bump, like that one.) */
+int limo_ctx_last_cam_lanes_info(const limo_ctx* ctx, int64_t info[9]);
 
 /*
  * Per-iteration solver log: what the reference prints for every solve (minimizer_progress_to_stdout = true,

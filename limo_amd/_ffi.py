@@ -378,6 +378,7 @@ ABI_SYMBOLS = [
     "limo_ctx_coop_fallbacks",
     "limo_ctx_last_solve_info",
     "limo_ctx_last_schur_gp_info",
+    "limo_ctx_last_cam_lanes_info",
     "limo_ctx_set_iteration_log",
     "limo_ba_batch_iteration_log",
     "limo_ctx_last_iteration_log",
@@ -520,6 +521,8 @@ def load():
         lib.limo_ctx_last_solve_info.argtypes = [vp, c_int64_p]
     if hasattr(lib, "limo_ctx_last_schur_gp_info"):  # (added without an ABI bump as well)
         lib.limo_ctx_last_schur_gp_info.argtypes = [vp, c_int64_p]
+    if hasattr(lib, "limo_ctx_last_cam_lanes_info"):  # (added without an ABI bump as well)
+        lib.limo_ctx_last_cam_lanes_info.argtypes = [vp, c_int64_p]
     if hasattr(lib, "limo_ctx_set_iteration_log"):  # (added without an ABI bump, as the ones above)
         lib.limo_ctx_set_iteration_log.argtypes = [vp, C.c_int32]
         lib.limo_ba_batch_iteration_log.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(BaIteration), c_int32_p]

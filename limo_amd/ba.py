@@ -103,6 +103,16 @@ class Context:
         _check(self.lib.limo_ctx_last_schur_gp_info(self.ptr, v), self.ptr, "limo_ctx_last_schur_gp_info")
         return dict(zip(("narrow_groups", "wide_groups", "narrow_launches", "wide_launches"), (int(x) for x in v)))
 
+    def last_cam_lanes_info(self):
+        """limo_ctx_last_cam_lanes_info: how many launches of k_cam_assemble / k_cam_solve of the last solve on this context ran with
+        128 and with 256 lanes per window, the workgroups per compute unit of the four instances, and the windows of the batch whose
+        camera system works in global memory."""
+        v = (C.c_int64 * 9)()
+        _check(self.lib.limo_ctx_last_cam_lanes_info(self.ptr, v), self.ptr, "limo_ctx_last_cam_lanes_info")
+        keys = ("assemble_128", "assemble_256", "solve_128", "solve_256", "wg_per_cu_assemble_128", "wg_per_cu_assemble_256",
+                "wg_per_cu_solve_128", "wg_per_cu_solve_256", "global_class_windows")
+        return dict(zip(keys, (int(x) for x in v)))
+
     def set_iteration_log(self, on):
         """limo_ctx_set_iteration_log: the solves on this context record Ceres' per-iteration table (off by default)."""
         _check(self.lib.limo_ctx_set_iteration_log(self.ptr, int(bool(on))), self.ptr, "limo_ctx_set_iteration_log")

@@ -136,7 +136,8 @@ struct SolveSwitches {
     double coop_timeout_ms = 50.0;  // KBA_COOP_TIMEOUT_MS: what a barrier of k_solve_coop waits before it gives the launch up
     bool groups_set = false;      // KBA_GROUPS is set ...
     int groups = 0;               // ... slot groups of a streaming solve (stream_geometry clamps to 1 .. 4) instead of its own rule
-    bool gp_wide = false;         // KBA_SCHUR_GP_WIDE (debugging aid): every ground-plane group runs the three-panel tile, the narrow kernel never
+    int cam_lanes = 0;            // KBA_CAM_LANES (test hook): 128 / 256 force that form of the camera kernels where the batch allows it; else 0: cam_lanes_for_launch's rule
+    bool gp_wide = false;        // KBA_SCHUR_GP_WIDE (debugging aid): every ground-plane group runs the three-panel tile, the narrow kernel never
 };
 
 inline SolveSwitches read_solve_switches() {
@@ -157,8 +158,49 @@ inline SolveSwitches read_solve_switches() {
         s.groups_set = true;
         s.groups = std::atoi(e);
     }
+    if (const char* e = std::getenv("KBA_CAM_LANES")) {
+        const int v = std::atoi(e);
+        s.cam_lanes = v == kCamLanesHalf || v == kBlock ? v : 0;
+    }
     s.gp_wide = on("KBA_SCHUR_GP_WIDE");
     return s;
+}
+
+// ------------------------------------------------------------------------------------------------ lanes of the camera kernels
+// k_cam_assemble / k_cam_solve exist with kBlock lanes per window and with kCamLanesHalf lanes that give every window the SAME bits
+// (kba_items.hpp:cam_assemble, virtual lanes), so the choice is free per launch.  Half the lanes hold half the registers for the
+// length of a window's dependent chain: twice the windows per CU, each somewhat slower.  That pays where a launch is bound by its
+// passes over the device (windows / resident windows), not by one chain.
+struct CamOccupancy {  // from the HIP runtime (limo_hip.hip): workgroups per CU at the plan's LDS sizes, compute units of the device
+    int n_cu = 0;
+    int asm_full = 0, asm_half = 0, solve_full = 0, solve_half = 0;
+};
+struct CamLanesPlan {
+    bool asm_half_ok = false, solve_half_ok = false;  // the batch allows the half form of the kernel
+    int asm_resident = 0, solve_resident = 0;         // windows the FULL form holds resident on the device
+};
+// Per batch.  The half form serves LDS-class windows whose slots one lane each covers (cam_assemble's slots_once), in the launch-
+// sequence paths of an unsharded solve batch (`plain`: not sharded, not a pose-only batch - those keep kBlock lanes), and only where
+// it at least doubles the workgroups per CU.  (The pack's LDS / global classification -
+// kba_items.hpp:cam_class_doubles - does not depend on the form: no window changes class.)
+inline CamLanesPlan plan_cam_lanes(const PackedBatch& P, const CamOccupancy& occ, bool plain) {
+    CamLanesPlan p;
+    p.asm_resident = occ.n_cu * occ.asm_full;
+    p.solve_resident = occ.n_cu * occ.solve_full;
+    bool ok = plain && P.n_win > 0;
+    for (const WinDesc& d : P.win) ok = ok && d.cam_scr_off < 0 && d.nc <= kCamLanesHalf;
+    p.asm_half_ok = ok && occ.asm_full > 0 && occ.asm_half >= 2 * occ.asm_full;
+    p.solve_half_ok = ok && occ.solve_full > 0 && occ.solve_half >= 2 * occ.solve_full;
+    return p;
+}
+// Per launch: the half form when the launch lists more windows than kCamLanesFactor x what the full form holds resident.  Below
+// that - a draining round, a batch of ~1000 windows or fewer, a single window - the launch is one pass, bound by one chain: kBlock
+// lanes.  forced: SolveSwitches::cam_lanes.
+constexpr int kCamLanesFactor = 1;
+inline int cam_lanes_for_launch(bool half_ok, int resident_full, int n_listed, int forced) {
+    if (!half_ok || forced == kBlock) return kBlock;
+    if (forced == kCamLanesHalf) return kCamLanesHalf;
+    return n_listed > kCamLanesFactor * resident_full ? kCamLanesHalf : kBlock;
 }
 
 enum SolvePath { PATH_NONE = 0, PATH_WG = 1, PATH_COOP = 2, PATH_STREAMING = 3, PATH_LOCKSTEP = 4 };  // (limo_ctx_last_solve_info)

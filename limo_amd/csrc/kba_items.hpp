@@ -1271,44 +1271,58 @@ KBA_HD double block_grad_inf(int kind, const double* x, const double* g) {
 // results.  red: N * nt doubles (host tree) / N * (nt / 64) doubles (device).  On gfx950 the waves reduce with
 // butterfly shuffles (every lane of a wave ends with the same bits) and meet once in LDS: one barrier instead of
 // log2(nt) of them - the trees were 4-5 us of each window-level kernel.
+// vrep > 1: the reduction of vrep * nt VIRTUAL lanes by nt physical ones.  Lane tid brings the values of the virtual lanes
+// tid + u * nt at v[u * N + q], u < vrep.  Every virtual wave runs its own butterfly and has its own slot of `red`, and the slots
+// (the tree) are folded as a workgroup of vrep * nt lanes folds them: the bits of that workgroup.  red: as for vrep * nt lanes.
 template <int N, int NSUM>
-KBA_HD void coop_reduce(double* v, int tid, int nt, double* red) {
+KBA_HD void coop_reduce(double* v, int tid, int nt, double* red, int vrep = 1) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (nt >= 64 && (nt & 63) == 0) {
         const int wave = tid >> 6, nw = nt >> 6;
-        for (int q = 0; q < N; ++q) {
-            double x = v[q];
-            for (int off = 32; off > 0; off >>= 1) {
-                const double o = __shfl_xor(x, off, 64);
-                x = q < NSUM ? x + o : fmax(x, o);
+        for (int u = 0; u < vrep; ++u)
+            for (int q = 0; q < N; ++q) {
+                double x = v[u * N + q];
+                for (int off = 32; off > 0; off >>= 1) {
+                    const double o = __shfl_xor(x, off, 64);
+                    x = q < NSUM ? x + o : fmax(x, o);
+                }
+                if ((tid & 63) == 0) red[(u * nw + wave) * N + q] = x;
             }
-            if ((tid & 63) == 0) red[wave * N + q] = x;
-        }
         KBA_SYNC();
         for (int q = 0; q < N; ++q) {
             double x = red[q];
-            for (int u = 1; u < nw; ++u) x = q < NSUM ? x + red[u * N + q] : fmax(x, red[u * N + q]);
+            for (int u = 1; u < nw * vrep; ++u) x = q < NSUM ? x + red[u * N + q] : fmax(x, red[u * N + q]);
             v[q] = x;
         }
         KBA_SYNC();
         return;
     }
 #endif
-    for (int q = 0; q < N; ++q) red[q * nt + tid] = v[q];
+    const int nvl = nt * vrep;
+    for (int u = 0; u < vrep; ++u)
+        for (int q = 0; q < N; ++q) red[q * nvl + tid + u * nt] = v[u * N + q];
     KBA_SYNC();
-    for (int s = nt >> 1; s > 0; s >>= 1) {
-        if (tid < s) {
-            for (int q = 0; q < NSUM; ++q) red[q * nt + tid] += red[q * nt + tid + s];
-            for (int q = NSUM; q < N; ++q) red[q * nt + tid] = fmax(red[q * nt + tid], red[q * nt + tid + s]);
+    for (int s = nvl >> 1; s > 0; s >>= 1) {
+        for (int t = tid; t < s; t += nt) {
+            for (int q = 0; q < NSUM; ++q) red[q * nvl + t] += red[q * nvl + t + s];
+            for (int q = NSUM; q < N; ++q) red[q * nvl + t] = fmax(red[q * nvl + t], red[q * nvl + t + s]);
         }
         KBA_SYNC();
     }
-    for (int q = 0; q < N; ++q) v[q] = red[q * nt];
+    for (int q = 0; q < N; ++q) v[q] = red[q * nvl];
     KBA_SYNC();
 }
 
-// doubles coop_reduce<N, .> needs in `red` for nt lanes: one slot per wave on the device, a full tree on the host
+// doubles coop_reduce<N, .> needs in `red` for nt lanes (virtual ones counted: vrep * nt): one slot per wave on the device, a full
+// tree on the host
+// (KBA_HOST_LANES: a host build that runs the items on MANY lanes, tests/cpp/test_cam_lanes.cpp - the host's tree needs a double per
+// lane and value whatever nt, so every scratch layout of that build has the tree's `red` region.  The device layout's `red` bound, 12 /
+// 24 doubles, is therefore NOT held by that sanitised host test; the device slots are exercised on the GPU only.)
+#if defined(KBA_HOST_LANES)
+KBA_HD int coop_red_doubles(int n, int nt) { return n * nt; }
+#else
 KBA_HD int coop_red_doubles(int n, int nt) { return n * ((nt >= 64 && (nt & 63) == 0) ? nt >> 6 : nt); }
+#endif
 
 // scratch doubles needed by cam_assemble / cam_solve for a system of nc slots and nt lanes
 constexpr int kGpChunk = 128;  // ground-plane rows staged in LDS per pass of cam_assemble
@@ -1360,7 +1374,16 @@ KBA_HD int cam_assemble_scratch(int nc, int nt, int n_view) {
 constexpr int kCamLdsCapBytes = 150 * 1024;
 KBA_HD int cam_solve_scratch(int nc, int nt, int nf = -1) {
     if (nf < 0) nf = nc;  // (nf: free slots of the compact system, <= nc)
-    return nf * (nf + 1) + nf + nc + coop_red_doubles(3, nt) + nf * (nf + 1) / 2 + nf;  // A | y | dl | red | Hs
+    return nf * (nf + 1) + nf + nc + coop_red_doubles(3, nt) + 2 * nf;  // A | y | dl | red | Hd
+}
+// What the pack classifies a window by (LDS or global memory, against kCamLdsCapBytes) and sizes its global scratch with: the larger
+// of the two scratches, the solve's counted as it was while its copy of the undamped system had a region of its own (nc (nc + 1) / 2 +
+// nc doubles more than cam_solve_scratch, ~1.5 nc^2 in all).  The class boundary is part of what a batch's plan, its launch paths and
+// its LDS sizes were measured with: 149.7 KB at 11 keyframes, 177 KB at 12.  The solve's smaller layout does not move it.
+KBA_HD int cam_class_doubles(int nc, int n_view) {
+    const int solve = cam_solve_scratch(nc, kBlock) - 2 * nc + nc * (nc + 1) / 2 + nc;
+    const int assemble = cam_assemble_scratch(nc, kBlock, n_view);
+    return assemble > solve ? assemble : solve;
 }
 
 // Workgroup-per-window: assemble the camera-camera normal equations H_cc, g_c at the linearisation point, the
@@ -1368,9 +1391,15 @@ KBA_HD int cam_solve_scratch(int nc, int nt, int nf = -1) {
 // region of bv.Hcc): the entries of the scaled, undamped system S_c H S_c | S_c g_c that the solve reads - upper triangle of the
 // free slots + rhs, in the solve's own enumeration (schur_need_decode), back to back.
 // scratch: see cam_assemble_scratch.
-KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch) {
+// nvl: VIRTUAL lanes, 0 (= nt) or 2 * nt.  With nvl = 2 * nt the nt lanes do what a workgroup of nvl lanes does wherever the result or
+// the path depends on the lane count - per-lane partial sums of the reductions (lane tid forms those of the virtual lanes tid and
+// tid + nt apart), regulariser rows by wave, the device forms for 256 lanes - and so give every window that workgroup's bits: 128
+// lanes hold half the registers of 256 for the length of a window's chain (k_cam_assemble<128>).  scratch: as for nvl lanes.
+KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch, int nvl = 0) {
     const WinDesc& wd = bv.win[w];
     const int nc = wd.nc, nbt = cam_bt_count(nc);
+    if (nvl <= 0) nvl = nt;
+    const int vrep = nvl / nt;  // 1 or 2
     double* H = scratch;      // the block tridiagonal (cam_bt_index)
     double* gc = H + nbt;     // g_c, assembled here and stored once
     double* sc = gc + nc;     // Jacobi scale of the slots
@@ -1499,10 +1528,10 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         // reads each, on three passes of the workgroup (11 of the 30 us of this function, profiles/r03_single_window_phase_ticks.txt).
         // Same products; an entry's rows are added four at a time inside the instruction (all device paths share this code, the
         // CPU-tier emulation keeps the loop below).
-        if (nt == 256) {
+        if (nvl == 256) {  // (a wave per keyframe: a keyframe's tile does not depend on which wave runs it)
             typedef double v4d_t __attribute__((ext_vector_type(4)));
             const int lane = tid & 63, li = lane & 15, kq = lane >> 4;
-            for (int kl = tid >> 6; kl < wd.n_kf; kl += 4) {
+            for (int kl = tid >> 6; kl < wd.n_kf; kl += nt >> 6) {
                 int lo = bv.kf_gp0[wd.kf0 + kl] - g0, hi = lo + bv.kf_ngp[wd.kf0 + kl];
                 lo = lo < 0 ? 0 : lo;
                 hi = hi > ng ? ng : hi;
@@ -1552,10 +1581,11 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
     // full workgroup every wave gets one kind: 0 motion rows, 1 normal-difference rows, 2 distance rows (+ the
     // scale row), 3 the per-keyframe and speed rows.
     const int reg_base = wd.has_scale_reg ? 1 : 0, reg_npair = wd.has_gp_reg ? wd.n_kf - 1 : 0;
-    for (int i0 = tid; i0 < (nt >= 256 ? nt : nrows); i0 += nt) {
+    // (virtual lanes: a wave takes the kinds wv, wv + nt / 64, ... in turn; a row's value does not depend on its lane)
+    for (int i0 = tid; i0 < (nvl >= 256 ? nvl : nrows); i0 += nt) {
         int i = i0;
-        if (nt >= 256) {
-            const int wv = tid >> 6, ln = tid & 63;
+        if (nvl >= 256) {
+            const int wv = i0 >> 6, ln = i0 & 63;
             i = -1;
             if (wv == 0) {
                 if (ln < reg_npair) i = reg_base + ln * 5 + 4;
@@ -1647,61 +1677,67 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
         }
     }
     KBA_TICK(5);
-    // (5) reductions
-    double cost = 0.0, failf = 0.0, gmax = 0.0, xn2 = 0.0, reg_free = 0.0, reg_fixed = 0.0;
-    for (int i = tid; i < wd.n_lblk * wd.n_view; i += nt) cost += bv.lv_part[wd.lvpart_off + (int64_t)i * kLinPartial];
-    for (int b = wd.lblk0 + tid; b < wd.lblk0 + wd.n_lblk; b += nt)
-        if (bv.lblk_linfail[b] != 0.0) failf = 1.0;
-    if (wd.n_lm_const) {  // (uniform) constant landmarks: blocks without a variable parameter are fixed cost - the pairs of a constant
-                          // landmark with a view without a free pose block (kLinFixedCost), ground rows of such a keyframe and landmark
-        for (int i = tid; i < wd.n_lblk * wd.n_view_fixed0; i += nt)
-            reg_fixed += bv.lv_part[wd.lvpart_off + ((int64_t)(i / wd.n_view_fixed0) * wd.n_view + i % wd.n_view_fixed0) * kLinPartial + kLinFixedCost];
-        for (int g = wd.gp0 + tid; g < wd.gp0 + wd.n_gp; g += nt) {
-            const double v = bv.gp_cost[g];
-            const bool fixed = gp_row_fixed(bv, g);
-            cost += fixed ? 0.0 : v;
-            reg_fixed += fixed ? v : 0.0;
+    // (5) reductions: the partial sums of the virtual lane(s) of this lane, each over its own entries vt, vt + nvl, ...
+    double v[2 * 6];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {  // (unrolled: v stays in registers)
+        if (u >= vrep) break;
+        const int vt = tid + u * nt;
+        double cost = 0.0, failf = 0.0, gmax = 0.0, xn2 = 0.0, reg_free = 0.0, reg_fixed = 0.0;
+        for (int i = vt; i < wd.n_lblk * wd.n_view; i += nvl) cost += bv.lv_part[wd.lvpart_off + (int64_t)i * kLinPartial];
+        for (int b = wd.lblk0 + vt; b < wd.lblk0 + wd.n_lblk; b += nvl)
+            if (bv.lblk_linfail[b] != 0.0) failf = 1.0;
+        if (wd.n_lm_const) {  // (uniform) constant landmarks: blocks without a variable parameter are fixed cost - the pairs of a constant
+                              // landmark with a view without a free pose block (kLinFixedCost), ground rows of such a keyframe and landmark
+            for (int i = vt; i < wd.n_lblk * wd.n_view_fixed0; i += nvl)
+                reg_fixed += bv.lv_part[wd.lvpart_off + ((int64_t)(i / wd.n_view_fixed0) * wd.n_view + i % wd.n_view_fixed0) * kLinPartial + kLinFixedCost];
+            for (int g = wd.gp0 + vt; g < wd.gp0 + wd.n_gp; g += nvl) {
+                const double gv = bv.gp_cost[g];
+                const bool fixed = gp_row_fixed(bv, g);
+                cost += fixed ? 0.0 : gv;
+                reg_fixed += fixed ? gv : 0.0;
+            }
+        } else {
+            for (int g = wd.gp0 + vt; g < wd.gp0 + wd.n_gp; g += nvl) cost += bv.gp_cost[g];
         }
-    } else {
-        for (int g = wd.gp0 + tid; g < wd.gp0 + wd.n_gp; g += nt) cost += bv.gp_cost[g];
-    }
-    for (int i = tid; i < nrows; i += nt) {
-        if (rows[i].n < 0)
-            reg_fixed += 0.5 * rows[i].r * rows[i].r;
-        else
-            reg_free += 0.5 * rows[i].r * rows[i].r;
-    }
-    for (int b = wd.lblk0 + tid; b < wd.lblk0 + wd.n_lblk; b += nt) {
-        gmax = fmax(gmax, bv.lblk_part[(int64_t)b * 8 + 0]);
-        xn2 += bv.lblk_part[(int64_t)b * 8 + 1];
-    }
-    for (int k = tid; k < wd.n_kf; k += nt) {
-        const int gk = wd.kf0 + k;
-        if (cm[k * kCamSlots + 0]) {
-            const double* x = bv.pose + 7 * (int64_t)gk;
-            gmax = fmax(gmax, block_grad_inf(0, x, gc + k * kCamSlots));
-            for (int i = 0; i < 7; ++i) xn2 += x[i] * x[i];
+        for (int i = vt; i < nrows; i += nvl) {
+            if (rows[i].n < 0)
+                reg_fixed += 0.5 * rows[i].r * rows[i].r;
+            else
+                reg_free += 0.5 * rows[i].r * rows[i].r;
         }
-        if (cm[k * kCamSlots + 6]) {
-            const double* x = bv.pdir + 3 * (int64_t)gk;
-            gmax = fmax(gmax, block_grad_inf(1, x, gc + k * kCamSlots + 6));
-            for (int i = 0; i < 3; ++i) xn2 += x[i] * x[i];
+        for (int b = wd.lblk0 + vt; b < wd.lblk0 + wd.n_lblk; b += nvl) {
+            gmax = fmax(gmax, bv.lblk_part[(int64_t)b * 8 + 0]);
+            xn2 += bv.lblk_part[(int64_t)b * 8 + 1];
         }
-        if (cm[k * kCamSlots + 9]) {
-            gmax = fmax(gmax, block_grad_inf(2, bv.pdist + gk, gc + k * kCamSlots + 9));
-            xn2 += bv.pdist[gk] * bv.pdist[gk];
+        for (int k = vt; k < wd.n_kf; k += nvl) {
+            const int gk = wd.kf0 + k;
+            if (cm[k * kCamSlots + 0]) {
+                const double* x = bv.pose + 7 * (int64_t)gk;
+                gmax = fmax(gmax, block_grad_inf(0, x, gc + k * kCamSlots));
+                for (int i = 0; i < 7; ++i) xn2 += x[i] * x[i];
+            }
+            if (cm[k * kCamSlots + 6]) {
+                const double* x = bv.pdir + 3 * (int64_t)gk;
+                gmax = fmax(gmax, block_grad_inf(1, x, gc + k * kCamSlots + 6));
+                for (int i = 0; i < 3; ++i) xn2 += x[i] * x[i];
+            }
+            if (cm[k * kCamSlots + 9]) {
+                gmax = fmax(gmax, block_grad_inf(2, bv.pdist + gk, gc + k * kCamSlots + 9));
+                xn2 += bv.pdist[gk] * bv.pdist[gk];
+            }
         }
+        double* vu = v + 6 * u;
+        vu[0] = reg_free;
+        vu[1] = reg_fixed;
+        vu[2] = cost;
+        vu[3] = xn2;
+        vu[4] = failf;
+        vu[5] = gmax;
     }
-    {   // six reductions at once (4 sums, 2 maxima); red holds 6*nt doubles
-        double v[6] = {reg_free, reg_fixed, cost, xn2, failf, gmax};
-        coop_reduce<6, 4>(v, tid, nt, red);
-        reg_free = v[0];
-        reg_fixed = v[1];
-        cost = v[2] + reg_free;
-        xn2 = v[3];
-        failf = v[4];
-        gmax = v[5];
-    }
+    // six reductions at once (4 sums, 2 maxima); red holds 6 * nvl doubles (host tree) / six per virtual wave (device)
+    coop_reduce<6, 4>(v, tid, nt, red, vrep);
+    const double reg_free = v[0], reg_fixed = v[1], cost = v[2] + reg_free, xn2 = v[3], failf = v[4], gmax = v[5];
     if (tid == 0) {
         WinRed& r = bv.red[w];
         r.lin_cost = cost;
@@ -1718,19 +1754,27 @@ KBA_HD void cam_assemble(const BatchView& bv, const SolveConsts& c, int w, int t
 // Workgroup-per-window: S = S_c H S_c + D^2 - sum Schur slabs, rhs = S_c g_c - sum slabs; dense Cholesky; camera
 // step, camera candidate, camera parts of the step reductions.  S_c H S_c and S_c g_c arrive scaled and packed from cam_assemble (the
 // head of the window's Hcc region, entry i of the enumeration below at double i).  scratch: see cam_solve_scratch.
-KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch, int* flag) {
+// nvl: virtual lanes as in cam_assemble (0 = nt, or 2 * nt: the bits and the scratch layout of a workgroup of nvl lanes; for windows
+// of nc <= nt slots only).
+KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch, int* flag, int nvl = 0) {
     // Works on the COMPACT system of the nf free slots.  scratch: A (nf x (nf+1), the rhs is column nf) | y (nf) |
-    // dl (nc) | red (nt) | Hs.
+    // dl (nc) | red (nvl) | Hd (2 nf).
     const WinDesc& wd = bv.win[w];
     const int nc = wd.nc, nf = wd.nf, nfp = wd.nf_pad, lda = nf + 1;
+    if (nvl <= 0) nvl = nt;
+    const int vrep = nvl / nt;  // 1 or 2
     double* A = scratch;
     double* y = A + nf * lda;
     double* dl = y + nf;
     double* red = dl + nc;
     // Hs: the entries of the scaled, UNDAMPED camera system and rhs (S_c H S_c | S_c g_c; upper triangle + rhs in the order of the
     // assembly below) - what the model cost change of the step needs: the hand-over entries as they were loaded for the assembly
-    // below, kept in LDS instead of read from memory a second time
-    double* Hs = red + coop_red_doubles(3, nt);
+    // below, kept in LDS instead of read from memory a second time.  Entry (ca, cb), ca < cb < nf, waits at A[cb][ca]: the factorisation
+    // works on the upper triangle and the rhs column and never reads or writes A below its diagonal (the pivot block loads whole rows,
+    // and uses the lanes from the diagonal on); the diagonal and the rhs wait in Hd.  14.6 KB per window instead of 20.8 at C2: LDS no
+    // longer bounds the windows per CU.
+    double* Hd = red + coop_red_doubles(3, nvl);
+    auto hs_at = [&](int ca, int cb) -> double& { return cb == ca ? Hd[ca] : cb == nf ? Hd[nf + ca] : A[cb * lda + ca]; };
     const double radius = bv.st[w].radius;
     const double* Hg = bv.Hcc + wd.hcc_off;  // cam_assemble's hand-over: those entries, in this order
     const double* sc = bv.scale_c + wd.cam0;
@@ -1781,7 +1825,7 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
             int ca, cb;
             schur_need_decode(i, nf, ca, cb);
             double s_e = Hg[i];  // (one coalesced load, on its way together with the slab entries below)
-            Hs[i] = s_e;
+            hs_at(ca, cb) = s_e;
             if (ca == cb) s_e += fmin(fmax(s_e, c.min_lm_diagonal), c.max_lm_diagonal) / radius;
             // (packed slabs - of a sharded solve's S_red, ground-plane slabs of S_part - hold exactly these entries in this order)
             off[e] = (c.schur_packed || pk) ? i : (int)schur_need_offset(ca, cb, nf, nfq, nfp);
@@ -1841,9 +1885,9 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     // Two workgroup barriers per block instead of four.  Same pivots, same failure rule; the four products of an entry are added
     // inside the MFMA instead of one after the other, so results differ from the loop below by rounding (all device paths share
     // this code; the CPU-tier emulation keeps the loop).
-    if (nt == 256) {
+    if (nvl == 256) {  // (128 lanes in the place of 256: the same blocks and tiles, the tiles dealt over two waves)
         typedef double v4d_t __attribute__((ext_vector_type(4)));
-        const int lane = tid & 63, wave = tid >> 6, li = lane & 15, kq = lane >> 4;
+        const int lane = tid & 63, wave = tid >> 6, n_wave = nt >> 6, li = lane & 15, kq = lane >> 4;
         double* invd = y;  // (y is free until the factorisation is over)
         if (tid == 0) *flag = 0;
         KBA_SYNC();
@@ -1911,7 +1955,7 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
                 int t = 0;
                 for (int ti = 0; ti < Ti; ++ti)
                     for (int tj = ti; tj < Tj; ++tj, ++t) {
-                        if ((t & 3) != wave) continue;
+                        if ((t & (n_wave - 1)) != wave) continue;  // (n_wave is 4 or 2; a tile does not depend on which wave runs it)
                         const int i_op = kbe + 16 * ti + li, j_op = kbe + 16 * tj + li;
                         const double wv = kin && i_op < nf ? -(A[kp * lda + i_op] * ivd) : 0.0;
                         const double pv = kin && j_op <= nf ? A[kp * lda + j_op] : 0.0;
@@ -2013,18 +2057,30 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     // camera part of the model cost change: -g_c.d - 1/2 d^T H_cc d (unscaled) = g'.y - 1/2 y^T H' y in the scaled variables of the
     // solve (d = -S_c y, g' = S_c g_c, H' = S_c H_cc S_c), from the entries the assembly kept in LDS (Hs): every lane takes the
     // entries it assembled.  (Rounds 2-5 read the nc columns of H_cc from memory again here: ten dependent round trips per lane.)
-    double part = 0.0;
-    for (int i = tid; i < n_need; i += nt) {
+    // (virtual lanes: lane tid forms the sums of the virtual lanes tid and, _o, tid + nt, each over its own entries vt, vt + nvl, ...)
+    double part = 0.0, part_o = 0.0;
+    for (int i = tid; i < n_need; i += nvl) {
         int ca, cb;
         schur_need_decode(i, nf, ca, cb);
         if (cb < nf)
-            part -= (ca == cb ? 0.5 : 1.0) * (Hs[i] * y[ca] * y[cb]);
+            part -= (ca == cb ? 0.5 : 1.0) * (hs_at(ca, cb) * y[ca] * y[cb]);
         else
-            part += Hs[i] * y[ca];
+            part += hs_at(ca, cb) * y[ca];
+    }
+    for (int i = tid + nt; vrep == 2 && i < n_need; i += nvl) {
+        int ca, cb;
+        schur_need_decode(i, nf, ca, cb);
+        if (cb < nf)
+            part_o -= (ca == cb ? 0.5 : 1.0) * (hs_at(ca, cb) * y[ca] * y[cb]);
+        else
+            part_o += hs_at(ca, cb) * y[ca];
     }
     KBA_TICK(14);
     const uint8_t* cm = bv.cmask + (int64_t)wd.cam0;
+    // (virtual lanes stand in only where n_kf <= nc <= nt - slots_once, kba_batch_plan.hpp:plan_cam_lanes - so a lane has at most one
+    // keyframe, its virtual lane tid's own; the virtual lane tid + nt has none: zeros)
     double step2 = 0.0, cand2 = 0.0;
+    const double step2_o = 0.0, cand2_o = 0.0;
     for (int k = tid; k < wd.n_kf; k += nt) {
         const int gk = wd.kf0 + k;
         const double* d = dl + k * kCamSlots;
@@ -2097,9 +2153,9 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
         }
     }
     KBA_TICK(12);
-    // three sums at once (red holds 3*nt doubles)
-    double v3[3] = {part, step2, cand2};
-    coop_reduce<3, 3>(v3, tid, nt, red);
+    // three sums at once (red holds 3 * nvl doubles on the host, three per virtual wave on the device)
+    double v3[2 * 3] = {part, step2, cand2, part_o, step2_o, cand2_o};
+    coop_reduce<3, 3>(v3, tid, nt, red, vrep);
     if (tid == 0) {
         WinRed& r = bv.red[w];
         r.chol_fail = 0;

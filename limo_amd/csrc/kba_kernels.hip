@@ -1338,7 +1338,14 @@ __global__ __launch_bounds__(64) void k_schur_lean_pair(BatchView bv, const int3
 
 // ------------------------------------------------------------------------------------------ camera system
 // (three waves per SIMD = three windows per CU; without the attribute 172 registers, two waves; four spill: profiles/r06_experiment_launch_train.txt)
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_cam_assemble(BatchView bv, SolveConsts c, const int32_t* wl) {
+// NT lanes per window: kBlock, or kCamLanesHalf = kBlock / 2 lanes that stand in for kBlock (cam_assemble's virtual lanes: the same bits
+// for every window).  A workgroup keeps its registers for the whole dependent chain of its window while one wave or a few dozen lanes
+// work for most of it; half the lanes at the same three waves per SIMD are twice the windows per CU.  The host picks the instance
+// per launch (kba_batch_plan.hpp:cam_lanes_for_launch).
+template <int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_cam_assemble(BatchView bv, SolveConsts c, const int32_t* wl) {
+    // (the full workgroup keeps its lane count a run-time value, as every round before had it: its code is the code that was measured)
+    const int nt = NT == kBlock ? (int)blockDim.x : NT, nvl = NT == kBlock ? 0 : kBlock;
     const int w = wl_at(bv, wl, blockIdx.x);
     if (w < 0) return;
     WinState& st = bv.st[w];
@@ -1348,9 +1355,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) 
         // scratch accesses of the common case must stay LDS instructions (a pointer that may be either makes them flat)
         const int64_t so = bv.win[w].cam_scr_off;
         if (so >= 0)
-            cam_assemble(bv, c, w, threadIdx.x, blockDim.x, bv.cam_scratch + so);
+            cam_assemble(bv, c, w, threadIdx.x, nt, bv.cam_scratch + so, nvl);
         else
-            cam_assemble(bv, c, w, threadIdx.x, blockDim.x, smem);
+            cam_assemble(bv, c, w, threadIdx.x, nt, smem, nvl);
         __syncthreads();
 #ifdef KBA_PROFILE_TICKS
         if (w == 0 && threadIdx.x == 0)
@@ -1380,7 +1387,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3, 3))) 
 }
 
 // (no occupancy attribute: with one the compiler's schedule is 27 % slower, profiles/r05_experiment_cam_solve_occupancy.txt)
-__global__ __launch_bounds__(kBlock) void k_cam_solve(BatchView bv, SolveConsts c, const int32_t* wl) {
+// NT: see k_cam_assemble
+template <int NT>
+__global__ __launch_bounds__(NT) void k_cam_solve(BatchView bv, SolveConsts c, const int32_t* wl) {
+    const int nt = NT == kBlock ? (int)blockDim.x : NT, nvl = NT == kBlock ? 0 : kBlock;
     const int w = wl_at(bv, wl, blockIdx.x);
     if (w < 0) return;
     if (!bv.st[w].active) return;
@@ -1388,9 +1398,9 @@ __global__ __launch_bounds__(kBlock) void k_cam_solve(BatchView bv, SolveConsts 
     __shared__ int flag;
     const int64_t so = bv.win[w].cam_scr_off;  // (two calls: see k_cam_assemble)
     if (so >= 0)
-        cam_solve(bv, c, w, threadIdx.x, blockDim.x, bv.cam_scratch + so, &flag);
+        cam_solve(bv, c, w, threadIdx.x, nt, bv.cam_scratch + so, &flag, nvl);
     else
-        cam_solve(bv, c, w, threadIdx.x, blockDim.x, smem, &flag);
+        cam_solve(bv, c, w, threadIdx.x, nt, smem, &flag, nvl);
 #ifdef KBA_PROFILE_TICKS
     __syncthreads();
     if (w == 0 && threadIdx.x == 0)

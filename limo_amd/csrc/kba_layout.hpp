@@ -25,6 +25,7 @@ constexpr int kViewLin = 64;      // doubles per view in BatchView::view_lin (kb
 constexpr int kCamSlots = 10;     // tangent dims per keyframe in the reduced camera system
 constexpr int kMaxNc = kMaxKf * kCamSlots;
 constexpr int kBlock = 256;       // lanes per workgroup in the scan kernels
+constexpr int kCamLanesHalf = kBlock / 2;  // lanes of the half form of k_cam_assemble / k_cam_solve (same bits as kBlock lanes)
 constexpr int kObsPerLane = 4;    // observations per lane of the view-major kernels: the camera-side partials are
                                   // accumulated in registers over them before the one workgroup reduction
 constexpr int kObsBlock = kBlock * kObsPerLane;  // observations per linearize / cost workgroup

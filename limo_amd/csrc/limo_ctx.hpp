@@ -56,6 +56,7 @@ struct limo_ctx {
     int coop_benched = 0;                   // solves kept off it since; the kCoopRetryAfter-th tries again (kba_batch_plan.hpp:choose_solve_path)
     long long last_solve_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // limo_ctx_last_solve_info: which path the last limo_ba_batch_solve took
     long long last_schur_gp_info[4] = {0, 0, 0, 0};           // limo_ctx_last_schur_gp_info: ... and which ground-plane Schur waves it ran
+    long long last_cam_lanes_info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // limo_ctx_last_cam_lanes_info: ... and which form its camera launches took
     // iteration log (limo_ctx_set_iteration_log): the switch limo_ba_batch_solve reads, and the logs of the windows of the last call
     // that made and destroyed its own batch (limo_ctx_last_iteration_log): window w has last_log_n[w] entries from last_log_off[w]
     bool iteration_log = false;

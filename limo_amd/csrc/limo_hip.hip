@@ -125,6 +125,11 @@ struct limo_ba_batch : Executor {
     int64_t n_rounds = 0, n_pair_launches = 0;
     int64_t n_narrow_launches = 0, n_widegp_launches = 0;  // launches that ran narrow / three-panel ground-plane waves (limo_ctx_last_schur_gp_info)
     int lin_variant = 1;  // k_lin_lm<true> / <false> of the last launch; the one-launch kernels always linearise through LDS
+    // lanes of the camera kernels (kba_batch_plan.hpp:plan_cam_lanes / cam_lanes_for_launch; limo_ctx_last_cam_lanes_info)
+    CamOccupancy cam_occ;
+    CamLanesPlan cam_plan;
+    int cam_lanes_forced = 0;              // SolveSwitches::cam_lanes of the solve in progress
+    int64_t n_cam_launches[2][2] = {{0, 0}, {0, 0}};  // [assemble, solve][half, full] launches of the solve in progress
 
     ~limo_ba_batch() override {
         // (the arrays of P that live in the context's pinned pack arena are not freed one by one - kba_pack.hpp:PackArena -, the arena
@@ -348,8 +353,18 @@ struct limo_ba_batch : Executor {
             schur_fn_gen = schur_kernel(2, plan.wide_npw, 0);
             HIP_TRY(ctx, hipFuncSetAttribute(schur_fn_gen, hipFuncAttributeMaxDynamicSharedMemorySize, plan.wide_lds));
         }
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, plan.asm_bytes));
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_solve, hipFuncAttributeMaxDynamicSharedMemorySize, plan.solve_bytes));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_assemble<kBlock>, hipFuncAttributeMaxDynamicSharedMemorySize, plan.asm_bytes));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_solve<kBlock>, hipFuncAttributeMaxDynamicSharedMemorySize, plan.solve_bytes));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_assemble<kCamLanesHalf>, hipFuncAttributeMaxDynamicSharedMemorySize, plan.asm_bytes));
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_solve<kCamLanesHalf>, hipFuncAttributeMaxDynamicSharedMemorySize, plan.solve_bytes));
+        {   // which form of the two the batch may take (kba_batch_plan.hpp:plan_cam_lanes): workgroups per CU of the four instances
+            HIP_TRY(ctx, hipDeviceGetAttribute(&cam_occ.n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cam_occ.asm_full, k_cam_assemble<kBlock>, kBlock, plan.asm_bytes));
+            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cam_occ.asm_half, k_cam_assemble<kCamLanesHalf>, kCamLanesHalf, plan.asm_bytes));
+            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cam_occ.solve_full, k_cam_solve<kBlock>, kBlock, plan.solve_bytes));
+            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&cam_occ.solve_half, k_cam_solve<kCamLanesHalf>, kCamLanesHalf, plan.solve_bytes));
+            cam_plan = plan_cam_lanes(P, cam_occ, shard_P == 1 && !pose_batch);
+        }
         HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_trim_select, hipFuncAttributeMaxDynamicSharedMemorySize, plan.trim_bytes));
         for (auto& e : act_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         HIP_TRY(ctx, hipEventCreate(&ev_total_a));
@@ -759,10 +774,23 @@ struct limo_ba_batch : Executor {
     // worklist, grid and stream are the caller's - the lock-step solve (linearize / assemble / step / trim) and the rounds of the
     // streaming solve (enqueue_round).  A grid of 0 launches nothing.
     void launch_cam_assemble(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
-        if (grid) hipLaunchKernelGGL(k_cam_assemble, dim3(grid), dim3(kBlock), plan.asm_bytes, s, v, c, list);
+        if (!grid) return;
+        // (grid: the windows the launch can list - the same bits from either form, so the form is this launch's own choice)
+        const bool half = cam_lanes_for_launch(cam_plan.asm_half_ok, cam_plan.asm_resident, grid, cam_lanes_forced) == kCamLanesHalf;
+        if (half)
+            hipLaunchKernelGGL(k_cam_assemble<kCamLanesHalf>, dim3(grid), dim3(kCamLanesHalf), plan.asm_bytes, s, v, c, list);
+        else
+            hipLaunchKernelGGL(k_cam_assemble<kBlock>, dim3(grid), dim3(kBlock), plan.asm_bytes, s, v, c, list);
+        ++n_cam_launches[0][half ? 0 : 1];
     }
     void launch_cam_solve(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
-        if (grid) hipLaunchKernelGGL(k_cam_solve, dim3(grid), dim3(kBlock), plan.solve_bytes, s, v, c, list);
+        if (!grid) return;
+        const bool half = cam_lanes_for_launch(cam_plan.solve_half_ok, cam_plan.solve_resident, grid, cam_lanes_forced) == kCamLanesHalf;
+        if (half)
+            hipLaunchKernelGGL(k_cam_solve<kCamLanesHalf>, dim3(grid), dim3(kCamLanesHalf), plan.solve_bytes, s, v, c, list);
+        else
+            hipLaunchKernelGGL(k_cam_solve<kBlock>, dim3(grid), dim3(kBlock), plan.solve_bytes, s, v, c, list);
+        ++n_cam_launches[1][half ? 0 : 1];
     }
     void launch_backsub(const BatchView& v, const int32_t* list, int grid, hipStream_t s) {
         if (grid) hipLaunchKernelGGL(k_backsub, dim3(grid), dim3(kBlock), 0, s, v, c, list);
@@ -1355,6 +1383,8 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     if (ch.benched) ++ctx->coop_benched;
     b->n_rounds = b->n_pair_launches = b->n_narrow_launches = b->n_widegp_launches = 0;
     b->gp_wide = sw.gp_wide;
+    b->cam_lanes_forced = sw.cam_lanes;
+    b->n_cam_launches[0][0] = b->n_cam_launches[0][1] = b->n_cam_launches[1][0] = b->n_cam_launches[1][1] = 0;
     b->lin_variant = 1;
     long long* info = ctx->last_solve_info;
     std::fill(info, info + 8, 0ll);
@@ -1425,6 +1455,19 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     ctx->last_schur_gp_info[1] = b->P.n_sgrp_wide;
     ctx->last_schur_gp_info[2] = b->n_narrow_launches;
     ctx->last_schur_gp_info[3] = b->n_widegp_launches;
+    {
+        long long* ci = ctx->last_cam_lanes_info;
+        ci[0] = b->n_cam_launches[0][0];
+        ci[1] = b->n_cam_launches[0][1];
+        ci[2] = b->n_cam_launches[1][0];
+        ci[3] = b->n_cam_launches[1][1];
+        ci[4] = b->cam_occ.asm_half;
+        ci[5] = b->cam_occ.asm_full;
+        ci[6] = b->cam_occ.solve_half;
+        ci[7] = b->cam_occ.solve_full;
+        ci[8] = 0;
+        for (const WinDesc& d : b->P.win) ci[8] += d.cam_scr_off >= 0 ? 1 : 0;
+    }
     HIP_TRY(ctx, hipEventRecord(b->ev_total_b, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
@@ -1713,6 +1756,12 @@ int limo_ctx_exchange_stats(limo_ctx* ctx, int64_t* stats3) {
 int limo_ctx_last_solve_info(const limo_ctx* ctx, int64_t info[8]) {
     if (!ctx || !info) return LIMO_ERR_INVALID;
     for (int i = 0; i < 8; ++i) info[i] = ctx->last_solve_info[i];
+    return LIMO_OK;
+}
+
+int limo_ctx_last_cam_lanes_info(const limo_ctx* ctx, int64_t info[9]) {
+    if (!ctx || !info) return LIMO_ERR_INVALID;
+    for (int i = 0; i < 9; ++i) info[i] = ctx->last_cam_lanes_info[i];
     return LIMO_OK;
 }
 

@@ -11,8 +11,9 @@ git archive "$rev" limo_amd/csrc include | tar -x -C "$tmp"
 mkdir -p limo_amd/lib/variants "$tmp/obj"
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -w"
 pids=()
-for src in limo_hip.hip kba_pack.cpp host_misc.cpp depth.hip landmark_init.hip; do
-  extra=""; case $src in depth.hip|landmark_init.hip) extra="-ffp-contract=off";; esac
+for src in limo_hip.hip kba_pack.cpp host_misc.cpp depth.hip landmark_init.hip five_point.hip landmark_select.hip; do
+  [ -f "$tmp/limo_amd/csrc/$src" ] || continue  # (a revision from before the source existed)
+  extra=""; case $src in depth.hip|landmark_init.hip|five_point.hip|landmark_select.hip) extra="-ffp-contract=off";; esac
   ( cd "$tmp/limo_amd/csrc" && hipcc $flags $extra -c -o "$tmp/obj/$src.o" $src ) &
   pids+=($!)
 done
