@@ -2,7 +2,7 @@
 // how much dynamic LDS every kernel of the solve gets (BatchPlan), and the Schur worklists (build_sblk_list).  Once per SOLVE: which
 // launch path it takes (choose_solve_path, from the KBA_* switches of SolveSwitches) and the slot geometry of a streaming solve
 // (stream_geometry).  Host-only and free of the HIP runtime, so that the decisions are testable without a device
-// (tests/cpp/test_batch_plan.cpp); limo_hip.hip turns the integers into kernel pointers and launches.
+// (tests/cpp/test_batch_plan.cpp); limo_batch.hpp turns the integers into kernel pointers and launches.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -171,7 +171,7 @@ inline SolveSwitches read_solve_switches() {
 // (kba_items.hpp:cam_assemble, virtual lanes), so the choice is free per launch.  Half the lanes hold half the registers for the
 // length of a window's dependent chain: twice the windows per CU, each somewhat slower.  That pays where a launch is bound by its
 // passes over the device (windows / resident windows), not by one chain.
-struct CamOccupancy {  // from the HIP runtime (limo_hip.hip): workgroups per CU at the plan's LDS sizes, compute units of the device
+struct CamOccupancy {  // from the HIP runtime (limo_batch.hpp:upload): workgroups per CU at the plan's LDS sizes, compute units of the device
     int n_cu = 0;
     int asm_full = 0, asm_half = 0, solve_full = 0, solve_half = 0;
 };

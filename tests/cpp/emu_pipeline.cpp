@@ -220,7 +220,7 @@ struct EmuBatch : Executor {
     }
 
     void expire(int) override {
-        if (assemble_pending) {  // (as limo_hip.hip: the deferred camera assembly of the last linearisation)
+        if (assemble_pending) {  // (as limo_batch_lockstep.hpp: the deferred camera assembly of the last linearisation)
             assemble_pending = false;
             exchange(1);
             assemble();
@@ -399,7 +399,7 @@ struct EmuBatch : Executor {
         }
     }
 
-    // ---- streaming solve (mirrors k_sched + the list-driven launches of limo_hip.hip:solve_streaming)
+    // ---- streaming solve (mirrors k_sched + the list-driven launches of limo_batch_stream.hpp:StreamSolve::solve)
     // Trimming of ONE window (the lock-step trim() above handles every do_trim window at once); unsharded only.
     void trim_window(int w) {
         const WinDesc& wd = bv.win[w];
