@@ -6,6 +6,8 @@
 // wiring, :704-736 scale / ground-plane regularisation and constness rules, :740-758 trimming schedule) and the
 // outer loop of robust_optimization::solveTrimmed (robust_optimization/src/robust_solving.cpp:140-248).
 #pragma once
+#include <array>
+#include <functional>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -117,7 +119,7 @@ struct PackOptions {
     bool pose_only = false;
     bool evaluate_only = false;  // no problem-build logic (no ground plane / regularisers), every parameter free
     const limo_speed_prior* prior = nullptr;
-    int shards = 1;  // > 1: lay the batch out for landmark sharding (no workgroup straddles two shards)
+    int shards = 1;  // > 1: lay the batch out for landmark sharding (no workgroup straddles two shards); refused with evaluate_only
     // A batch of adjustPoseOnly problems (limo_ba_batch_create_pose_only): window w takes window_priors[w] (null: no window has a
     // prior; an entry with speed_weight <= 0: that window has none) instead of `prior`, and an invalid window is named by its index
     // in the error text.
@@ -132,6 +134,43 @@ struct PackOptions {
     // where a kernel at create forms the planes from lm_slot and obs_u / obs_v / obs_d, which are on the device anyway.
     bool host_pair_planes = true;
 };
+
+// THE PROBLEM'S RULES: which residual and parameter blocks one window has - the reference's problem-build logic of
+// BundleAdjusterKeyframes::solve() / adjustPoseOnly(), decided from the caller's window and the mode alone.
+// Everything here is in the CALLER's indices (keyframe, landmark, observation, camera as the window numbers them); nothing knows of
+// the batch or of a packed index.  pack_windows lays out what this says exists.
+struct WindowProblem {
+    int rc = LIMO_OK;           // validation: LIMO_OK, or the window is refused with err (a literal) and nothing below is meaningful
+    const char* err = nullptr;
+    struct View {
+        int kf, cam;
+    };
+    std::vector<View> views;    // the (keyframe, camera) pairs that carry observations, in pack order (build_window_problem)
+    std::vector<int> obs_view;  // [n_obs] the view of every observation (index into views)
+    struct GpRow {
+        int kf, lm;
+        double w;
+    };
+    std::vector<GpRow> gp;          // ground-plane rows, in landmark order
+    std::vector<uint8_t> lm_state;  // [n_lm] 0: not in the problem, 1: variable, 2: constant parameter block
+    std::vector<uint8_t> lm_const;  // [n_lm] flagged in PackOptions::lm_fixed (whatever its state); n_const of them
+    int n_const = 0;
+    std::array<uint8_t, kMaxKf * kCamSlots> present{}, free{};  // [n_kf * kCamSlots] the camera slot's parameter exists / is variable
+    bool has_scale_reg = false;     // PoseRegularization between the first two poses: weight and target
+    double scale_w = 0.0, scale_s0 = 0.0;
+    bool has_gp_reg = false;        // the ground-plane regularisers
+    int n_depth = 0, n_repr = 0;    // residual blocks built: observations with a depth, all observations
+    bool do_trim = false;           // the trimmed schedule applies (n_lm > min_landmarks_for_trimming)
+    double speed_w = 0.0, speed_dt = 0.0, speed_vel[3] = {0, 0, 0}, speed_Rb[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0},
+           speed_tb[3] = {0, 0, 0};  // SpeedRegularizationVector2 of a pose-only window; speed_w == 0: none
+};
+// w: the window's index in the batch - it selects the window's entry of PackOptions::window_priors / lm_fixed, nothing else.
+WindowProblem build_window_problem(const limo_ba_window& W, const limo_ba_options& opts, const PackOptions& po, int w);
+
+// Runs f(0 .. n - 1) on host threads, the caller among them: min(hardware threads, max_threads) of them - KBA_PACK_THREADS, read
+// here and nowhere else, overrides the count - handing out `grain` consecutive items at a time; one thread or none: a plain loop.
+// The threads are the pack's pool (kba_pack.cpp:PackPool), or fresh ones while another caller holds it.
+void pack_parallel_for(int n, unsigned max_threads, int grain, const std::function<void(int)>& f);
 
 // Returns LIMO_OK or a negative limo_status; err receives a message.
 int pack_windows(int32_t n, const limo_ba_window* windows, const limo_ba_options& opts, const PackOptions& po,

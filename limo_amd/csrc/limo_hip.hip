@@ -326,20 +326,7 @@ int limo_ba_batch_download(limo_ba_batch* b, limo_ba_window* windows_out, limo_b
             r.time_sec = b->timers.last_solve_sec;
         }
     };
-    unsigned nt = std::min({std::thread::hardware_concurrency(), 32u, (unsigned)(P.n_win / 32)});
-    if (const char* e = std::getenv("KBA_PACK_THREADS")) nt = (unsigned)std::max(1, std::atoi(e));
-    if (nt <= 1) {
-        for (int w = 0; w < P.n_win; ++w) one_window(w);
-    } else {
-        std::atomic<int> next{0};
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < nt; ++t)
-            pool.emplace_back([&] {
-                for (int w0 = next.fetch_add(8); w0 < P.n_win; w0 = next.fetch_add(8))
-                    for (int w = w0; w < std::min(w0 + 8, (int)P.n_win); ++w) one_window(w);
-            });
-        for (auto& th : pool) th.join();
-    }
+    pack_parallel_for(P.n_win, std::min(32u, (unsigned)(P.n_win / 32)), 8, one_window);
     return LIMO_OK;
 }
 
