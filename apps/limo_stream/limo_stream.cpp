@@ -8,7 +8,15 @@
 //   limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--poses out.txt] [--gt-poses gt.txt]
 //               [--dump-velodyne DIR] [--velodyne DIR] [--no-depth] [--depth-ahead thread|stream|none] [--quiet]
 //               [--depth-params FILE] [--progress] [--five-point-prior [--five-point-host | --five-point-device]]
-//               [--select-host | --select-device] [--sequences N [--frames-step K] [--stagger S] [--host-threads T]]
+//               [--select-host | --select-device] [--depth-thres A] [--reprojection-thres A] [--outlier-quantile Q] [--shrubbery-weight W]
+//               [--sequences N [--frames-step K] [--stagger S] [--host-threads T] [--sweep FILE]]
+// --depth-thres / --reprojection-thres / --outlier-quantile / --shrubbery-weight set the outlier rejection of solve() and adjustPoseOnly()
+// (the node's robust_loss_depth_thres, robust_loss_reprojection_thres, outlier_rejection_quantile, shrubbery_weight) for a single drive
+// and for every sequence of a lock-step one.  --sweep FILE (with --sequences N) gives sequence i the parameters of line i of FILE:
+// key=value tokens with the keys depth_thres, reprojection_thres, outlier_quantile, shrubbery_weight, window; a missing key takes the
+// command line's value.  Every sequence of a sweep drives the SAME world - seed --seed for all, not seed + i - so the per-sequence part of
+// the JSON line, which echoes each sequence's parameters next to its ATE, is the sweep's result (the reference's
+// tune_parameters_kitti.py, side by side on one GPU).
 // --sequences N drives N sequences in lock step through ONE LockstepDriver (limo_amd/kba/lockstep_driver.hpp: one batched device call
 // per stage and tick for all of them) instead of one StreamDriver: sequence i is the synthetic drive of --seed (seed + i), runs
 // frames - i*K frames (--frames-step K) and gets its first frame at tick i*S (--stagger S); --host-threads T sets the threads of the
@@ -42,6 +50,7 @@
 #include <map>
 #include <memory>
 #include <optional>
+#include <sstream>
 #include <string>
 
 #include "../../limo_amd/kba/depth_params_yaml.hpp"
@@ -147,22 +156,67 @@ struct Synth {
 // gets its first frame at tick i * stagger; every tick hands the driver the frames that are due.  The input of a tick is synthesised
 // before the tick and timed apart from it, as in the single drive.
 struct LockstepOptions {
-    int sequences = 0, frames_step = 0, stagger = 0, host_threads = 0, perturb_rig = -1;
+    int sequences = 0, frames_step = 0, stagger = 0, host_threads = 0, perturb_rig = -1, perturb_trim_rounds = -1;
     int n_frames = 200, n_feat = 1500, n_az = 2000;
     uint64_t seed = 7;
-    std::string poses_path, gt_path, depth_params_path;
+    std::string poses_path, gt_path, depth_params_path, sweep_path;
     bool quiet = false;
 };
+
+// --sweep FILE: line i gives sequence i's parameters as key=value tokens - depth_thres, reprojection_thres, outlier_quantile,
+// shrubbery_weight, window; a key a line does not set keeps the command line's value (`base`).  false: err says why.
+bool read_sweep(const std::string& path, int n, const StreamParams& base, std::vector<StreamParams>& out, std::string& err) {
+    std::ifstream f(path);
+    if (!f) {
+        err = "cannot read " + path;
+        return false;
+    }
+    out.clear();
+    std::string line;
+    while (std::getline(f, line)) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        StreamParams p = base;
+        std::istringstream tokens(line);
+        std::string tok;
+        while (tokens >> tok) {
+            const size_t eq = tok.find('=');
+            const std::string key = tok.substr(0, eq), val = eq == std::string::npos ? "" : tok.substr(eq + 1);
+            char* end = nullptr;
+            const double v = std::strtod(val.c_str(), &end);
+            if (val.empty() || *end) {
+                err = "line " + std::to_string(out.size() + 1) + ": `" + tok + "` is not key=number";
+                return false;
+            }
+            if (key == "depth_thres") p.robust_loss_depth_thres = v;
+            else if (key == "reprojection_thres") p.robust_loss_reprojection_thres = v;
+            else if (key == "outlier_quantile") p.outlier_rejection_quantile = v;
+            else if (key == "shrubbery_weight") p.shrubbery_weight = v;
+            else if (key == "window") p.max_size_optimization_window = (int)v;
+            else {
+                err = "line " + std::to_string(out.size() + 1) + ": unknown key `" + key + "` (depth_thres, reprojection_thres, outlier_quantile, shrubbery_weight, window)";
+                return false;
+            }
+        }
+        out.push_back(p);
+    }
+    if ((int)out.size() != n) {
+        err = std::to_string(out.size()) + " lines for " + std::to_string(n) + " sequences";
+        return false;
+    }
+    return true;
+}
 
 int run_lockstep(const LockstepOptions& o, StreamParams sp) {
     using clk = std::chrono::steady_clock;
     const int N = o.sequences;
+    const bool sweep = !o.sweep_path.empty();  // every sequence drives the SAME world (the seed), with a parameter set of its own
     struct Drive {
         std::unique_ptr<synth_world::World> world;
         std::unique_ptr<Synth> synth;
         Camera::Ptr cam;
         Frame frame;
         int n_frames = 0, first_tick = 0;
+        uint64_t seed = 0;
     };
     std::vector<Drive> drives(N);
     std::vector<LockstepDriver::Rig> rigs;
@@ -175,9 +229,10 @@ int run_lockstep(const LockstepOptions& o, StreamParams sp) {
             std::fprintf(stderr, "limo_stream: --frames-step leaves sequence %d without a frame\n", i);
             return 2;
         }
-        d.world = std::make_unique<synth_world::World>(d.n_frames, o.seed + (uint64_t)i);
+        d.seed = sweep ? o.seed : o.seed + (uint64_t)i;
+        d.world = std::make_unique<synth_world::World>(d.n_frames, d.seed);
         d.world->n_az = o.n_az;
-        d.synth = std::make_unique<Synth>(*d.world, o.seed + (uint64_t)i, o.n_feat, std::string(), std::string());
+        d.synth = std::make_unique<Synth>(*d.world, d.seed, o.n_feat, std::string(), std::string());
         // --perturb-rig I (testing aid): sequence I comes with another focal length - the driver must refuse it
         d.cam = std::make_shared<Camera>(d.world->f + (i == o.perturb_rig ? 1. : 0.), Vector2d(d.world->cx, d.world->cy), d.world->cam_veh);
         rigs.push_back({d.cam, d.world->cam_lidar});
@@ -186,9 +241,19 @@ int run_lockstep(const LockstepOptions& o, StreamParams sp) {
     }
     sp.image_width = (int)drives[0].world->W;
     sp.image_height = (int)drives[0].world->H;
+    std::vector<StreamParams> sps(N, sp);
+    if (sweep) {
+        std::string err;
+        if (!read_sweep(o.sweep_path, N, sp, sps, err)) {
+            std::fprintf(stderr, "limo_stream: --sweep: %s\n", err.c_str());
+            return 2;
+        }
+    }
+    // --perturb-trim-rounds I (testing aid): sequence I comes with another number of trimming rounds - the driver must refuse it
+    if (o.perturb_trim_rounds >= 0 && o.perturb_trim_rounds < N) sps[o.perturb_trim_rounds].outlier_rejection_num_iterations += 1;
     std::unique_ptr<LockstepDriver> driver;
     try {
-        driver = std::make_unique<LockstepDriver>(sp, rigs, o.host_threads);
+        driver = std::make_unique<LockstepDriver>(sps, rigs, o.host_threads);
     } catch (const std::invalid_argument& e) {
         std::fprintf(stderr, "limo_stream: %s\n", e.what());
         return 2;
@@ -256,19 +321,22 @@ int run_lockstep(const LockstepOptions& o, StreamParams sp) {
         }
         const StreamDriver::Stats& ss = driver->sequenceStats(i);
         std::printf("limo_stream: sequence %d (seed %llu, first tick %d): %d frames, %d keyframes, %d solves, %d landmark selections on the device, ATE rmse %.4f m (max %.4f m)\n", i,
-                    (unsigned long long)(o.seed + (uint64_t)i), d.first_tick, ss.frames, ss.keyframes, ss.solves, driver->adjuster(i).device_selections_, ate, worst);
-        char buf[512];
+                    (unsigned long long)d.seed, d.first_tick, ss.frames, ss.keyframes, ss.solves, driver->adjuster(i).device_selections_, ate, worst);
+        char buf[768];
+        // (the sequence's parameters next to its ATE: the table a sweep is run for)
         std::snprintf(buf, sizeof(buf),
                       "%s{\"seed\": %llu, \"first_tick\": %d, \"frames\": %d, \"keyframes\": %d, \"solves\": %d, \"five_point_calls\": %d, \"five_point_device_calls\": %d, "
-                      "\"select_device_calls\": %d, \"ate_rmse\": %.6f, \"ate_max\": %.6f}",
-                      i ? ", " : "", (unsigned long long)(o.seed + (uint64_t)i), d.first_tick, ss.frames, ss.keyframes, ss.solves, ss.five_point_calls, ss.five_point_device_calls,
-                      driver->adjuster(i).device_selections_, ate, worst);
+                      "\"select_device_calls\": %d, \"depth_thres\": %.17g, \"reprojection_thres\": %.17g, \"outlier_quantile\": %.17g, \"shrubbery_weight\": %.17g, "
+                      "\"window\": %d, \"ate_rmse\": %.6f, \"ate_max\": %.6f}",
+                      i ? ", " : "", (unsigned long long)d.seed, d.first_tick, ss.frames, ss.keyframes, ss.solves, ss.five_point_calls, ss.five_point_device_calls,
+                      driver->adjuster(i).device_selections_, sps[i].robust_loss_depth_thres, sps[i].robust_loss_reprojection_thres, sps[i].outlier_rejection_quantile,
+                      sps[i].shrubbery_weight, sps[i].max_size_optimization_window, ate, worst);
         per_sequence += buf;
     }
     auto stage = [](const char* name, const LockstepDriver::Stage& s, bool last = false) {
         char buf[384];
-        std::snprintf(buf, sizeof(buf), "\"%s\": {\"batched_calls\": %ld, \"items\": %ld, \"max_items\": %d, \"fallback_calls\": %ld, \"ms_host\": %.3f, \"ms_abi\": %.3f}%s", name,
-                      s.batched_calls, s.items, s.max_items, s.fallback_calls, 1e3 * s.sec_host, 1e3 * s.sec_abi, last ? "" : ", ");
+        std::snprintf(buf, sizeof(buf), "\"%s\": {\"batched_calls\": %ld, \"items\": %ld, \"max_items\": %d, \"fallback_calls\": %ld, \"per_window_calls\": %ld, \"ms_host\": %.3f, \"ms_abi\": %.3f}%s",
+                      name, s.batched_calls, s.items, s.max_items, s.fallback_calls, s.per_window_calls, 1e3 * s.sec_host, 1e3 * s.sec_abi, last ? "" : ", ");
         return std::string(buf);
     };
     std::printf("limo_stream: %d sequences in lock step on %d host threads: %d frames in %d ticks, %.2f ms per tick -> %.1f frames/s over all sequences; input synthesis %.1f ms per tick\n", N,
@@ -295,6 +363,7 @@ int main(int argc, char** argv) {
     int select_where = -1;      // landmark selection of solve(): the same
     StreamParams::DepthAhead depth_ahead = StreamParams::DepthAhead::Thread;
     double min_flow = -1., time_between_keyframes = -1.;
+    double depth_thres = -1., reprojection_thres = -1., outlier_quantile = -1., shrubbery_weight = -1.;  // (< 0: StreamParams' default)
     LockstepOptions lockstep;
     bool single_only = false;  // an option the lock-step drive does not have
     for (int i = 1; i < argc; ++i) {
@@ -310,6 +379,12 @@ int main(int argc, char** argv) {
         else if (arg("--host-threads")) lockstep.host_threads = std::atoi(argv[++i]);
         else if (arg("--perturb-rig")) lockstep.perturb_rig = std::atoi(argv[++i]);  // (testing aid, see run_lockstep)
         else if (arg("--misannounce-every")) misannounce_every = std::atoi(argv[++i]), single_only = true;  // (testing aid, see the frame loop)
+        else if (arg("--perturb-trim-rounds")) lockstep.perturb_trim_rounds = std::atoi(argv[++i]);  // (testing aid, see run_lockstep)
+        else if (arg("--sweep")) lockstep.sweep_path = argv[++i];
+        else if (arg("--depth-thres")) depth_thres = std::atof(argv[++i]);
+        else if (arg("--reprojection-thres")) reprojection_thres = std::atof(argv[++i]);
+        else if (arg("--outlier-quantile")) outlier_quantile = std::atof(argv[++i]);
+        else if (arg("--shrubbery-weight")) shrubbery_weight = std::atof(argv[++i]);
         else if (arg("--min-flow")) min_flow = std::atof(argv[++i]);
         else if (arg("--time-between-keyframes")) time_between_keyframes = std::atof(argv[++i]);
         else if (arg("--poses")) poses_path = argv[++i];
@@ -335,14 +410,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--select-host")) select_where = 0;
         else if (!std::strcmp(argv[i], "--select-device")) select_where = 1;
         else {
-            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--five-point-host] [--five-point-device] [--select-host] [--select-device] [--quiet] [--progress] [--sequences N [--frames-step K] [--stagger S] [--host-threads T]]\n");
+            std::fprintf(stderr, "usage: limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--min-flow px] [--time-between-keyframes sec] [--poses file] [--gt-poses file] [--dump-velodyne dir] [--velodyne dir] [--no-depth] [--depth-ahead thread|stream|none] [--depth-params file] [--five-point-prior] [--five-point-host] [--five-point-device] [--select-host] [--select-device] [--depth-thres a] [--reprojection-thres a] [--outlier-quantile q] [--shrubbery-weight w] [--quiet] [--progress] [--sequences N [--frames-step K] [--stagger S] [--host-threads T] [--sweep file]]\n");
             return 2;
         }
     }
     using clk = std::chrono::steady_clock;
-    const bool in_lockstep = lockstep.sequences != 0 || lockstep.frames_step != 0 || lockstep.stagger != 0 || lockstep.host_threads != 0 || lockstep.perturb_rig >= 0;
+    const bool in_lockstep = lockstep.sequences != 0 || lockstep.frames_step != 0 || lockstep.stagger != 0 || lockstep.host_threads != 0 || lockstep.perturb_rig >= 0 ||
+                             lockstep.perturb_trim_rounds >= 0 || !lockstep.sweep_path.empty();
     if (in_lockstep && (lockstep.sequences < 1 || lockstep.frames_step < 0 || lockstep.stagger < 0 || lockstep.host_threads < 0 || single_only)) {
-        std::fprintf(stderr, "limo_stream: --frames-step, --stagger and --host-threads go with --sequences N (N >= 1, values >= 0); a lock-step drive has no --progress, "
+        std::fprintf(stderr, "limo_stream: --frames-step, --stagger, --host-threads and --sweep go with --sequences N (N >= 1, values >= 0); a lock-step drive has no --progress, "
                              "--velodyne, --dump-velodyne or --misannounce-every\n");
         return 2;
     }
@@ -353,6 +429,10 @@ int main(int argc, char** argv) {
     sp.max_size_optimization_window = window;
     sp.assign_depth = use_depth;
     sp.depth_ahead = depth_ahead;
+    if (depth_thres >= 0.) sp.robust_loss_depth_thres = depth_thres;
+    if (reprojection_thres >= 0.) sp.robust_loss_reprojection_thres = reprojection_thres;
+    if (outlier_quantile >= 0.) sp.outlier_rejection_quantile = outlier_quantile;
+    if (shrubbery_weight >= 0.) sp.shrubbery_weight = shrubbery_weight;
     if (min_flow >= 0.) sp.min_median_flow = min_flow;
     if (time_between_keyframes > 0.) sp.time_between_keyframes_sec = time_between_keyframes;
     if (five_point_prior) sp.motion_prior = StreamParams::MotionPrior::FivePoint;

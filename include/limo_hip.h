@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch, with limo_ctx_last_solve_info and with limo_ba_solve_fixed_landmarks / limo_ba_batch_create_fixed_landmarks: more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
+#define LIMO_ABI_VERSION 6 /* (still 6 with limo_ba_batch_solve_each / limo_ba_adjust_pose_only_batch_each, with limo_ba_batch_create_pose_only / limo_ba_adjust_pose_only_batch, with limo_ctx_last_solve_info and with limo_ba_solve_fixed_landmarks / limo_ba_batch_create_fixed_landmarks: more symbols, no layout changes) 6: limo_depth_params carries the whole parameter file, LIMO_ERR_UNSUPPORTED, limo_depth_last_reasons; 5: limo_ctx_comm_init_host; 2: limo_ba_evaluate_rows, limo_ctx_exchange_stats, limo_depth_last_ground_plane, limo_depth_set_timing, limo_depth_last_kernel_ms; 3: limo_ctx_coop_fallbacks; 4: limo_depth_estimate_begin / _end */
 
 /* Keyframe::FixationStatus, keyframe.hpp:30 */
 enum limo_fixation { LIMO_FIX_POSE = 0, LIMO_FIX_SCALE = 1, LIMO_FIX_NONE = 2 };
@@ -393,6 +393,34 @@ int limo_ba_batch_create_pose_only(limo_ctx* ctx, int32_t n_windows, const limo_
 /* create + solve + download + destroy; poses optimised in place, reports[n] may be NULL. */
 int limo_ba_adjust_pose_only_batch(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
                                    const limo_ba_options* opts, limo_ba_report* reports);
+
+/*
+ * Per-window solve options: limo_ba_batch_solve / limo_ba_adjust_pose_only_batch with ONE limo_ba_options PER WINDOW - a sweep
+ * over outlier-rejection parameters (the reference's tune_parameters_kitti.py: robust_loss_depth_thres x
+ * robust_loss_reprojection_thres) runs as one batch instead of one batch per parameter set.  opts has n_opts entries, and n_opts
+ * is the number of windows of the batch (n_windows for the pose-only call).
+ *   - Fields that may differ from window to window: depth_thres, reprojection_thres, depth_quantile, reprojection_quantile - the
+ *     numeric fields of the reference's OutlierRejectionOptions (bundle_adjuster_keyframes.hpp:79-89).  Every other field - the
+ *     schedule (num_trim_rounds, trim_solver_iterations, max_num_iterations, max_solver_time_sec), min_landmarks_for_trimming,
+ *     minimum_number_residual_groups, the LM constants - must be bitwise equal in all entries.  If one differs the call returns
+ *     LIMO_ERR_INVALID before anything is launched and limo_last_error names the first offending window and field ("window 3:
+ *     max_num_iterations").  The same for n_opts != the number of windows, opts == NULL, and an entry whose threshold or quantile
+ *     is not a finite number ("window 3: depth_thres is not finite").  The batch is untouched and solves normally afterwards.
+ *   - Result.  Window i gets the result of the single call (limo_ba_solve / limo_ba_adjust_pose_only /
+ *     limo_ba_solve_fixed_landmarks) made with opts[i], BIT FOR BIT: every parameter array, the trimmed set, every integer of the
+ *     report, initial_cost and final_cost - on every launch path limo_ctx_last_solve_info can report, with and without the
+ *     iteration log.  (The device keeps one 64-byte record per window: the six constants make_consts derives from opts[i]; a
+ *     workgroup reads its window's record with one scalar load.)
+ *   - No change on the uniform path.  An array whose entries are all equal takes exactly the path of
+ *     limo_ba_batch_solve(&opts[0]): no table is uploaded and the kernels see a null table pointer.  A later
+ *     limo_ba_batch_solve(opts) on the same batch is uniform again; limo_ba_batch_reset works between the two forms.
+ *   - Scope.  Any unsharded batch: limo_ba_batch_create, _create_pose_only, _create_fixed_landmarks.  A landmark-sharded batch
+ *     returns LIMO_ERR_INVALID; limo_ba_evaluate* and limo_ba_solve_sharded take one set of options as before.
+ */
+int limo_ba_batch_solve_each(limo_ba_batch* batch, int32_t n_opts, const limo_ba_options* opts);
+/* limo_ba_adjust_pose_only_batch with opts[n_windows]: create + solve_each + download + destroy. */
+int limo_ba_adjust_pose_only_batch_each(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
+                                        const limo_ba_options* opts, limo_ba_report* reports);
 
 /*
  * limo_ba_solve with per-landmark constness: the window is solved against landmarks the caller trusts (a map, LiDAR, an older part

@@ -390,6 +390,8 @@ ABI_SYMBOLS = [
     "limo_ba_adjust_pose_only_batch",
     "limo_ba_solve_fixed_landmarks",
     "limo_ba_batch_create_fixed_landmarks",
+    "limo_ba_batch_solve_each",
+    "limo_ba_adjust_pose_only_batch_each",
     "limo_landmark_init",
     "limo_trim_quantile",
     "limo_depth_default_params",
@@ -486,6 +488,9 @@ def load():
     if hasattr(lib, "limo_ba_solve_fixed_landmarks"):  # (added without an ABI bump, like the two above)
         lib.limo_ba_solve_fixed_landmarks.argtypes = [vp, C.POINTER(BaWindow), c_uint8_p, C.POINTER(BaOptions), C.POINTER(BaReport)]
         lib.limo_ba_batch_create_fixed_landmarks.argtypes = [vp, C.c_int32, C.POINTER(BaWindow), C.POINTER(c_uint8_p), C.POINTER(vp)]
+    if hasattr(lib, "limo_ba_batch_solve_each"):  # (added without an ABI bump, like the ones above)
+        lib.limo_ba_batch_solve_each.argtypes = [vp, C.c_int32, C.POINTER(BaOptions)]
+        lib.limo_ba_adjust_pose_only_batch_each.argtypes = [vp, C.c_int32, C.POINTER(BaWindow), C.POINTER(SpeedPrior), C.POINTER(BaOptions), C.POINTER(BaReport)]
     lib.limo_landmark_init.argtypes = [vp, C.c_int32, c_int32_p, C.POINTER(Ray), c_uint8_p, c_double_p, c_uint8_p]
     lib.limo_trim_quantile.argtypes = [C.c_int32, c_int64_p, c_double_p, C.c_double, c_int64_p]
     lib.limo_depth_default_params.argtypes = [C.POINTER(DepthParams)]

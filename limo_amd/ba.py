@@ -264,10 +264,18 @@ class Context:
 
     def adjust_pose_only_batch(self, windows, priors, opts):
         """limo_ba_adjust_pose_only_batch: N independent pose-only windows in one call.  priors: None, or one entry per window
-        (a _ffi.SpeedPrior, or None for a window without prior).  The windows' poses are updated in place; returns the reports."""
+        (a _ffi.SpeedPrior, or None for a window without prior).  opts: one BaOptions, or a sequence with one per window (thresholds and
+        quantiles may differ, include/limo_hip.h).  The windows' poses are updated in place; returns the reports."""
         windows = list(windows)
         arr = struct_array(windows)
         reps = (_ffi.BaReport * max(1, len(windows)))()
+        if not isinstance(opts, _ffi.BaOptions):  # a sequence: one set of options per window (limo_ba_adjust_pose_only_batch_each)
+            each, n_each = options_array(opts)
+            if n_each != len(windows):
+                raise ValueError("opts: %d entries for %d windows" % (n_each, len(windows)))
+            rc = self.lib.limo_ba_adjust_pose_only_batch_each(self.ptr, len(windows), arr, prior_array(priors, len(windows)), each, reps)
+            _check(rc, self.ptr, "limo_ba_adjust_pose_only_batch_each")
+            return [reps[i].as_dict() for i in range(len(windows))]
         rc = self.lib.limo_ba_adjust_pose_only_batch(self.ptr, len(windows), arr, prior_array(priors, len(windows)), C.byref(opts), reps)
         _check(rc, self.ptr, "limo_ba_adjust_pose_only_batch")
         return [reps[i].as_dict() for i in range(len(windows))]
@@ -315,6 +323,15 @@ def fixed_flags(lm_fixed, n_lm):
     if flags.size != n_lm:
         raise ValueError("lm_fixed: %d flags for %d landmarks" % (flags.size, n_lm))
     return flags if n_lm else np.zeros(1, np.uint8)
+
+
+def options_array(opts):
+    """(limo_ba_options[n], n) from a sequence of _ffi.BaOptions (copies; the array is at least one entry long)."""
+    opts = list(opts)
+    arr = (_ffi.BaOptions * max(1, len(opts)))()
+    for i, o in enumerate(opts):
+        C.memmove(C.byref(arr, i * C.sizeof(_ffi.BaOptions)), C.byref(o), C.sizeof(_ffi.BaOptions))
+    return arr, len(opts)
 
 
 def prior_array(priors, n):
@@ -366,7 +383,13 @@ class Batch:
         _check(self.lib.limo_ba_batch_create(ctx.ptr, len(self.windows), self._arr, C.byref(self.ptr)), ctx.ptr, "limo_ba_batch_create")
 
     def solve(self, opts):
-        _check(self.lib.limo_ba_batch_solve(self.ptr, C.byref(opts)), self.ctx.ptr, "limo_ba_batch_solve")
+        """opts: one BaOptions for all windows, or a sequence with one per window (limo_ba_batch_solve_each: thresholds and quantiles may
+        differ from window to window, everything else must be equal)."""
+        if isinstance(opts, _ffi.BaOptions):
+            _check(self.lib.limo_ba_batch_solve(self.ptr, C.byref(opts)), self.ctx.ptr, "limo_ba_batch_solve")
+            return
+        each, n_each = options_array(opts)
+        _check(self.lib.limo_ba_batch_solve_each(self.ptr, n_each, each), self.ctx.ptr, "limo_ba_batch_solve_each")
 
     def reset(self):
         _check(self.lib.limo_ba_batch_reset(self.ptr), self.ctx.ptr, "limo_ba_batch_reset")

@@ -388,6 +388,26 @@ __global__ void k_view_consts(BatchView bv) {
 // (79 B per observation under counters in round 5, with the slot table; the separate view-major linearise + landmark-major
 // accumulate pair of round 1 moved 101 + 93.)
 typedef const double __attribute__((address_space(4))) cdouble;
+
+// The constants of window w's workgroup: `c`, with the six members a window may have for itself taken from the window's record
+// where the solve carries a table (BatchView::wopt; limo_ba_batch_solve_each with options that differ).  The window is uniform
+// over the workgroup and the table was written before the launch: one scalar load of the record through the constant address
+// space, no vector load, no register per lane.  Without a table (a kernel argument: a uniform branch) nothing is read.  The
+// per-lane statements (kba_items.hpp) take the patched copy like any SolveConsts.
+__device__ __forceinline__ SolveConsts window_consts(const BatchView& bv, const SolveConsts& c, int w) {
+    SolveConsts k = c;
+    if (bv.wopt) {
+        cdouble* r = (cdouble*)(bv.wopt + __builtin_amdgcn_readfirstlane(w));
+        static_assert(offsetof(WinOpts, reprojection_quantile) == 5 * sizeof(double), "the record's six doubles, in this order");
+        k.a_rep = r[0];
+        k.a_dep = r[1];
+        k.inv_a_rep2 = r[2];
+        k.inv_a_dep2 = r[3];
+        k.depth_quantile = r[4];
+        k.reprojection_quantile = r[5];
+    }
+    return k;
+}
 constexpr int kLinAccl = 13;  // doubles per lane that lin_lm_block parks in LDS: V 6 | g 3 | Jacobi scale 3 | ground-plane row
 // (the body of k_lin_lm for landmark workgroup b; k_solve_wg runs it for the workgroups of its window one after the other)
 // The landmark block's nine running sums (V 6 | g 3) live in LDS ([9][kBlock] doubles in front of the view slices, one column
@@ -590,7 +610,7 @@ template <bool VLDS>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_lin_lm(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int b = wl_at(bv, wl, blockIdx.x);
     if (b < 0) return;
-    lin_lm_block<VLDS>(bv, c, b);
+    lin_lm_block<VLDS>(bv, window_consts(bv, c, bv.lblk_win[b]), b);
 }
 // vlds: the launch keeps a copy of the view constants in LDS as well
 __host__ __device__ inline int lin_lm_lds_bytes(int n_view_max, bool vlds) {
@@ -638,7 +658,7 @@ __device__ __forceinline__ void backsub_block(const BatchView& bv, const SolveCo
 __global__ __launch_bounds__(kBlock) void k_backsub(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int b = wl_at(bv, wl, blockIdx.x);
     if (b < 0) return;
-    backsub_block(bv, c, b);
+    backsub_block(bv, window_consts(bv, c, bv.lblk_win[b]), b);
 }
 
 // ------------------------------------------------------------------------------------------ Schur complement (MFMA)
@@ -1634,7 +1654,7 @@ __global__ __launch_bounds__(kBlock) void k_trim_select(BatchView bv, SolveConst
         w = wl[blockIdx.x];
     }
     if (!bv.win[w].do_trim) return;
-    trim_select_win(bv, c, w);
+    trim_select_win(bv, window_consts(bv, c, w), w);
     if (bv.counted) {
         __syncthreads();
         if (threadIdx.x == 0) sched_after_trim(bv.st[w], c);
@@ -1655,9 +1675,10 @@ __global__ __launch_bounds__(kBlock) void k_trim_select(BatchView bv, SolveConst
 //   * the step reduction of k_step_decide is a 64-lane sum: reduce_step(.., n_work = 64) forms exactly that one;
 //   * cap_ticks > 0: wall-clock cap of each solve in ticks of the 100 MHz constant clock (Solver::Options::
 //     max_solver_time_in_seconds as run_schedule applies it: checked once per iteration after the linearisation).
-__global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c, long long cap_ticks, double* plane_rep, double* plane_dep) {
+__global__ __launch_bounds__(kBlock) void k_solve_wg(BatchView bv, SolveConsts c_launch, long long cap_ticks, double* plane_rep, double* plane_dep) {
     const int w = blockIdx.x;
     const int tid = threadIdx.x;
+    const SolveConsts c = window_consts(bv, c_launch, w);  // (the window's own thresholds and quantiles, where the solve has a table)
     const WinDesc& wd = bv.win[w];
     WinState& st = bv.st[w];
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1836,7 +1857,7 @@ __device__ __forceinline__ bool coop_sync(int32_t* bar, int32_t* abort_word, int
     return __syncthreads_and(ok) != 0;
 }
 
-__global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts c, CoopParams a) {
+__global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts c_launch, CoopParams a) {
     // Workgroup -> (window, member).  The G workgroups of a window are placed on ONE XCD (block b runs on XCD b % 8 -
     // observed, not promised: it buys speed, never correctness): what one of them writes with plain stores stays in the L2 the
     // others read from, so the first touches behind every barrier are L2 hits instead of round trips over the fabric
@@ -1846,6 +1867,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_coop(BatchView bv, SolveConsts
     const int xcd = blockIdx.x & 7, member = blockIdx.x >> 3;
     const int w = xcd + 8 * (member / G), g = member % G;
     if (w >= bv.n_win) return;
+    const SolveConsts c = window_consts(bv, c_launch, w);  // (the window's own thresholds and quantiles, where the solve has a table)
     const int tid = threadIdx.x, wave = tid >> 6;
     const WinDesc& wd = bv.win[w];
     WinState& st = bv.st[w];

@@ -207,6 +207,18 @@ struct SolveConsts {  // subset of limo_ba_options the kernels need
                           // k_solve_coop)
 };
 
+// Per-window solve options (limo_ba_batch_solve_each): the six members of SolveConsts a window may have for itself, as
+// make_consts of the window's own limo_ba_options gives them (kba_window_options.hpp:window_options_table) - the bits of the single
+// call, the IEEE division behind inv_a_*2 included.  One record per window, a cache line each: a workgroup reads its window's record
+// with one wave-uniform scalar load (kba_kernels.hip:window_consts).
+struct alignas(64) WinOpts {
+    double a_rep, a_dep;
+    double inv_a_rep2, inv_a_dep2;
+    double depth_quantile, reprojection_quantile;
+    double pad[2];
+};
+static_assert(sizeof(WinOpts) == 64, "one record per cache line");
+
 // Raw pointers to every buffer of a batch (device pointers in the library, host pointers in the emulator).
 struct BatchView {
     int32_t n_win, TK, TL, TO, TV, TG, n_blk, n_lblk, n_sblk, Vmax;
@@ -336,6 +348,8 @@ struct BatchView {
     int32_t* sched_lists;       // the worklists, back to back
     int32_t sched_off[SL_COUNT];  // offset of list k's count word inside sched_lists
     int32_t* sched_done_host;   // pinned ring (4 words): windows finished as of round r at [r & 3]
+    // --- per-window solve options: not a batch buffer, set by the library for a solve whose windows' options differ
+    const WinOpts* wopt = nullptr;  // [n_win], indexed like `win`; null (every uniform solve, the emulator): all windows take SolveConsts
 };
 
 // depth values of the d plane of BatchView::pair_m that no measured depth can have (a measured depth is > 0)

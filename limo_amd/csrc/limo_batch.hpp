@@ -254,6 +254,10 @@ struct limo_ba_batch {
     SolveConsts c;
     int rc = LIMO_OK;
     SolveRun run;
+    // per-window options of the solve in progress (limo_ba_batch_solve_each with options that differ): the host's records, uploaded
+    // to d_wopt (made by the first such solve); every view of a uniform solve holds a null table (set_window_table)
+    std::vector<WinOpts> wopt_host;
+    WinOpts* d_wopt = nullptr;
     // ---- across solves
     int lin_lds_set = 0;  // dynamic LDS k_lin_lm<false> was allowed beyond the default 48 KB (k_lin_lm<true> never needs more)
     // S_part holds packed slabs (SolveConsts::slab_packed) of an earlier solve of this batch.  The tile layout counts on the zeros of
@@ -488,6 +492,21 @@ struct limo_ba_batch {
         }
         opts = o;
         c = consts_for(o);
+        return LIMO_OK;
+    }
+
+    // The per-window table of the solve that follows, in every view a kernel of it can be handed (unsharded: pv = {bv}; the slot
+    // groups keep copies of bv).  null: a uniform solve - no kernel reads a record.
+    void set_window_table(const WinOpts* t) {
+        bv.wopt = t;
+        for (BatchView& v : pv) v.wopt = t;
+        for (StreamGroup& g : stream.groups) g.sv.wopt = t;
+    }
+    // wopt_host -> the device (the context's stream, in front of the solve's launches)
+    int upload_window_table() {
+        if (!d_wopt && dmalloc((void**)&d_wopt, sizeof(WinOpts) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+        HIP_TRY(ctx, hipMemcpyAsync(d_wopt, wopt_host.data(), sizeof(WinOpts) * wopt_host.size(), hipMemcpyHostToDevice, ctx->stream));
+        set_window_table(d_wopt);
         return LIMO_OK;
     }
 

@@ -21,6 +21,7 @@
 #include "kba_batch_plan.hpp"
 #include "kba_buffers.hpp"
 #include "kba_rows.hpp"
+#include "kba_window_options.hpp"
 
 using namespace kba;
 
@@ -198,11 +199,17 @@ int limo_ba_batch_create(limo_ctx* ctx, int32_t n_windows, const limo_ba_window*
     return batch_create_impl(ctx, n_windows, windows, nullptr, PackOptions(), out);
 }
 
-int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
-    if (!b) return LIMO_ERR_INVALID;
+// The solve behind limo_ba_batch_solve (each == null: one set of options, no table in any view) and limo_ba_batch_solve_each
+// (each: the windows' own options, which passed check_window_options and differ - opts is each[0]).
+static int batch_solve_impl(limo_ba_batch* b, const limo_ba_options* opts, const limo_ba_options* each) {
     limo_ctx* ctx = b->ctx;
     if (hipSetDevice(ctx->device) != hipSuccess) return LIMO_ERR_NO_DEVICE;
     if (opts && b->refresh_options(*opts) != LIMO_OK) return LIMO_ERR_RUNTIME;
+    b->set_window_table(nullptr);
+    if (each) {
+        window_options_table(b->P.n_win, each, false, b->wopt_host);
+        if (b->upload_window_table() != LIMO_OK) return LIMO_ERR_RUNTIME;
+    }
     b->rc = LIMO_OK;
     // iteration log: every solve starts its windows' logs at zero entries (not offered for a landmark-sharded batch)
     if (b->log.bind(ctx->iteration_log && b->shards.n_shards == 1) != LIMO_OK) return LIMO_ERR_RUNTIME;
@@ -224,6 +231,27 @@ int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
     b->publish_run();
     if (b->timers.stop_solve() != LIMO_OK) return LIMO_ERR_RUNTIME;
     return b->rc;
+}
+
+int limo_ba_batch_solve(limo_ba_batch* b, const limo_ba_options* opts) {
+    if (!b) return LIMO_ERR_INVALID;
+    return batch_solve_impl(b, opts, nullptr);
+}
+
+int limo_ba_batch_solve_each(limo_ba_batch* b, int32_t n_opts, const limo_ba_options* opts) {
+    if (!b) return LIMO_ERR_INVALID;
+    limo_ctx* ctx = b->ctx;
+    if (b->shards.n_shards > 1) {
+        ctx->err = "limo_ba_batch_solve_each: not offered for a landmark-sharded batch";
+        return LIMO_ERR_INVALID;
+    }
+    bool uniform = true;
+    std::string why;
+    if (check_window_options(b->P.n_win, n_opts, opts, &uniform, why) != LIMO_OK) {  // (nothing has been launched)
+        ctx->err = "limo_ba_batch_solve_each: " + why;
+        return LIMO_ERR_INVALID;
+    }
+    return batch_solve_impl(b, &opts[0], uniform ? nullptr : opts);
 }
 
 int limo_ba_batch_reset(limo_ba_batch* b) {
@@ -455,7 +483,7 @@ int limo_ba_solve_sharded(limo_ctx* ctx, limo_ba_window* window, const limo_ba_o
 // The calls that take windows and give results back (limo_ba_solve, limo_ba_adjust_pose_only, limo_ba_adjust_pose_only_batch): create,
 // solve, download, destroy over `n` windows.  KBA_HOST_TRACE=1 prints where the host time of the call goes.
 static int solve_n(limo_ctx* ctx, int32_t n, limo_ba_window* windows, const limo_ba_options* opts, const PackOptions& po, limo_ba_report* reports,
-                   const char* what) {
+                   const char* what, const limo_ba_options* each = nullptr) {
     using Clock = std::chrono::steady_clock;
     static const bool trace = std::getenv("KBA_HOST_TRACE") != nullptr;
     const auto t_a = Clock::now();
@@ -463,7 +491,11 @@ static int solve_n(limo_ctx* ctx, int32_t n, limo_ba_window* windows, const limo
     int rc = batch_create_impl(ctx, n, windows, opts, po, &b);
     if (rc != LIMO_OK) return rc;
     const auto t0 = Clock::now();
-    rc = limo_ba_batch_solve(b, nullptr);
+    rc = each ? limo_ba_batch_solve_each(b, n, each) : limo_ba_batch_solve(b, nullptr);  // (each: the windows' own options; opts is each[0])
+    if (rc != LIMO_OK && each) {
+        limo_ba_batch_destroy(b);
+        return rc;
+    }
     const auto t1 = Clock::now();
     if (rc == LIMO_OK) rc = limo_ba_batch_download(b, windows, reports);
     {   // the windows' iteration logs outlive the batch in the context's buffer (empty with the switch off)
@@ -597,6 +629,27 @@ int limo_ba_adjust_pose_only_batch(limo_ctx* ctx, int32_t n_windows, limo_ba_win
     po.per_window_prior = true;
     po.window_priors = priors;
     return solve_n(ctx, n_windows, windows, opts, po, reports, "limo_ba_adjust_pose_only_batch");
+}
+
+int limo_ba_adjust_pose_only_batch_each(limo_ctx* ctx, int32_t n_windows, limo_ba_window* windows, const limo_speed_prior* priors,
+                                        const limo_ba_options* opts, limo_ba_report* reports) {
+    if (!ctx) return LIMO_ERR_INVALID;
+    if (!windows || n_windows <= 0) {
+        ctx->err = "limo_ba_adjust_pose_only_batch_each: no windows";
+        return LIMO_ERR_INVALID;
+    }
+    bool uniform = true;
+    std::string why;
+    if (check_window_options(n_windows, n_windows, opts, &uniform, why) != LIMO_OK) {  // (before anything is packed or launched)
+        ctx->err = "limo_ba_adjust_pose_only_batch_each: " + why;
+        return LIMO_ERR_INVALID;
+    }
+    if (uniform) return limo_ba_adjust_pose_only_batch(ctx, n_windows, windows, priors, &opts[0], reports);
+    PackOptions po;
+    po.pose_only = true;
+    po.per_window_prior = true;
+    po.window_priors = priors;
+    return solve_n(ctx, n_windows, windows, &opts[0], po, reports, "limo_ba_adjust_pose_only_batch_each", opts);
 }
 
 int limo_ba_evaluate(limo_ctx* ctx, const limo_ba_window* window, const limo_ba_options* opts, int apply_loss,

@@ -5,10 +5,11 @@
 //     -> motion prior                                 external, constant velocity (host), or the five-point prior: matches and gate
 //                                                     per sequence, the estimates through one limo_five_point_batch
 //                                                     (StreamParams::five_point_on_device; off: the host estimator per sequence)
-//     -> limo_ba_adjust_pose_only_batch               every frame without an external prior
+//     -> limo_ba_adjust_pose_only_batch[_each]        every frame without an external prior (_each: the jobs' options differ)
 //     -> keyframe selection (host, per sequence), then the pushes of all sequences: one limo_landmark_init over the concatenated rays
 //     -> for the sequences whose solve is due: window cut + labels (host), limo_landmark_select_batch
-//        (StreamParams::landmark_selection_on_device; off: the host selector per sequence), limo_ba_batch_create / _solve / _download
+//        (StreamParams::landmark_selection_on_device; off: the host selector per sequence), limo_ba_batch_create / _solve[_each] /
+//        _download
 //     -> pose of the frame, motion, statistics
 // A sequence without a frame in a tick sits out; sequences may start late, end early and solve on different ticks.  Every sequence is
 // a stream_detail::Sequence of its own: the policy of a frame is that type's, this file holds the calls.  What the batched entry points
@@ -18,7 +19,9 @@
 // thread that calls tick() calls the C-ABI, on the driver's one context.  No result depends on host_threads.
 // Where the library behind the C-ABI lacks a batched entry point, that stage loops over the single call.  Stats counts both.
 // Not here: the depth assignment one frame ahead (there is no begin / end form of the batch call), the iteration table
-// (BundleAdjusterKeyframes::minimizer_progress_to_stdout_), different rigs or parameters per sequence, several GPUs.
+// (BundleAdjusterKeyframes::minimizer_progress_to_stdout_), different rigs per sequence, per-sequence parameters of the depth,
+// five-point and selection batches or of the solve schedule (the outlier-rejection thresholds and quantiles, the shrubbery weight
+// and the keyframe / window policy MAY differ per sequence: the second constructor), several GPUs.
 #pragma once
 #include <condition_variable>
 #include <functional>
@@ -125,6 +128,8 @@ private:
 #pragma weak limo_five_point_default_params
 #pragma weak limo_five_point_batch
 #pragma weak limo_ba_adjust_pose_only_batch
+#pragma weak limo_ba_adjust_pose_only_batch_each
+#pragma weak limo_ba_batch_solve_each
 #pragma weak limo_landmark_select
 #pragma weak limo_landmark_select_batch
 #pragma weak limo_ba_batch_create
@@ -148,9 +153,11 @@ public:
     };
     // One stage of the tick.  batched_calls: calls of the batched entry point, items: what they carried (frames, windows, pushes, pools),
     // max_items: the most one call carried; fallback_calls: single calls made because the library lacks the batched entry point or
-    // refused the batch.  sec_host: the per-sequence host phase in front of the call (on the pool), sec_abi: inside the C-ABI.
+    // refused the batch.  per_window_calls (pose_only, solve): batched calls whose jobs carried DIFFERING options - the _each entry
+    // points (a backend without them gets one batched call per group of equal options instead, and counts none here).
+    // sec_host: the per-sequence host phase in front of the call (on the pool), sec_abi: inside the C-ABI.
     struct Stage {
-        long batched_calls = 0, items = 0, fallback_calls = 0;
+        long batched_calls = 0, items = 0, fallback_calls = 0, per_window_calls = 0;
         int max_items = 0;
         double sec_host = 0., sec_abi = 0.;
     };
@@ -165,9 +172,26 @@ public:
     };
 
     // host_threads <= 0: min(N, 16) (never the machine's core count: a GPU node shares its cores)
+    // (all sequences with the same parameters)
     LockstepDriver(const StreamParams& p, const std::vector<Rig>& rigs, int host_threads = 0)
-            : p_(p), host_threads_(host_threads > 0 ? host_threads : (int)std::min<size_t>(std::max<size_t>(rigs.size(), 1), 16)), pool_(host_threads_) {
+            : LockstepDriver(std::vector<StreamParams>(std::max<size_t>(rigs.size(), 1), p), rigs, host_threads) {}
+    // One StreamParams per sequence - a sweep over outlier-rejection parameters side by side (the reference's tune_parameters_kitti.py).
+    // May differ: robust_loss_depth_thres, robust_loss_reprojection_thres, outlier_rejection_quantile, shrubbery_weight,
+    // max_size_optimization_window, min_number_connecting_landmarks, min_median_flow, critical_rotation_difference,
+    // time_between_keyframes_sec, height_over_ground, prior_speed - host phases of the sequence, or options that travel with its
+    // window.  Every other field must be equal: outlier_rejection_num_iterations and solver_time_sec decide the schedule of a batched
+    // solve, the rest parameterises a batched depth, five-point or selection call (max_size_optimization_window among them while the
+    // device selection is on: it sizes that call's add rules).  A difference there is refused, the way a differing rig is.
+    LockstepDriver(const std::vector<StreamParams>& ps, const std::vector<Rig>& rigs, int host_threads = 0)
+            : ps_(ps), p_(ps_.empty() ? fallback_params_ : ps_[0]),
+              host_threads_(host_threads > 0 ? host_threads : (int)std::min<size_t>(std::max<size_t>(rigs.size(), 1), 16)), pool_(host_threads_) {
         if (rigs.empty()) throw std::invalid_argument("LockstepDriver: no sequence");
+        if (ps_.size() != rigs.size()) throw std::invalid_argument("LockstepDriver: " + std::to_string(ps_.size()) + " parameter sets for " + std::to_string(rigs.size()) + " sequences");
+        for (size_t i = 1; i < ps_.size(); ++i)
+            if (const char* field = fixedDifference(ps_[0], ps_[i]))
+                throw std::invalid_argument("LockstepDriver: the parameters of sequence " + std::to_string(i) + " differ from sequence 0's in " + field +
+                                            ": it decides the schedule of a batched solve or parameterises a batched depth, five-point or selection call, which take one "
+                                            "value; drive it with a StreamDriver of its own");
         for (size_t i = 0; i < rigs.size(); ++i) {
             if (!rigs[i].camera) throw std::invalid_argument("LockstepDriver: sequence " + std::to_string(i) + " has no camera");
             if (!sameRig(rigs[0], rigs[i]))
@@ -175,8 +199,8 @@ public:
                                             " differs from sequence 0's (camera intrinsics, camera <- vehicle or camera <- lidar): the batched depth and selection "
                                             "calls take one rig; drive it with a StreamDriver of its own");
         }
-        const bool five_point_device = p.five_point_on_device && &limo_five_point_default_params != nullptr && (&limo_five_point_batch != nullptr || &limo_five_point != nullptr);
-        for (size_t i = 0; i < rigs.size(); ++i) seqs_.push_back(std::make_unique<Sequence>(p_, rigs[i].camera, five_point_device, (int)i));
+        const bool five_point_device = p_.five_point_on_device && &limo_five_point_default_params != nullptr && (&limo_five_point_batch != nullptr || &limo_five_point != nullptr);
+        for (size_t i = 0; i < rigs.size(); ++i) seqs_.push_back(std::make_unique<Sequence>(ps_[i], rigs[i].camera, five_point_device, (int)i));
         T_cam_lidar_ = convert(rigs[0].T_camera_lidar);
         ctx_ = createContext();
         limo_depth_default_params(&depth_params_);
@@ -276,9 +300,30 @@ public:
                     priors.push_back(s->pose_job.prior);  // (speed_weight 0: "no prior for this window")
                 }
                 std::vector<limo_ba_report> reports(ref.size());
-                check(limo_ba_adjust_pose_only_batch(ctx_, (int32_t)ws.size(), ws.data(), priors.data(), &ref[0]->pose_job.opts, reports.data()), "limo_ba_adjust_pose_only_batch");
+                // the jobs' own options: all equal - today's call; else one call with an entry per window, or (a backend without it)
+                // one call per group of equal options.  No window is ever solved with another window's options.
+                std::vector<limo_ba_options> opts;
+                for (Sequence* s : ref) opts.push_back(s->pose_job.opts);
+                const std::vector<std::vector<size_t>> groups = optionGroups(opts);
+                if (groups.size() == 1) {
+                    check(limo_ba_adjust_pose_only_batch(ctx_, (int32_t)ws.size(), ws.data(), priors.data(), &opts[0], reports.data()), "limo_ba_adjust_pose_only_batch");
+                    batched(stats_.pose_only, ref.size());
+                } else if (&limo_ba_adjust_pose_only_batch_each != nullptr) {
+                    check(limo_ba_adjust_pose_only_batch_each(ctx_, (int32_t)ws.size(), ws.data(), priors.data(), opts.data(), reports.data()), "limo_ba_adjust_pose_only_batch_each");
+                    batched(stats_.pose_only, ref.size());
+                    ++stats_.pose_only.per_window_calls;
+                } else {
+                    for (const std::vector<size_t>& g : groups) {
+                        std::vector<limo_ba_window> gw;
+                        std::vector<limo_speed_prior> gp;
+                        for (size_t k : g) gw.push_back(ws[k]), gp.push_back(priors[k]);
+                        std::vector<limo_ba_report> gr(g.size());
+                        check(limo_ba_adjust_pose_only_batch(ctx_, (int32_t)gw.size(), gw.data(), gp.data(), &opts[g[0]], gr.data()), "limo_ba_adjust_pose_only_batch");
+                        for (size_t i = 0; i < g.size(); ++i) reports[g[i]] = gr[i];
+                        batched(stats_.pose_only, g.size());
+                    }
+                }
                 for (size_t k = 0; k < ref.size(); ++k) ref[k]->pose_job.report = reports[k];
-                batched(stats_.pose_only, ref.size());
             } else {
                 for (Sequence* s : ref) {
                     BundleAdjusterKeyframes::WindowJob& j = s->pose_job;
@@ -357,22 +402,38 @@ public:
         if (!due.empty()) {
             Timed t(stats_.solve.sec_abi);
             if (&limo_ba_batch_create != nullptr && &limo_ba_batch_solve != nullptr && &limo_ba_batch_download != nullptr && &limo_ba_batch_destroy != nullptr) {
-                std::vector<limo_ba_window> ws;
-                for (Sequence* s : due) ws.push_back(*s->solve_job.window);
-                std::vector<limo_ba_report> reports(due.size());
-                limo_ba_batch* b = nullptr;
-                check(limo_ba_batch_create(ctx_, (int32_t)ws.size(), ws.data(), &b), "limo_ba_batch_create");
-                int rc = limo_ba_batch_solve(b, &due[0]->solve_job.opts);
-                const char* what = "limo_ba_batch_solve";
-                if (rc == LIMO_OK) {
-                    rc = limo_ba_batch_download(b, ws.data(), reports.data());
-                    what = "limo_ba_batch_download";
+                // one resident batch over `which` of the due sequences: create, solve (each: an entry of options per window), download
+                auto solveBatch = [&](const std::vector<size_t>& which, const std::vector<limo_ba_options>& opts, bool each) {
+                    std::vector<limo_ba_window> ws;
+                    for (size_t k : which) ws.push_back(*due[k]->solve_job.window);
+                    std::vector<limo_ba_report> reports(which.size());
+                    limo_ba_batch* b = nullptr;
+                    check(limo_ba_batch_create(ctx_, (int32_t)ws.size(), ws.data(), &b), "limo_ba_batch_create");
+                    int rc = each ? limo_ba_batch_solve_each(b, (int32_t)opts.size(), opts.data()) : limo_ba_batch_solve(b, &opts[0]);
+                    const char* what = each ? "limo_ba_batch_solve_each" : "limo_ba_batch_solve";
+                    if (rc == LIMO_OK) {
+                        rc = limo_ba_batch_download(b, ws.data(), reports.data());
+                        what = "limo_ba_batch_download";
+                    }
+                    const std::string err = rc != LIMO_OK ? limo_last_error(ctx_) : "";
+                    limo_ba_batch_destroy(b);
+                    if (rc != LIMO_OK) throw std::runtime_error(std::string(what) + ": " + err);
+                    for (size_t i = 0; i < which.size(); ++i) due[which[i]]->solve_job.report = reports[i];
+                    batched(stats_.solve, which.size());
+                };
+                // (the jobs' own options: as in the pose-only stage)
+                std::vector<limo_ba_options> opts;
+                std::vector<size_t> all;
+                for (size_t k = 0; k < due.size(); ++k) opts.push_back(due[k]->solve_job.opts), all.push_back(k);
+                const std::vector<std::vector<size_t>> groups = optionGroups(opts);
+                if (groups.size() == 1) {
+                    solveBatch(all, opts, false);
+                } else if (&limo_ba_batch_solve_each != nullptr) {
+                    solveBatch(all, opts, true);
+                    ++stats_.solve.per_window_calls;
+                } else {
+                    for (const std::vector<size_t>& g : groups) solveBatch(g, {opts[g[0]]}, false);
                 }
-                const std::string err = rc != LIMO_OK ? limo_last_error(ctx_) : "";
-                limo_ba_batch_destroy(b);
-                if (rc != LIMO_OK) throw std::runtime_error(std::string(what) + ": " + err);
-                for (size_t k = 0; k < due.size(); ++k) due[k]->solve_job.report = reports[k];
-                batched(stats_.solve, due.size());
             } else {
                 for (Sequence* s : due) {
                     BundleAdjusterKeyframes::WindowJob& j = s->solve_job;
@@ -409,6 +470,55 @@ private:
         for (int i = 0; i < 3; ++i) same = same && a.T_camera_lidar.t[i] == b.T_camera_lidar.t[i];
         return same;
     }
+    // The first field of b that must equal a's and does not (see the second constructor), or null.
+    static const char* fixedDifference(const StreamParams& a, const StreamParams& b) {
+#define KBA_LOCKSTEP_FIXED(f) \
+    if (!(a.f == b.f)) return #f;
+        KBA_LOCKSTEP_FIXED(outlier_rejection_num_iterations)
+        KBA_LOCKSTEP_FIXED(solver_time_sec)
+        KBA_LOCKSTEP_FIXED(motion_prior)
+        KBA_LOCKSTEP_FIXED(five_point_on_device)
+        KBA_LOCKSTEP_FIXED(landmark_selection_on_device)
+        KBA_LOCKSTEP_FIXED(max_number_landmarks_near_bin)
+        KBA_LOCKSTEP_FIXED(max_number_landmarks_middle_bin)
+        KBA_LOCKSTEP_FIXED(max_number_landmarks_far_bin)
+        KBA_LOCKSTEP_FIXED(roi_middle)
+        KBA_LOCKSTEP_FIXED(roi_far)
+        KBA_LOCKSTEP_FIXED(voxel_size_xyz)
+        KBA_LOCKSTEP_FIXED(add_ground_landmarks_per_keyframe)
+        KBA_LOCKSTEP_FIXED(add_depth_landmarks_newest)
+        KBA_LOCKSTEP_FIXED(assign_depth)
+        KBA_LOCKSTEP_FIXED(depth_ahead)
+        KBA_LOCKSTEP_FIXED(image_width)
+        KBA_LOCKSTEP_FIXED(image_height)
+        KBA_LOCKSTEP_FIXED(ground_labels)
+#undef KBA_LOCKSTEP_FIXED
+        if (a.landmark_selection_on_device && a.add_ground_landmarks_per_keyframe > 0 && a.max_size_optimization_window != b.max_size_optimization_window)
+            return "max_size_optimization_window (with landmark_selection_on_device it sizes the selection call's add rules)";
+        return nullptr;
+    }
+    static bool sameOptions(const limo_ba_options& a, const limo_ba_options& b) {
+        return a.depth_thres == b.depth_thres && a.reprojection_thres == b.reprojection_thres && a.depth_quantile == b.depth_quantile &&
+               a.reprojection_quantile == b.reprojection_quantile && a.num_trim_rounds == b.num_trim_rounds && a.trim_solver_iterations == b.trim_solver_iterations &&
+               a.min_landmarks_for_trimming == b.min_landmarks_for_trimming && a.minimum_number_residual_groups == b.minimum_number_residual_groups &&
+               a.max_num_iterations == b.max_num_iterations && a.max_solver_time_sec == b.max_solver_time_sec && a.function_tolerance == b.function_tolerance &&
+               a.gradient_tolerance == b.gradient_tolerance && a.parameter_tolerance == b.parameter_tolerance &&
+               a.initial_trust_region_radius == b.initial_trust_region_radius && a.max_trust_region_radius == b.max_trust_region_radius &&
+               a.min_trust_region_radius == b.min_trust_region_radius && a.min_lm_diagonal == b.min_lm_diagonal && a.max_lm_diagonal == b.max_lm_diagonal &&
+               a.min_relative_decrease == b.min_relative_decrease && a.max_num_consecutive_invalid_steps == b.max_num_consecutive_invalid_steps &&
+               a.jacobi_scaling == b.jacobi_scaling;
+    }
+    // the jobs of a call by equal options: groups of indices, each in job order, the groups in the order of their first job
+    static std::vector<std::vector<size_t>> optionGroups(const std::vector<limo_ba_options>& opts) {
+        std::vector<std::vector<size_t>> groups;
+        for (size_t k = 0; k < opts.size(); ++k) {
+            size_t g = 0;
+            while (g < groups.size() && !sameOptions(opts[groups[g][0]], opts[k])) ++g;
+            if (g == groups.size()) groups.emplace_back();
+            groups[g].push_back(k);
+        }
+        return groups;
+    }
     // a phase over `which` on the pool: fn(sequence, its index in `which`)
     template <class Phase>
     void host(const std::vector<Sequence*>& which, double& sec, Phase fn) {
@@ -429,10 +539,12 @@ private:
         st.max_items = std::max(st.max_items, (int)items);
     }
 
-    StreamParams p_;
+    std::vector<StreamParams> ps_;   // one per sequence (fixed at construction: the sequences refer to their entry)
+    const StreamParams fallback_params_{};
+    const StreamParams& p_;          // ps_[0]: what the batched depth, five-point and selection calls take (equal in every entry)
     int host_threads_ = 1;
     lockstep_detail::HostPool pool_;  // (after host_threads_: built from it)
-    std::vector<std::unique_ptr<Sequence>> seqs_;  // (after p_: they refer to it)
+    std::vector<std::unique_ptr<Sequence>> seqs_;  // (after ps_: they refer to it)
     Pose T_cam_lidar_;
     limo_ctx* ctx_ = nullptr;
     limo_depth_params depth_params_;

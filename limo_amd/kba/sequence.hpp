@@ -49,6 +49,13 @@ struct StreamParams {
     double solver_time_sec = 20.;               // wall-clock cap of a solve; <= 0: none (deterministic)
     double prior_speed = 11.;                   // m/s along the vehicle's x axis while no motion has been estimated yet (the
                                                 // node scales its five-point direction by interface_.prior_speed, :160-165)
+    // outlier rejection of solve() and adjustPoseOnly() (keyframe_ba_monolid.launch:41-46; the node writes them into
+    // BundleAdjusterKeyframes::outlier_rejection_options_, and so does the sequence): the defaults are OutlierRejectionOptions' own.
+    // What the reference's tune_parameters_kitti.py sweeps.
+    double robust_loss_depth_thres = 0.16;        // Cauchy scale of the depth blocks
+    double robust_loss_reprojection_thres = 1.6;  // ... of the reprojection blocks
+    double outlier_rejection_quantile = 0.95;     // both quantiles of the trimming rounds
+    int outlier_rejection_num_iterations = 1;     // trimming rounds (part of the schedule)
     // Motion prior of a frame that comes without an external one (mono_lidar.cpp:157-186): the node takes the direction from
     // the five-point algorithm on the matches between the last keyframe and the frame and the length from the speed of the last
     // two keyframes (five_point.hpp restates it); constant velocity from the last two frame poses is this driver's default (no
@@ -126,6 +133,11 @@ auto timed(double& sec, F&& fn) -> decltype(fn()) {  // ... the time of fn()
 // the node's wiring of keyframe selection and landmark selection (mono_lidar.cpp:396-430) for one sequence's adjuster
 inline void configureSequence(const StreamParams& p, BundleAdjusterKeyframes& ba, KeyframeSelector& selector) {
     ba.set_solver_time(p.solver_time_sec);
+    ba.outlier_rejection_options_.depth_thres = p.robust_loss_depth_thres;
+    ba.outlier_rejection_options_.reprojection_thres = p.robust_loss_reprojection_thres;
+    ba.outlier_rejection_options_.depth_quantile = p.outlier_rejection_quantile;
+    ba.outlier_rejection_options_.reprojection_quantile = p.outlier_rejection_quantile;
+    ba.outlier_rejection_options_.num_iterations = p.outlier_rejection_num_iterations;
     selector.addScheme(KeyframeRejectionSchemeFlow::createConst(p.min_median_flow));
     selector.addScheme(KeyframeSelectionSchemePose::createConst(p.critical_rotation_difference));
     selector.addScheme(KeyframeSparsificationSchemeTime::createConst(p.time_between_keyframes_sec * 1e9));

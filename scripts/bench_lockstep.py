@@ -10,6 +10,10 @@ drive of this commit against the parent's, runs alternated, to show what the spl
   scripts/bench_lockstep.py --against-parent [--frames 200] [--repeats 3] [--out ...]   (on the GPU machine) for a change of the drivers'
                                                     host side when REV already has the lock-step driver: the parent's `--sequences N` too,
                                                     alternated with this commit's, and the single drives with both flag sets
+  scripts/bench_lockstep.py --sweep 16 [--frames 200] [--out ...]   (on the GPU machine) a sweep of 16 parameter sets - depth_thres x
+                                                    reprojection_thres, 4 x 4 of the reference's tune_parameters_kitti.py grid - over ONE world in
+                                                    lock step (`--sequences 16 --sweep FILE`: the file is written here), against the same 16
+                                                    drives of this commit's limo_stream run one after another with the parameters as flags
 
 The kernels are the same in both programs (this comparison is only fair while limo_amd/csrc is unchanged between REV and the work
 tree: --build-parent refuses otherwise).  Every process runs under its own time limit; a failing run ends the script.  The table goes to
@@ -75,6 +79,49 @@ def lockstep(exe, n, frames, flags, limit):
     return info
 
 
+def sweep_lines(n):
+    """n parameter sets: the corner of tune_parameters_kitti.py's grid (10 x 11 values of robust_loss_depth_thres x
+    robust_loss_reprojection_thres) this many sequences cover, row by row."""
+    depth = [0.04 * (i + 1) for i in range(10)]
+    repro = [0.4 * (i + 1) for i in range(11)]
+    side = max(1, int(round(n ** 0.5)))
+    return [(depth[(k // side) % 10], repro[(k % side) % 11]) for k in range(n)]
+
+
+def sweep(a):
+    """`--sequences N --sweep FILE` against the N single drives with flags, one after another: frames/s of both, the share of
+    batched bundle-adjustment calls that carried differing options, and the sweep's own result (parameters -> ATE)."""
+    if not os.path.exists(EXE):
+        sys.exit("%s is missing (build())" % EXE)
+    n = a.sweep
+    sets = sweep_lines(n)
+    with tempfile.NamedTemporaryFile("w", suffix=".sweep", delete=False) as f:
+        for d, r in sets:
+            f.write("depth_thres=%r reprojection_thres=%r\n" % (d, r))
+        path = f.name
+    try:
+        out, wall = run([EXE, "--sequences", str(n), "--frames", str(a.frames), "--az", "2000", "--seed", "7", "--quiet", "--sweep", path], a.limit)
+    finally:
+        os.unlink(path)
+    info = json.loads(out.strip().splitlines()[-1])
+    info["wall_s"] = wall
+    secs = [single(EXE, a.frames, 7, ["--depth-thres", repr(d), "--reprojection-thres", repr(r)], a.limit)[1] for d, r in sets]
+    base = n * a.frames / sum(secs)
+    st = info["stages"]
+    print("sweep of %d parameter sets, %d frames each: lock step %.1f frames/s (%.2f ms per tick) | %d single drives one after another %.1f frames/s | x %.2f" % (
+        n, a.frames, info["frames_per_s"], info["ms_pipeline"] / max(1, info["ticks"]), n, base, info["frames_per_s"] / base))
+    for name in ("pose_only", "solve"):
+        print("  %-9s %d batched calls (%d with an entry of options per window), most items %d, %d single-call fallbacks, %.2f ms per tick inside the C-ABI" % (
+            name, st[name]["batched_calls"], st[name]["per_window_calls"], st[name]["max_items"], st[name]["fallback_calls"], st[name]["ms_abi"] / max(1, info["ticks"])))
+    print("  depth_thres reprojection_thres  ATE rmse [m]")
+    for p in info["per_sequence"]:
+        print("  %11.2f %18.1f  %.4f" % (p["depth_thres"], p["reprojection_thres"], p["ate_rmse"]))
+    res = {"frames": a.frames, "sets": n, "lockstep": info, "single_pipeline_s": secs, "single_frames_per_s": base, "speedup": info["frames_per_s"] / base}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(res, open(a.out, "w"), indent=1)
+    print("wrote", a.out)
+
+
 def against_parent(a):
     """Host-side changes of the drivers, this commit against a parent that HAS the lock-step driver: per row the parent, the parent
     again and this commit, alternated, a.repeats runs each.  The two parent series are the same program: all their runs together give
@@ -110,6 +157,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--build-parent", metavar="REV")
     ap.add_argument("--against-parent", action="store_true", help="the single and the lock-step drive (N = 1, 16) of this commit against the parent's, alternated, with the box's spread")
+    ap.add_argument("--sweep", type=int, metavar="N", help="N parameter sets over one world in lock step against the N single drives with flags, one after another")
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--sizes", default="1,4,16,64")
     ap.add_argument("--repeats", type=int, default=3)
@@ -119,6 +167,8 @@ def main():
     a = ap.parse_args()
     if a.build_parent:
         return build_parent(a.build_parent)
+    if a.sweep:
+        return sweep(a)
     for exe in (EXE, PARENT):
         if not os.path.exists(exe):
             sys.exit("%s is missing (build(); scripts/bench_lockstep.py --build-parent REV)" % exe)
