@@ -7,7 +7,7 @@
 //
 //   limo_stream [--frames N] [--features N] [--az N] [--seed S] [--window K] [--poses out.txt] [--gt-poses gt.txt]
 //               [--dump-velodyne DIR] [--velodyne DIR] [--no-depth] [--depth-ahead thread|stream|none] [--quiet]
-//               [--depth-params FILE] [--progress] [--five-point-prior [--five-point-host | --five-point-device]]
+//               [--depth-params FILE] [--progress] [--covariance FILE] [--five-point-prior [--five-point-host | --five-point-device]]
 //               [--select-host | --select-device] [--depth-thres A] [--reprojection-thres A] [--outlier-quantile Q] [--shrubbery-weight W]
 //               [--sequences N [--frames-step K] [--stagger S] [--host-threads T] [--sweep FILE]]
 // --depth-thres / --reprojection-thres / --outlier-quantile / --shrubbery-weight set the outlier rejection of solve() and adjustPoseOnly()
@@ -28,6 +28,10 @@
 // estimator five_point.hpp, or limo_five_point) instead of StreamParams' default.  Same pose rows, bit for bit.
 // --select-host / --select-device say where solve() selects its landmarks (the host selector, or limo_landmark_select) instead of
 // StreamParams' default.  Same pose rows, bit for bit.
+// --covariance FILE writes one row per frame: the 36 numbers (row-major 6 x 6: rotation 3 | translation 3, the tangent units of
+// include/limo_hip.h, "Pose covariance") of the marginal covariance of the frame's adjustPoseOnly and its limo_cov_status; a frame that
+// was not refined (the first one) has zeros and LIMO_COV_NOT_COMPUTED, a frame before the first solve() - no landmark selected yet, nothing
+// constrains its pose - NaN and LIMO_COV_RANK_DEFICIENT.  With --sequences N: FILE.i per sequence.  No pose row changes.
 // --progress prints Ceres' per-iteration table for every adjustPoseOnly and solve to stdout, as the reference's node does
 // (BundleAdjusterKeyframes::minimizer_progress_to_stdout_); the pose rows do not change.
 // --depth-params reads the depth estimator's settings from a mono_lidar_fusion_parameters.yaml (the file the reference
@@ -159,7 +163,7 @@ struct LockstepOptions {
     int sequences = 0, frames_step = 0, stagger = 0, host_threads = 0, perturb_rig = -1, perturb_trim_rounds = -1;
     int n_frames = 200, n_feat = 1500, n_az = 2000;
     uint64_t seed = 7;
-    std::string poses_path, gt_path, depth_params_path, sweep_path;
+    std::string poses_path, gt_path, depth_params_path, sweep_path, covariance_path;
     bool quiet = false;
 };
 
@@ -314,6 +318,10 @@ int run_lockstep(const LockstepOptions& o, StreamParams sp) {
             std::ofstream f(o.poses_path + "." + std::to_string(i));
             driver->writeKittiTrajectory(i, f);
         }
+        if (!o.covariance_path.empty()) {
+            std::ofstream f(o.covariance_path + "." + std::to_string(i));
+            driver->writeCovariances(i, f);
+        }
         if (!o.gt_path.empty()) {
             std::ofstream f(o.gt_path + "." + std::to_string(i));
             const EigenPose cv = d.cam->getEigenPose();
@@ -357,7 +365,7 @@ int run_lockstep(const LockstepOptions& o, StreamParams sp) {
 int main(int argc, char** argv) {
     int n_frames = 200, n_feat = 1500, n_az = 2000, window = 5, misannounce_every = 0;
     uint64_t seed = 7;
-    std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path;
+    std::string poses_path, gt_path, dump_dir, replay_dir, depth_params_path, covariance_path;
     bool use_depth = true, quiet = false, five_point_prior = false, progress = false;
     int five_point_where = -1;  // 0: host, 1: device, -1: StreamParams' default
     int select_where = -1;      // landmark selection of solve(): the same
@@ -388,6 +396,7 @@ int main(int argc, char** argv) {
         else if (arg("--min-flow")) min_flow = std::atof(argv[++i]);
         else if (arg("--time-between-keyframes")) time_between_keyframes = std::atof(argv[++i]);
         else if (arg("--poses")) poses_path = argv[++i];
+        else if (arg("--covariance")) covariance_path = argv[++i];
         else if (arg("--gt-poses")) gt_path = argv[++i];
         else if (arg("--dump-velodyne")) dump_dir = argv[++i], single_only = true;
         else if (arg("--velodyne")) replay_dir = argv[++i], single_only = true;
@@ -438,13 +447,14 @@ int main(int argc, char** argv) {
     if (five_point_prior) sp.motion_prior = StreamParams::MotionPrior::FivePoint;
     if (five_point_where >= 0) sp.five_point_on_device = five_point_where == 1;
     if (select_where >= 0) sp.landmark_selection_on_device = select_where == 1;
+    sp.pose_covariance = !covariance_path.empty();
     sp.solver_time_sec = -1.;  // no wall-clock cap: the drive is reproducible
     sp.image_width = (int)world.W;
     sp.image_height = (int)world.H;
     sp.height_over_ground = synth_world::World::kHeightOverGround;
     if (in_lockstep) {  // (the depths of a tick are assigned inside the tick: --depth-ahead has nothing to run ahead of)
         lockstep.n_frames = n_frames, lockstep.n_feat = n_feat, lockstep.n_az = n_az, lockstep.seed = seed;
-        lockstep.poses_path = poses_path, lockstep.gt_path = gt_path, lockstep.depth_params_path = depth_params_path, lockstep.quiet = quiet;
+        lockstep.poses_path = poses_path, lockstep.covariance_path = covariance_path, lockstep.gt_path = gt_path, lockstep.depth_params_path = depth_params_path, lockstep.quiet = quiet;
         return run_lockstep(lockstep, sp);
     }
     StreamDriver driver(sp, cam, world.cam_lidar);
@@ -516,6 +526,10 @@ int main(int argc, char** argv) {
     if (!poses_path.empty()) {
         std::ofstream f(poses_path);
         driver.writeKittiTrajectory(f);
+    }
+    if (!covariance_path.empty()) {
+        std::ofstream f(covariance_path);
+        driver.writeCovariances(f);
     }
     // devkit-style relative errors on the KITTI pose rows (camera frame)
     std::vector<EigenPose> gt_rows, est_rows;

@@ -336,6 +336,49 @@ int limo_ba_batch_iteration_log(limo_ba_batch* batch, int32_t window, int32_t ca
 int limo_ctx_last_iteration_log(limo_ctx* ctx, int32_t window, int32_t cap, limo_ba_iteration* out, int32_t* n);
 
 /*
+ * Pose covariance: how well a solve determines its poses - what ceres::Covariance::GetCovarianceBlockInTangentSpace gives for the
+ * pose blocks of the problem that has just been solved.  Off by default; switching it on changes no result of a solve.
+ * DEFINITION.  For one window, after a solve, J is the Jacobian of the FINAL problem: the problem built at the solve's x0, minus
+ * the residual blocks of the landmarks the trimming rounds removed, constant parameter blocks excluded (Ceres' reduced program),
+ * evaluated at the final point, robustified (sqrt(rho') folded in, as in every linearisation of the solve), with respect to the
+ * tangent parameters of the solve:
+ *   rotation 3      delta with q (+) delta = [cos|delta|, sin|delta| delta / |delta|] * q - LEFT-multiplied, rotation ANGLE 2 |delta|:
+ *                   a covariance in rotation-vector units is 4 x the rotation-rotation block, 2 x the rotation-translation blocks
+ *   translation 3, plane normal 3 (ambient, rank-2 Jacobian), plane distance 1, landmarks 3.
+ * The result is the pose-pose block of the generalised inverse of J^T J (landmarks, plane normals and plane distances marginalised).
+ * OUTPUT per window: a dense symmetric [6 n_kf][6 n_kf] row-major matrix in the caller's keyframe order, rotation 3 | translation 3
+ * per keyframe; rows and columns of keyframes without a free pose block are zero.  An entry and its mirror image are equal bit for
+ * bit.  A status per window:
+ *   LIMO_COV_OK              the covariance was computed
+ *   LIMO_COV_RANK_DEFICIENT  the undamped system is rank deficient beyond the plane normals' own null directions (a free gauge, a
+ *                            free keyframe that nothing observes): a Cholesky pivot fell to 2^-26 of its slot's diagonal entry
+ *   LIMO_COV_NO_FREE_POSE    the window has no free pose block
+ *   LIMO_COV_EVAL_FAILED     the linearisation at the final point failed, or a landmark block did not factor without damping
+ *   LIMO_COV_NOT_COMPUTED    the switch was off, or the solve was limo_ba_solve_sharded
+ * The matrix is all NaN for every computed status but OK and NO_FREE_POSE, and all zero for NO_FREE_POSE; NOT_COMPUTED has none.
+ * COST.  One more linearisation, Schur complement and dense factorisation per window at the end of the solve (six to eight launches), the
+ * LM state saved and restored around them: parameters, report, iteration log and trimmed flags of the solve, and every later solve
+ * of the batch, are the bytes of a run with the switch off.  With the switch off nothing is launched or allocated.
+ */
+enum limo_cov_status {
+    LIMO_COV_OK = 0,
+    LIMO_COV_RANK_DEFICIENT = 1,
+    LIMO_COV_NO_FREE_POSE = 2,
+    LIMO_COV_EVAL_FAILED = 3,
+    LIMO_COV_NOT_COMPUTED = 4
+};
+/* The switch belongs to the context and is read by every solve on it (limo_ba_batch_solve / _solve_each, and through them
+ * limo_ba_solve, limo_ba_solve_fixed_landmarks, limo_ba_adjust_pose_only and its batch forms), on any launch path.  Storage -
+ * sum over the windows of (6 n_kf)^2 doubles - comes from the context's pool at the batch's first solve with the switch on. */
+int limo_ctx_set_pose_covariance(limo_ctx* ctx, int32_t on);
+/* The matrix of window `window` of a resident batch after its last solve: (6 n_kf)^2 doubles into `out` (cap_doubles: the room
+ * there; too little is LIMO_ERR_INVALID) and its status.  out == NULL with cap_doubles == 0 asks for the status alone.
+ * LIMO_COV_NOT_COMPUTED writes nothing. */
+int limo_ba_batch_pose_covariance(limo_ba_batch* batch, int32_t window, int64_t cap_doubles, double* out, int32_t* status);
+/* The same for the calls that make and destroy their own batch: window `window` of the last such call on the context. */
+int limo_ctx_last_pose_covariance(limo_ctx* ctx, int32_t window, int64_t cap_doubles, double* out, int32_t* status);
+
+/*
  * Evaluate the reprojection / depth residual blocks of a window at its current parameters
  * (Problem::Evaluate semantics).  Outputs are per observation in the caller's observation order; rows
  * 0,1 = reprojection (u,v), row 2 = depth (zero when the observation has no depth):

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("LIMO_HIP_LIB") or os.path.join(_HERE, "lib", "liblimo
 LIMO_FIX_POSE, LIMO_FIX_SCALE, LIMO_FIX_NONE = 0, 1, 2
 LIMO_OK, LIMO_ERR_INVALID, LIMO_ERR_NOT_ENOUGH_KF, LIMO_ERR_RUNTIME, LIMO_ERR_NO_DEVICE, LIMO_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 LIMO_CONVERGENCE, LIMO_NO_CONVERGENCE, LIMO_FAILURE = 0, 1, 2
+LIMO_COV_OK, LIMO_COV_RANK_DEFICIENT, LIMO_COV_NO_FREE_POSE, LIMO_COV_EVAL_FAILED, LIMO_COV_NOT_COMPUTED = range(5)  # enum limo_cov_status
 
 c_double_p = C.POINTER(C.c_double)
 c_float_p = C.POINTER(C.c_float)
@@ -382,6 +383,9 @@ ABI_SYMBOLS = [
     "limo_ctx_set_iteration_log",
     "limo_ba_batch_iteration_log",
     "limo_ctx_last_iteration_log",
+    "limo_ctx_set_pose_covariance",
+    "limo_ba_batch_pose_covariance",
+    "limo_ctx_last_pose_covariance",
     "limo_ba_evaluate",
     "limo_ba_evaluate_batch_time",
     "limo_ba_evaluate_rows",
@@ -532,6 +536,10 @@ def load():
         lib.limo_ctx_set_iteration_log.argtypes = [vp, C.c_int32]
         lib.limo_ba_batch_iteration_log.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(BaIteration), c_int32_p]
         lib.limo_ctx_last_iteration_log.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(BaIteration), c_int32_p]
+    if hasattr(lib, "limo_ctx_set_pose_covariance"):  # (added without an ABI bump, as the ones above)
+        lib.limo_ctx_set_pose_covariance.argtypes = [vp, C.c_int32]
+        lib.limo_ba_batch_pose_covariance.argtypes = [vp, C.c_int32, C.c_int64, c_double_p, c_int32_p]
+        lib.limo_ctx_last_pose_covariance.argtypes = [vp, C.c_int32, C.c_int64, c_double_p, c_int32_p]
     lib.limo_depth_set_timing.argtypes = [vp, C.c_int32]
     lib.limo_depth_last_kernel_ms.argtypes = [vp, c_double_p]
     lib.limo_depth_last_ground_plane.argtypes = [vp, C.c_int32, c_double_p, c_int32_p]

@@ -34,6 +34,7 @@ class Context:
     def __init__(self, device=0, stream=None):
         self.lib = _ffi.load()
         self.device = device
+        self._last_n_kf = []  # keyframes of the windows of the last call that owned its batch (last_pose_covariance)
         self.ptr = C.c_void_p()
         rc = self.lib.limo_ctx_create(device, C.byref(self.ptr))
         if rc != 0:
@@ -60,6 +61,7 @@ class Context:
         """limo_ba_solve; lm_fixed (one flag per landmark, non-zero = constant parameter block): limo_ba_solve_fixed_landmarks."""
         s = window.as_struct()
         rep = _ffi.BaReport()
+        self._last_n_kf = [window.n_kf]
         if lm_fixed is not None:
             flags = fixed_flags(lm_fixed, window.n_lm)
             rc = self.lib.limo_ba_solve_fixed_landmarks(self.ptr, C.byref(s), flags.ctypes.data_as(_ffi.c_uint8_p), C.byref(opts), C.byref(rep))
@@ -73,6 +75,7 @@ class Context:
         n_shards virtual shards on this GPU when there is none."""
         s = window.as_struct()
         rep = _ffi.BaReport()
+        self._last_n_kf = [window.n_kf]
         _check(self.lib.limo_ba_solve_sharded(self.ptr, C.byref(s), C.byref(opts), int(n_shards), C.byref(rep)), self.ptr, "limo_ba_solve_sharded")
         return rep.as_dict()
 
@@ -122,6 +125,19 @@ class Context:
         context, as a numpy array of _ffi.iteration_dtype() (empty with the switch off)."""
         return _read_iteration_log(lambda cap, out, n: self.lib.limo_ctx_last_iteration_log(self.ptr, int(window), cap, out, n), self.ptr,
                                    "limo_ctx_last_iteration_log")
+
+    def set_pose_covariance(self, on):
+        """limo_ctx_set_pose_covariance: every solve on this context ends with the marginal pose covariance of its windows (off by
+        default; changes no result of a solve)."""
+        _check(self.lib.limo_ctx_set_pose_covariance(self.ptr, int(bool(on))), self.ptr, "limo_ctx_set_pose_covariance")
+
+    def last_pose_covariance(self, window=0):
+        """limo_ctx_last_pose_covariance: (matrix [6 n_kf, 6 n_kf] or None, status) of window `window` of the last solve /
+        adjust_pose_only[_batch] call on this context (the context remembers the keyframe counts of that call's windows).  The matrix
+        is None for LIMO_COV_NOT_COMPUTED.  Tangent units: include/limo_hip.h, "Pose covariance"."""
+        n_kf = self._last_n_kf[window] if 0 <= window < len(self._last_n_kf) else 1
+        return _read_pose_covariance(lambda cap, out, st: self.lib.limo_ctx_last_pose_covariance(self.ptr, int(window), cap, out, st), n_kf, self.ptr,
+                                     "limo_ctx_last_pose_covariance")
 
     def comm_init(self, unique_id, rank, world):
         _check(self.lib.limo_ctx_comm_init(self.ptr, unique_id, int(rank), int(world)), self.ptr, "limo_ctx_comm_init")
@@ -258,6 +274,7 @@ class Context:
     def adjust_pose_only(self, window, prior, opts):
         s = window.as_struct()
         rep = _ffi.BaReport()
+        self._last_n_kf = [window.n_kf]
         rc = self.lib.limo_ba_adjust_pose_only(self.ptr, C.byref(s), None if prior is None else C.byref(prior), C.byref(opts), C.byref(rep))
         _check(rc, self.ptr, "limo_ba_adjust_pose_only")
         return rep.as_dict()
@@ -269,6 +286,7 @@ class Context:
         windows = list(windows)
         arr = struct_array(windows)
         reps = (_ffi.BaReport * max(1, len(windows)))()
+        self._last_n_kf = [w.n_kf for w in windows]
         if not isinstance(opts, _ffi.BaOptions):  # a sequence: one set of options per window (limo_ba_adjust_pose_only_batch_each)
             each, n_each = options_array(opts)
             if n_each != len(windows):
@@ -315,6 +333,17 @@ def _read_iteration_log(call, ctx_ptr, what):
         _check(call(n.value, out.ctypes.data_as(C.POINTER(_ffi.BaIteration)), C.byref(n)), ctx_ptr, what)
         assert n.value == out.size
     return out
+
+
+def _read_pose_covariance(call, n_kf, ctx_ptr, what):
+    """Both readers of the pose covariance: the status first, then the matrix."""
+    st = C.c_int32(_ffi.LIMO_COV_NOT_COMPUTED)
+    _check(call(0, None, C.byref(st)), ctx_ptr, what)
+    if st.value == _ffi.LIMO_COV_NOT_COMPUTED:
+        return None, st.value
+    out = np.zeros((6 * n_kf, 6 * n_kf))
+    _check(call(out.size, out.ctypes.data_as(_ffi.c_double_p), C.byref(st)), ctx_ptr, what)
+    return out, st.value
 
 
 def fixed_flags(lm_fixed, n_lm):
@@ -411,6 +440,12 @@ class Batch:
         _ffi.iteration_dtype() (empty when the context's switch was off)."""
         return _read_iteration_log(lambda cap, out, n: self.lib.limo_ba_batch_iteration_log(self.ptr, int(w), cap, out, n), self.ctx.ptr,
                                    "limo_ba_batch_iteration_log")
+
+    def pose_covariance(self, w=0):
+        """limo_ba_batch_pose_covariance: (matrix [6 n_kf, 6 n_kf] or None, status) of window w after the last solve of this batch
+        (None, LIMO_COV_NOT_COMPUTED when the context's switch was off)."""
+        return _read_pose_covariance(lambda cap, out, st: self.lib.limo_ba_batch_pose_covariance(self.ptr, int(w), cap, out, st), self.windows[w].n_kf,
+                                     self.ctx.ptr, "limo_ba_batch_pose_covariance")
 
     def kernel_stats(self, reset=False):
         ms = C.c_double()

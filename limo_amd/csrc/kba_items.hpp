@@ -2166,6 +2166,166 @@ KBA_HD void cam_solve(const BatchView& bv, const SolveConsts& c, int w, int tid,
     KBA_TICK(13);
 }
 
+// ======================================================================================= marginal pose covariance
+// cam_cov (limo_hip.h, "Pose covariance"): the pose-pose block of the generalised inverse of J^T J of one window, from the UNDAMPED
+// Schur complement onto its free camera slots.  Runs behind cam_assemble and the Schur waves of a linearisation at the final point
+// whose SolveConsts carry min_lm_diagonal = max_lm_diagonal = 0: every damping term of the train is then an exact zero
+// (lm_damp_store, and the clamp below would be), and the hand-over and the slabs hold S_c H S_c and sum Y' Y'^T as cam_solve reads them.
+//   1. [S], assembled as cam_solve does (same enumeration, slab skip, packed layouts, order of the sum; no rhs, no damping) - but with
+//      the compact slots in REVERSE order, plane slots first: eliminating from the front leaves the pose slots for last;
+//   2. a free plane normal has three tangent slots and the rank-2 Jacobian (I - n n^T) / |n|: S is singular along n / scale in them.
+//      mu w w^T is added to the normal's diagonal block, w the unit vector along that direction, mu the block's largest diagonal
+//      entry; the pose block of the inverse is that of the generalised inverse for any multiple of any w with a component along
+//      the null vector;
+//   3. right-looking Cholesky of the upper triangle, one barrier per pivot (cam_solve's loop; the device takes it as well, so that
+//      the emulator runs the kernel's statements).  RANK TEST: a pivot <= 2^-26 times the slot's diagonal entry before the
+//      elimination (below that the inverse keeps fewer than eight digits) declares the window rank deficient;
+//   4. the trailing nfq x nfq block U_t of the factor is the factor of the Schur complement onto the pose slots:
+//      M = U_t^-1 U_t^-T, a lane per column of U_t^-1, then a lane per entry of M;
+//   5. cov = diag(s) M diag(s) on the pose slots (the Jacobi scale undone), scattered to rows 6 k + j of the caller's keyframe k;
+//      an entry and its mirror image are ONE value stored twice.  Rows and columns of keyframes without a free pose block: zero.
+// status: LIMO_COV_*; any status but OK leaves NaN in every entry, NO_FREE_POSE zeros.
+// scratch: A (nf x nf) | d0 (nf) | X (nfq x nfq) | compact -> slot (nf ints): cam_cov_scratch.
+constexpr double kCovRankRatio = 1.0 / 67108864.0;  // 2^-26 = sqrt(machine epsilon)
+KBA_HD int cam_cov_scratch(int nf, int nfq) { return nf * nf + nf + nfq * nfq + (nf + 1) / 2; }
+KBA_HD void cam_cov(const BatchView& bv, const SolveConsts& c, int w, int tid, int nt, double* scratch, double* out, int32_t* status) {
+    const WinDesc& wd = bv.win[w];
+    const int nc = wd.nc, nf = wd.nf, nfp = wd.nf_pad, nfq = wd.nfq, lda = nf, n6 = 6 * wd.n_kf, t0 = nf - nfq;
+    double* A = scratch;
+    double* d0 = A + nf * nf;
+    double* X = d0 + nf;
+    int* inv = reinterpret_cast<int*>(X + nfq * nfq);
+    const double* sc = bv.scale_c + wd.cam0;
+    const int32_t* cs = bv.cslot + wd.cam0;
+    const uint8_t* cm = bv.cmask + (int64_t)wd.cam0;
+    auto fill = [&](double v, int32_t st) {
+        for (int i = tid; i < n6 * n6; i += nt) out[i] = v;
+        if (tid == 0) *status = st;
+    };
+    if (nfq == 0) {
+        fill(0.0, LIMO_COV_NO_FREE_POSE);
+        return;
+    }
+    {   // the linearisation failed, or a landmark block did not factor without damping (uniform: every lane reads the same words)
+        bool bad = bv.red[w].lin_fail != 0;
+        for (int b = wd.lblk0; b < wd.lblk0 + wd.n_lblk; ++b) bad = bad || bv.lblk_part[(int64_t)b * 8 + 5] != 0.0;
+        if (bad) {
+            fill(nan(""), LIMO_COV_EVAL_FAILED);
+            return;
+        }
+    }
+    for (int i = tid; i < n6 * n6; i += nt) out[i] = 0.0;
+    for (int a = tid; a < nc; a += nt)
+        if (cs[a] >= 0) inv[cs[a]] = a;
+    // ---- (1) [S] = S_c H S_c - sum slabs, upper triangle of the reversed numbering: entry (ca, cb) at A[nf-1-cb][nf-1-ca]
+    {
+        const double* Hg = bv.Hcc + wd.hcc_off;
+        const int slab = c.schur_packed ? schur_need_pad(nf) : nfp * nfp;
+        const double* sp = c.schur_nslab > 0 ? bv.S_red + wd.sred_off : bv.S_part + wd.spart_off;
+        const int n_need = nf * (nf + 1) / 2 + nf;
+        const int n_slab = c.schur_nslab > 0 ? c.schur_nslab : schur_slabs(wd, c.schur_span, c.schur_span_gp);
+        const int q_gp = c.schur_nslab > 0 ? 0 : (schur_plain_slabs(wd, c.schur_span) & ~3);
+        const bool pk = c.slab_packed && wd.schur_fast && c.schur_nslab == 0;
+        const int n_pk = pk ? schur_plain_slabs(wd, c.schur_span) : 0;
+        const int64_t stride_pl = pk ? schur_need_pad(nfq) : 0, stride_gp = pk ? schur_need_pad(nf) : slab;
+        for (int i = tid; i < n_need; i += nt) {
+            int ca, cb;
+            schur_need_decode(i, nf, ca, cb);
+            if (cb >= nf) continue;  // (the rhs column: no part of the covariance)
+            const double s_e = Hg[i];
+            const int off = (c.schur_packed || pk) ? i : (int)schur_need_offset(ca, cb, nf, nfq, nfp);
+            const int off_pl = pk ? slab_packed_read(false, ca, cb, nf, nfq) : -1;
+            const int qs = (ca >= nfq || cb >= nfq) ? q_gp : 0;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};  // (per entry the order of the sum is q mod 4, as in cam_solve)
+            for (int q = qs; q < n_slab; ++q) {
+                const bool plain = q < n_pk;
+                const int o = plain ? off_pl : off;
+                if (o < 0) continue;  // (a packed plain slab holds no entry that involves a plane slot)
+                const int64_t base = plain ? (int64_t)q * stride_pl : n_pk * stride_pl + (int64_t)(q - n_pk) * stride_gp;
+                acc[q < (n_slab & ~3) ? (q & 3) : 0] += sp[base + o];
+            }
+            A[(nf - 1 - cb) * lda + (nf - 1 - ca)] = s_e - ((acc[0] + acc[1]) + (acc[2] + acc[3]));
+        }
+    }
+    KBA_SYNC();
+    // ---- (2) the null direction of every free plane normal
+    for (int k = tid; k < wd.n_kf; k += nt) {
+        const int a0 = k * kCamSlots + 6;
+        if (!cm[a0]) continue;
+        const double* n = bv.pdir + 3 * (int64_t)(wd.kf0 + k);
+        double wv[3] = {n[0] / sc[a0], n[1] / sc[a0 + 1], n[2] / sc[a0 + 2]};
+        const double len = sqrt(wv[0] * wv[0] + wv[1] * wv[1] + wv[2] * wv[2]);
+        for (int i = 0; i < 3; ++i) wv[i] /= len;
+        // (times the largest diagonal entry of the normal's block: the term has the block's own magnitude in any units - without the
+        // Jacobi scale the block is not O(1), and a unit term would fall under the rank test's ratio next to a large one)
+        double mu = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            const int r = nf - 1 - cs[a0 + i];
+            mu = fmax(mu, A[r * lda + r]);
+        }
+        if (!(mu > 0.0)) mu = 1.0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = i; j < 3; ++j) {
+                const int ra = nf - 1 - cs[a0 + i], rb = nf - 1 - cs[a0 + j];  // (cs ascends with the slot: rb <= ra)
+                A[(rb < ra ? rb : ra) * lda + (rb < ra ? ra : rb)] += mu * (wv[i] * wv[j]);
+            }
+    }
+    KBA_SYNC();
+    for (int i = tid; i < nf; i += nt) d0[i] = A[i * lda + i];
+    KBA_SYNC();
+    // ---- (3) A = U^T U with the rank test
+    const int tw = nt >= 16 ? 16 : 1, th = nt / tw, tx = tid % tw, ty = tid / tw;
+    bool deficient = false;
+    for (int k = 0; k < nf; ++k) {
+        const double d = A[k * lda + k];
+        if (!(d > kCovRankRatio * d0[k])) {
+            deficient = true;  // uniform: every lane reads the same pivot
+            break;
+        }
+        const double inv_d = 1.0 / d;
+        for (int i = k + 1 + ty; i < nf; i += th) {
+            const double aki = A[k * lda + i] * inv_d;
+            for (int j = i + tx; j < nf; j += tw) A[i * lda + j] -= aki * A[k * lda + j];
+        }
+        KBA_SYNC();
+    }
+    if (deficient) {
+        KBA_SYNC();  // (the zeros above are stored before the NaN)
+        fill(nan(""), LIMO_COV_RANK_DEFICIENT);
+        return;
+    }
+    // ---- (4) U_t = rows t0 .. nf - 1 divided by the roots of their pivots; X = U_t^-1 (upper), column by column
+    for (int k = t0 + tid; k < nf; k += nt) d0[k] = sqrt(A[k * lda + k]);
+    KBA_SYNC();
+    for (int k = t0 + ty; k < nf; k += th) {
+        const double dp = d0[k];
+        for (int j = k + tx; j < nf; j += tw) A[k * lda + j] = j == k ? dp : A[k * lda + j] / dp;
+    }
+    KBA_SYNC();
+    for (int j = tid; j < nfq; j += nt) {
+        X[j * nfq + j] = 1.0 / A[(t0 + j) * lda + t0 + j];
+        for (int i = j - 1; i >= 0; --i) {
+            double s = 0.0;
+            for (int k = i + 1; k <= j; ++k) s += A[(t0 + i) * lda + t0 + k] * X[k * nfq + j];
+            X[i * nfq + j] = -s / A[(t0 + i) * lda + t0 + i];
+        }
+    }
+    KBA_SYNC();
+    // ---- (5) M = X X^T, scale undone, scattered: trailing index t is compact slot nfq - 1 - t
+    for (int e = tid; e < nfq * nfq; e += nt) {
+        const int ta = e / nfq, tb = e % nfq;
+        if (tb < ta) continue;
+        double m = 0.0;
+        for (int k = tb; k < nfq; ++k) m += X[ta * nfq + k] * X[tb * nfq + k];
+        const int a = inv[nfq - 1 - ta], b = inv[nfq - 1 - tb];
+        const int ra = 6 * (a / kCamSlots) + a % kCamSlots, rb = 6 * (b / kCamSlots) + b % kCamSlots;
+        const double v = sc[a] * m * sc[b];
+        out[ra * n6 + rb] = v;
+        out[rb * n6 + ra] = v;
+    }
+    if (tid == 0) *status = LIMO_COV_OK;
+}
+
 
 // After backsub + candidate cost kernels: fold the landmark / observation partials into WinRed (workgroup, red[nt]).
 // n_work: the lanes that take entries (the first n_work of the nt lanes that meet in the reduction; default all).  The

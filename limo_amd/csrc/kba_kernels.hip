@@ -1431,6 +1431,40 @@ __global__ __launch_bounds__(NT) void k_cam_solve(BatchView bv, SolveConsts c, c
 #endif
 }
 
+// ------------------------------------------------------------------------------------------ pose covariance (kba_items.hpp:cam_cov)
+// The covariance pass of a batch (limo_batch.hpp:PoseCovariance::run) linearises every window once more at its final point with
+// the existing train.  k_cov_begin arms the windows for it - the host has saved the LM state and puts it back afterwards: the
+// first linearisation of a solve (Jacobi scale, current landmarks), no log, a finite radius (the damping terms are zero through
+// the clamp bounds of the pass's SolveConsts, whatever the radius).
+__global__ void k_cov_begin(BatchView bv) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= bv.n_win) return;
+    WinState& s = bv.st[w];
+    s.active = 1;
+    s.need_lin = 1;
+    s.first = 1;
+    s.accept = 0;
+    s.compute_scale = 1;
+    s.redamp = 0;
+    s.radius = 1.0;
+    s.iter = 0;  // (with the pass's tolerances lm_decide_lin ends no window that linearised: the Schur waves skip an inactive one)
+    s.max_iter = 1 << 30;
+    s.log = nullptr;
+    s.log_cap = 0;
+}
+// One workgroup per window.  scr_off[w] >= 0: the window's scratch (cam_cov_scratch) does not fit the launch's LDS and lies at that
+// offset of gscratch.  cov_off[w]: the window's matrix in cov.
+__global__ __launch_bounds__(kBlock) void k_cam_cov(BatchView bv, SolveConsts c, double* cov, const int64_t* cov_off, const int64_t* scr_off, double* gscratch,
+                                                    int32_t* status) {
+    const int w = blockIdx.x;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int64_t so = scr_off[w];  // (two calls: see k_cam_assemble)
+    if (so >= 0)
+        cam_cov(bv, c, w, threadIdx.x, kBlock, gscratch + so, cov + cov_off[w], status + w);
+    else
+        cam_cov(bv, c, w, threadIdx.x, kBlock, smem, cov + cov_off[w], status + w);
+}
+
 __global__ __launch_bounds__(64) void k_step_decide(BatchView bv, SolveConsts c, const int32_t* wl) {
     const int w = wl_at(bv, wl, blockIdx.x);
     if (w < 0) return;

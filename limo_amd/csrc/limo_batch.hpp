@@ -6,6 +6,7 @@
 //   stream  StreamSolve    slot groups, their streams and scheduler words                              limo_batch_stream.hpp
 //   one     OneLaunch      k_solve_wg / k_solve_coop and the recovery of a barrier timeout             limo_batch_onelaunch.hpp
 //   log     IterationLog   the per-window iteration log                                                 (this file)
+//   cov     PoseCovariance the covariance pass behind a solve, its storage                              (this file)
 //   timers  KernelTimers   event pairs around timed kernels, the clock of a solve                      (this file)
 // Every struct declares all its data first, grouped by lifetime.  Included by limo_hip.hip alone (behind kba_kernels.hip and
 // `using namespace kba`), which keeps the C ABI.
@@ -204,6 +205,34 @@ struct IterationLog {
     int export_to_ctx();
 };
 
+// ---- marginal pose covariance (limo_hip.h, "Pose covariance"; kba_items.hpp:cam_cov).  With the context's switch on every solve of
+// the batch ends with run(): the LM state is saved, the lock-step train linearises every window once more at its final point with
+// both clamp bounds of the damping at zero (k_view_consts, k_lin_lm, k_cam_assemble, the Schur launch over the full worklists, with
+// the solve's own loss scales), k_cam_cov factors the undamped Schur complement, and the LM state is put back.  Everything else
+// the train writes is scratch that the next linearisation of a solve writes again before it reads it.
+struct PoseCovariance {
+    limo_ba_batch& b;
+    // ---- across solves: made by the first solve with the switch on (ensure)
+    double* d_cov = nullptr;        // the windows' [6 n_kf]^2 matrices, back to back
+    int32_t* d_status = nullptr;    // [n_win] LIMO_COV_*
+    int64_t *d_cov_off = nullptr, *d_scr_off = nullptr;
+    double* d_scratch = nullptr;    // cam_cov's scratch of the windows too large for LDS
+    WinState* d_st_save = nullptr;
+    WinRed* d_red_save = nullptr;
+    std::vector<int64_t> cov_off;   // [n_win + 1]
+    int lds_bytes = 0;
+    bool ready = false;             // ensure() has made all of the above
+    bool offered = true;            // false: the batch of a call that reports no covariance (limo_ba_solve_sharded) - no pass
+    // ---- per solve
+    bool computed = false;          // the last solve of the batch ended with the pass
+
+    explicit PoseCovariance(limo_ba_batch& batch) : b(batch) {}
+    int ensure();
+    int run();
+    int read(int w, int64_t cap, double* out, int32_t* status);
+    int export_to_ctx();
+};
+
 // ---- kernel timing (linearisation, Schur) via HIP events on the stream of the launch, and the clock of a whole solve
 struct KernelTimers {
     limo_ba_batch& b;
@@ -272,6 +301,7 @@ struct limo_ba_batch {
     StreamSolve stream{*this};
     OneLaunch one{*this};
     IterationLog log{*this};
+    PoseCovariance cov{*this};
     KernelTimers timers{*this};
 
     limo_ba_batch() = default;
@@ -752,6 +782,123 @@ inline int IterationLog::export_to_ctx() {
         if (ctx->last_log_n[w])
             HIP_TRY(ctx, hipMemcpyAsync(ctx->last_log.data() + ctx->last_log_off[w], d_log + (size_t)w * log_cap,
                                         sizeof(limo_ba_iteration) * ctx->last_log_n[w], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return LIMO_OK;
+}
+
+// =============================================================================================== PoseCovariance
+inline int PoseCovariance::ensure() {
+    if (ready) return LIMO_OK;
+    limo_ctx* ctx = b.ctx;
+    const PackedBatch& P = b.P;
+    cov_off.assign(P.n_win + 1, 0);
+    std::vector<int64_t> scr_off(std::max(1, P.n_win), -1);
+    int64_t scr_total = 0;
+    lds_bytes = 0;
+    for (int w = 0; w < P.n_win; ++w) {
+        const WinDesc& d = P.win[w];
+        cov_off[w + 1] = cov_off[w] + (int64_t)36 * d.n_kf * d.n_kf;
+        const int doubles = cam_cov_scratch(d.nf, d.nfq), bytes = doubles * (int)sizeof(double);
+        if (bytes > kCamLdsCapBytes) {
+            scr_off[w] = scr_total;
+            scr_total += doubles;
+        } else {
+            lds_bytes = std::max(lds_bytes, bytes);
+        }
+    }
+    if (b.dmalloc((void**)&d_cov, sizeof(double) * (size_t)std::max<int64_t>(1, cov_off[P.n_win]))) return LIMO_ERR_RUNTIME;
+    if (b.dmalloc((void**)&d_status, sizeof(int32_t) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+    if (b.dmalloc((void**)&d_cov_off, sizeof(int64_t) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+    if (b.dmalloc((void**)&d_scr_off, sizeof(int64_t) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+    if (b.dmalloc((void**)&d_scratch, sizeof(double) * (size_t)std::max<int64_t>(1, scr_total))) return LIMO_ERR_RUNTIME;
+    if (b.dmalloc((void**)&d_st_save, sizeof(WinState) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+    if (b.dmalloc((void**)&d_red_save, sizeof(WinRed) * std::max(1, P.n_win))) return LIMO_ERR_RUNTIME;
+    if (P.n_win) {  // (synchronous copies: the host vectors are this call's)
+        HIP_TRY(ctx, hipMemcpy(d_cov_off, cov_off.data(), sizeof(int64_t) * P.n_win, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_scr_off, scr_off.data(), sizeof(int64_t) * P.n_win, hipMemcpyHostToDevice));
+    }
+    ready = true;
+    return LIMO_OK;
+}
+
+// The pass, on the context's stream behind the solve's last launch.  Not offered for a landmark-sharded batch.
+inline int PoseCovariance::run() {
+    limo_ctx* ctx = b.ctx;
+    const PackedBatch& P = b.P;
+    hipStream_t s = ctx->stream;
+    computed = false;
+    if (b.shards.n_shards > 1 || !offered || !P.n_win) return LIMO_OK;
+    if (ensure() != LIMO_OK) return LIMO_ERR_RUNTIME;
+    {   // the kernel's dynamic LDS limit belongs to the process, not to the batch: only ever raised
+        static std::atomic<int> lds_limit{0};
+        if (lds_bytes > lds_limit.load()) {
+            HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_cam_cov, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+            lds_limit.store(lds_bytes);
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_st_save, b.bv.st, sizeof(WinState) * P.n_win, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_red_save, b.bv.red, sizeof(WinRed) * P.n_win, hipMemcpyDeviceToDevice, s));
+    const SolveConsts keep = b.c;
+    b.c.min_lm_diagonal = 0.0;  // clamp(a, 0, 0) = 0: lm_damp_store adds an exact zero for any finite radius
+    b.c.max_lm_diagonal = 0.0;
+    b.c.gradient_tolerance = -1.0;  // the decision behind the linearisation (lm_decide_lin) keeps every window active for the Schur waves
+    b.c.min_radius = -1.0;
+    b.lock.full_lists();
+    const WorkLists& l = b.lock.wl[0].cur;
+    hipLaunchKernelGGL(k_cov_begin, dim3(cdiv(P.n_win, 256)), dim3(256), 0, s, b.bv);
+    b.launch_check("k_cov_begin");
+    if (P.TV) {
+        hipLaunchKernelGGL(k_view_consts, dim3(cdiv(P.TV, 256)), dim3(256), 0, s, b.bv);
+        b.launch_check("k_view_consts");
+    }
+    if (l.n_lblk) {
+        b.launch_lin_lm(l.n_lblk, s, b.bv, l.lblk);
+        b.launch_check("k_lin_lm");
+    }
+    {
+        BatchView bvs = b.bv;  // (the words of LockStep::assemble's slot 0: the next solve writes them before it reads them)
+        bvs.n_active_host = b.d_pin->active;
+        b.launch_cam_assemble(bvs, l.win, l.n_win, s);
+        b.launch_check("k_cam_assemble");
+    }
+    if (l.n_sblk) {
+        if (b.c.slab_packed) b.spart_has_packed = true;
+        b.launch_schur(b.bv, l.sblk, l.n_sblk_plain, l.sblk + l.n_sblk_plain, l.n_sblk_fgp, l.sblk + l.n_sblk_plain + l.n_sblk_fgp,
+                       l.n_sblk - l.n_sblk_plain - l.n_sblk_fgp, false, s);
+        b.launch_check("Schur kernels");
+    }
+    hipLaunchKernelGGL(k_cam_cov, dim3(P.n_win), dim3(kBlock), lds_bytes, s, b.bv, b.c, d_cov, (const int64_t*)d_cov_off, (const int64_t*)d_scr_off, d_scratch, d_status);
+    b.launch_check("k_cam_cov");
+    b.c = keep;
+    HIP_TRY(ctx, hipMemcpyAsync(b.bv.st, d_st_save, sizeof(WinState) * P.n_win, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(b.bv.red, d_red_save, sizeof(WinRed) * P.n_win, hipMemcpyDeviceToDevice, s));
+    computed = b.rc == LIMO_OK;
+    return b.rc;
+}
+// matrix and status of window w -> host
+inline int PoseCovariance::read(int w, int64_t cap, double* out, int32_t* status) {
+    limo_ctx* ctx = b.ctx;
+    *status = LIMO_COV_NOT_COMPUTED;
+    if (!computed) return LIMO_OK;
+    const int64_t n = cov_off[w + 1] - cov_off[w];
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status + w, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out && n) HIP_TRY(ctx, hipMemcpyAsync(out, d_cov + cov_off[w], sizeof(double) * (size_t)std::min(n, cap), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return LIMO_OK;
+}
+// every window's matrix into the context's buffer (limo_ctx_last_pose_covariance), for the calls that destroy their batch
+inline int PoseCovariance::export_to_ctx() {
+    limo_ctx* ctx = b.ctx;
+    ctx->last_cov.clear();
+    ctx->last_cov_status.clear();
+    ctx->last_cov_off.clear();
+    if (!computed) return LIMO_OK;
+    const int n_win = b.P.n_win;
+    ctx->last_cov.resize((size_t)cov_off[n_win]);
+    ctx->last_cov_status.resize(n_win);
+    ctx->last_cov_off.assign(cov_off.begin(), cov_off.end());
+    if (cov_off[n_win]) HIP_TRY(ctx, hipMemcpyAsync(ctx->last_cov.data(), d_cov, sizeof(double) * (size_t)cov_off[n_win], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->last_cov_status.data(), d_status, sizeof(int32_t) * n_win, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return LIMO_OK;
 }

@@ -63,6 +63,13 @@ struct limo_ctx {
     std::vector<limo_ba_iteration> last_log;
     std::vector<int32_t> last_log_n;
     std::vector<size_t> last_log_off;
+    // pose covariance (limo_ctx_set_pose_covariance): the switch every solve reads, and the matrices of the windows of the last call
+    // that made and destroyed its own batch (limo_ctx_last_pose_covariance): window w has (6 n_kf)^2 doubles from last_cov_off[w].
+    // last_cov_status empty: nothing held (switch off, limo_ba_solve_sharded) - LIMO_COV_NOT_COMPUTED for any window
+    bool pose_covariance = false;
+    std::vector<double> last_cov;
+    std::vector<int32_t> last_cov_status;
+    std::vector<size_t> last_cov_off;
     // limo_select_set_timing: HIP events around the kernels of limo_landmark_select[_batch]; the device time of the last call
     bool select_timing = false;
     double select_last_ms = 0.;

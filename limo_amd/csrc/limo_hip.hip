@@ -229,6 +229,9 @@ static int batch_solve_impl(limo_ba_batch* b, const limo_ba_options* opts, const
     const int gathered = b->shards.gather_landmarks();
     if (gathered != LIMO_OK) return gathered;
     b->publish_run();
+    // pose covariance: the pass behind the solve's last launch, after the record of the solve is taken (its launches are not the solve's)
+    b->cov.computed = false;
+    if (ctx->pose_covariance && b->rc == LIMO_OK && b->cov.run() != LIMO_OK) return LIMO_ERR_RUNTIME;
     if (b->timers.stop_solve() != LIMO_OK) return LIMO_ERR_RUNTIME;
     return b->rc;
 }
@@ -467,8 +470,12 @@ int limo_ba_solve_sharded(limo_ctx* ctx, limo_ba_window* window, const limo_ba_o
     ctx->last_log.clear();  // (no iteration log on this path: limo_ctx_last_iteration_log reports zero entries after it)
     ctx->last_log_n.clear();
     ctx->last_log_off.clear();
+    ctx->last_cov.clear();  // (nor a pose covariance: LIMO_COV_NOT_COMPUTED)
+    ctx->last_cov_status.clear();
+    ctx->last_cov_off.clear();
     int rc = batch_create_impl(ctx, 1, window, opts, po, &b, ranks);
     if (rc != LIMO_OK) return rc;
+    b->cov.offered = false;  // (also with one shard: the call reports none, so it does not pay for the pass)
     rc = limo_ba_batch_solve(b, opts);
     limo_ba_report rep;
     if (rc == LIMO_OK) rc = limo_ba_batch_download(b, window, &rep);
@@ -501,6 +508,8 @@ static int solve_n(limo_ctx* ctx, int32_t n, limo_ba_window* windows, const limo
     {   // the windows' iteration logs outlive the batch in the context's buffer (empty with the switch off)
         const int lrc = b->log.export_to_ctx();
         if (rc == LIMO_OK) rc = lrc;
+        const int crc = b->cov.export_to_ctx();  // (and their pose covariances)
+        if (rc == LIMO_OK) rc = crc;
     }
     const auto t2 = Clock::now();
     if (reports)
@@ -579,6 +588,55 @@ int limo_ctx_last_iteration_log(limo_ctx* ctx, int32_t window, int32_t cap, limo
     *n = ctx->last_log_n[window];
     const int m = std::min(*n, cap);
     if (m > 0) std::memcpy(out, ctx->last_log.data() + ctx->last_log_off[window], sizeof(limo_ba_iteration) * m);
+    return LIMO_OK;
+}
+
+int limo_ctx_set_pose_covariance(limo_ctx* ctx, int32_t on) {
+    if (!ctx) return LIMO_ERR_INVALID;
+    ctx->pose_covariance = on != 0;
+    return LIMO_OK;
+}
+
+// the argument checks the two readers share (n_win < 0: nothing held, any window >= 0 passes); null: the arguments are fine
+static const char* pose_covariance_args(int32_t window, int32_t n_win, int64_t cap, const double* out, const int32_t* status) {
+    if (!status) return "status is NULL";
+    if (cap < 0) return "cap_doubles < 0";
+    if (cap > 0 && !out) return "out is NULL with cap_doubles > 0";
+    if (window < 0 || (n_win >= 0 && window >= n_win)) return "window out of range";
+    return nullptr;
+}
+
+int limo_ba_batch_pose_covariance(limo_ba_batch* b, int32_t window, int64_t cap_doubles, double* out, int32_t* status) {
+    if (!b) return LIMO_ERR_INVALID;
+    limo_ctx* ctx = b->ctx;
+    if (const char* bad = pose_covariance_args(window, b->P.n_win, cap_doubles, out, status)) {
+        ctx->err = std::string("limo_ba_batch_pose_covariance: ") + bad;
+        return LIMO_ERR_INVALID;
+    }
+    if (out && b->cov.computed && cap_doubles < b->cov.cov_off[window + 1] - b->cov.cov_off[window]) {
+        ctx->err = "limo_ba_batch_pose_covariance: cap_doubles < (6 n_kf)^2";
+        return LIMO_ERR_INVALID;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return LIMO_ERR_NO_DEVICE;
+    return b->cov.read(window, cap_doubles, out, status);
+}
+
+int limo_ctx_last_pose_covariance(limo_ctx* ctx, int32_t window, int64_t cap_doubles, double* out, int32_t* status) {
+    if (!ctx) return LIMO_ERR_INVALID;
+    const int32_t n_win = ctx->last_cov_status.empty() ? -1 : (int32_t)ctx->last_cov_status.size();
+    if (const char* bad = pose_covariance_args(window, n_win, cap_doubles, out, status)) {
+        ctx->err = std::string("limo_ctx_last_pose_covariance: ") + bad;
+        return LIMO_ERR_INVALID;
+    }
+    *status = LIMO_COV_NOT_COMPUTED;
+    if (n_win < 0) return LIMO_OK;
+    const size_t n = ctx->last_cov_off[window + 1] - ctx->last_cov_off[window];
+    if (out && (size_t)cap_doubles < n) {
+        ctx->err = "limo_ctx_last_pose_covariance: cap_doubles < (6 n_kf)^2";
+        return LIMO_ERR_INVALID;
+    }
+    *status = ctx->last_cov_status[window];
+    if (out && n) std::memcpy(out, ctx->last_cov.data() + ctx->last_cov_off[window], sizeof(double) * n);
     return LIMO_OK;
 }
 

@@ -249,6 +249,24 @@ void BundleAdjusterKeyframes::collectIterations(limo_ctx* ctx, const char* what)
     std::fflush(stdout);
 }
 
+// The pose-covariance entry points are weak references as well: with a backend that lacks them the shim reports LIMO_COV_NOT_COMPUTED.
+#pragma weak limo_ctx_set_pose_covariance
+#pragma weak limo_ctx_last_pose_covariance
+
+void BundleAdjusterKeyframes::setCovarianceSwitch(limo_ctx* ctx, WindowJob& job) {
+    job.cov.clear();
+    job.cov_status = LIMO_COV_NOT_COMPUTED;
+    if (&limo_ctx_set_pose_covariance != nullptr) (void)limo_ctx_set_pose_covariance(ctx, pose_covariance_ ? 1 : 0);
+}
+
+void BundleAdjusterKeyframes::collectCovariance(limo_ctx* ctx, WindowJob& job) {
+    if (!pose_covariance_ || &limo_ctx_last_pose_covariance == nullptr) return;
+    const size_t n = (size_t)36 * job.window->n_kf * job.window->n_kf;
+    job.cov.assign(n, 0.);
+    if (limo_ctx_last_pose_covariance(ctx, 0, (int64_t)n, job.cov.data(), &job.cov_status) != LIMO_OK) job.cov_status = LIMO_COV_NOT_COMPUTED;
+    if (job.cov_status == LIMO_COV_NOT_COMPUTED) job.cov.clear();
+}
+
 void BundleAdjusterKeyframes::set_solver_time(double s) {
     this->solver_time_sec = s;
 }
@@ -876,10 +894,25 @@ void BundleAdjusterKeyframes::prepareSolve(WindowJob& job) {
     dump_window_if_asked(F.w, dump_tag_, dump_calls_);
 }
 
+// the 6 x 6 diagonal block of every keyframe of the job's window, by keyframe id (a call without a matrix leaves the map empty)
+void BundleAdjusterKeyframes::keepCovariance(const WindowJob& job) {
+    last_pose_cov_.clear();
+    const size_t n_kf = job.flat->kfs.size(), n6 = 6 * n_kf;
+    if (job.cov_status == LIMO_COV_NOT_COMPUTED || job.cov.size() != n6 * n6) return;
+    for (size_t k = 0; k < n_kf; ++k) {
+        PoseCovariance pc;
+        pc.status = job.cov_status;
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) pc.cov[6 * i + j] = job.cov[(6 * k + i) * n6 + 6 * k + j];
+        last_pose_cov_[job.flat->kfs[k]->timestamp_] = pc;
+    }
+}
+
 // commitSolve: poses, planes and landmarks of the solved window back into the objects, job.report into last_report_; the report string.
 void BundleAdjusterKeyframes::runSolve(WindowJob& job) {
     limo_ctx* ctx = context();
     setIterationLog(ctx);
+    setCovarianceSwitch(ctx, job);
     int rc;
     {
         AddMicros t{shim_us_.call};
@@ -888,6 +921,7 @@ void BundleAdjusterKeyframes::runSolve(WindowJob& job) {
     if (rc == LIMO_ERR_NOT_ENOUGH_KF) throw NotEnoughKeyframesException(job.flat->kfs.size(), 3);
     checkCall(ctx, rc, "limo_ba_solve");
     collectIterations(ctx, "solve");
+    collectCovariance(ctx, job);
 }
 
 std::string BundleAdjusterKeyframes::commitSolve(WindowJob& job) {
@@ -896,6 +930,7 @@ std::string BundleAdjusterKeyframes::commitSolve(WindowJob& job) {
         AddMicros t{write_back};
         job.flat->write_back(true);
         last_report_ = last_report_of(job.report);
+        keepCovariance(job);
     }
     if (shim_trace)
         std::fprintf(stderr, "[shim] solve: %zu active landmarks, %zu selected, %d LM iterations in %d solves: active maps + selection %.0f us, flatten %.0f us, limo_ba_solve %.0f us, write-back %.0f us\n",
@@ -965,17 +1000,21 @@ void BundleAdjusterKeyframes::preparePoseOnly(Keyframe& kf, WindowJob& job) {
     job.has_prior = prior.speed_weight > 0.0;
     job.opts = window_options(outlier_rejection_options_, 30, solver_time_sec);  // :865
     job.report = limo_ba_report{};
+    job.cov.clear();
+    job.cov_status = LIMO_COV_NOT_COMPUTED;
 }
 
 // commitPoseOnly: the refined pose (and plane) back into the frame's keyframe, job.report into last_report_; the report string.
 void BundleAdjusterKeyframes::runPoseOnly(WindowJob& job) {
     limo_ctx* ctx = context();
     setIterationLog(ctx);
+    setCovarianceSwitch(ctx, job);
     {
         AddMicros t{shim_us_.call};
         checkCall(ctx, limo_ba_adjust_pose_only(ctx, job.window, job.has_prior ? &job.prior : nullptr, &job.opts, &job.report), "limo_ba_adjust_pose_only");
     }
     collectIterations(ctx, "adjustPoseOnly");
+    collectCovariance(ctx, job);
 }
 
 std::string BundleAdjusterKeyframes::commitPoseOnly(WindowJob& job) {
@@ -985,6 +1024,7 @@ std::string BundleAdjusterKeyframes::commitPoseOnly(WindowJob& job) {
         AddMicros t{write_back};
         job.flat->write_back(false);
         last_report_ = last_report_of(job.report);
+        keepCovariance(job);
         summary = report_string(job.report, "adjustPoseOnly");
     }
     if (shim_trace)

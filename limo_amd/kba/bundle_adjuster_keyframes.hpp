@@ -92,6 +92,27 @@ public:
         return last_iterations_;
     }
 
+    // Marginal covariance of the poses a call returns (not in the reference; include/limo_hip.h, "Pose covariance": what
+    // ceres::Covariance::GetCovarianceBlockInTangentSpace gives for a pose block of the problem just solved).  setPoseCovariance(true):
+    // solve() and adjustPoseOnly() switch the library's pass on and keep, for every keyframe of their window, the 6 x 6 block
+    // (rotation 3 | translation 3, row-major, the solve's tangent units: the rotation tangent is a left-multiplied HALF-angle vector)
+    // and the window's status; lastPoseCovariance(id) reads the last call's.  A keyframe the last call did not hold, the switch off
+    // and a backend without the symbols give LIMO_COV_NOT_COMPUTED and zeros.
+    struct PoseCovariance {
+        std::array<double, 36> cov{};
+        int status = LIMO_COV_NOT_COMPUTED;
+    };
+    void setPoseCovariance(bool on) { pose_covariance_ = on; }
+    bool poseCovariance() const { return pose_covariance_; }
+    PoseCovariance lastPoseCovariance(KeyframeId id) const {
+        const auto it = last_pose_cov_.find(id);
+        return it == last_pose_cov_.end() ? PoseCovariance() : it->second;
+    }
+    // ... in rotation-vector units: the rotation rows and columns times 2
+    static void toRotationVectorUnits(std::array<double, 36>& c) {
+        for (int i = 0; i < 36; ++i) c[i] *= (i / 6 < 3 ? 2. : 1.) * (i % 6 < 3 ? 2. : 1.);
+    }
+
     // Where solve() selects its landmarks (not in the reference).  With parameters set, solve() flattens the active landmarks, minus the
     // selector's outliers, into a limo_select_pool and calls limo_landmark_select (the device form of cheirality + voxel + add-depth as
     // StreamDriver wires them: include/limo_hip.h); the selector takes the result over (LandmarkSelector::acceptSelection), so outliers,
@@ -128,6 +149,10 @@ public:
         bool has_prior = false;
         limo_ba_options opts{};
         limo_ba_report report{};           // result
+        // result, with setPoseCovariance(true): the window's [6 n_kf][6 n_kf] matrix and status (whoever makes the call fills them:
+        // run..., or the lock-step driver from limo_ctx_last_pose_covariance of its batched call); commit... keeps the keyframes' blocks
+        std::vector<double> cov;
+        int32_t cov_status = LIMO_COV_NOT_COMPUTED;
     };
     void preparePoseOnly(Keyframe& kf, WindowJob& job);
     void runPoseOnly(WindowJob& job);
@@ -177,6 +202,11 @@ private:
     void setIterationLog(limo_ctx* ctx);      // before the solve: the context's switch follows minimizer_progress_to_stdout_
     void collectIterations(limo_ctx* ctx, const char* what);  // behind it: last_iterations_ and the table
     std::vector<limo_ba_iteration> last_iterations_;
+    void setCovarianceSwitch(limo_ctx* ctx, WindowJob& job);   // before the call: the context's switch follows pose_covariance_
+    void collectCovariance(limo_ctx* ctx, WindowJob& job);     // behind it: window 0 of the call into job.cov / job.cov_status
+    void keepCovariance(const WindowJob& job);                 // commit...: last_pose_cov_ from the job
+    bool pose_covariance_ = false;
+    std::map<KeyframeId, PoseCovariance> last_pose_cov_;
     // LIMO_SHIM_TRACE=1: where the host time of adjustPoseOnly() / solve() goes.  Every half and piece adds its microseconds here;
     // commitPoseOnly / commitSolve print the line and start over (a call somebody else made, a batched one, shows as 0 us).
     struct ShimTimes {

@@ -129,6 +129,8 @@ private:
 #pragma weak limo_five_point_batch
 #pragma weak limo_ba_adjust_pose_only_batch
 #pragma weak limo_ba_adjust_pose_only_batch_each
+#pragma weak limo_ctx_set_pose_covariance
+#pragma weak limo_ctx_last_pose_covariance
 #pragma weak limo_ba_batch_solve_each
 #pragma weak limo_landmark_select
 #pragma weak limo_landmark_select_batch
@@ -291,6 +293,18 @@ public:
         {
             const auto ref = those(act, &Sequence::wantsPoseOnly);
             Timed t(stats_.pose_only.sec_abi);
+            // pose covariance (StreamParams::pose_covariance): the call ends with the library's pass when a sequence of it asks, and
+            // window `window` of the call that has just returned goes into the job of the sequence it belongs to
+            bool want_cov = false;
+            for (Sequence* s : ref) want_cov = want_cov || s->p.pose_covariance;
+            want_cov = want_cov && &limo_ctx_set_pose_covariance != nullptr && &limo_ctx_last_pose_covariance != nullptr;
+            if (!ref.empty() && &limo_ctx_set_pose_covariance != nullptr) check(limo_ctx_set_pose_covariance(ctx_, want_cov ? 1 : 0), "limo_ctx_set_pose_covariance");
+            auto fetch_cov = [&](Sequence* s, size_t window) {
+                if (!want_cov || !s->p.pose_covariance) return;
+                BundleAdjusterKeyframes::WindowJob& j = s->pose_job;
+                j.cov.assign((size_t)36 * j.window->n_kf * j.window->n_kf, 0.);
+                check(limo_ctx_last_pose_covariance(ctx_, (int32_t)window, (int64_t)j.cov.size(), j.cov.data(), &j.cov_status), "limo_ctx_last_pose_covariance");
+            };
             if (ref.empty()) {
             } else if (&limo_ba_adjust_pose_only_batch != nullptr) {
                 std::vector<limo_ba_window> ws;
@@ -308,10 +322,12 @@ public:
                 if (groups.size() == 1) {
                     check(limo_ba_adjust_pose_only_batch(ctx_, (int32_t)ws.size(), ws.data(), priors.data(), &opts[0], reports.data()), "limo_ba_adjust_pose_only_batch");
                     batched(stats_.pose_only, ref.size());
+                    for (size_t k = 0; k < ref.size(); ++k) fetch_cov(ref[k], k);
                 } else if (&limo_ba_adjust_pose_only_batch_each != nullptr) {
                     check(limo_ba_adjust_pose_only_batch_each(ctx_, (int32_t)ws.size(), ws.data(), priors.data(), opts.data(), reports.data()), "limo_ba_adjust_pose_only_batch_each");
                     batched(stats_.pose_only, ref.size());
                     ++stats_.pose_only.per_window_calls;
+                    for (size_t k = 0; k < ref.size(); ++k) fetch_cov(ref[k], k);
                 } else {
                     for (const std::vector<size_t>& g : groups) {
                         std::vector<limo_ba_window> gw;
@@ -320,6 +336,7 @@ public:
                         std::vector<limo_ba_report> gr(g.size());
                         check(limo_ba_adjust_pose_only_batch(ctx_, (int32_t)gw.size(), gw.data(), gp.data(), &opts[g[0]], gr.data()), "limo_ba_adjust_pose_only_batch");
                         for (size_t i = 0; i < g.size(); ++i) reports[g[i]] = gr[i];
+                        for (size_t i = 0; i < g.size(); ++i) fetch_cov(ref[g[i]], i);
                         batched(stats_.pose_only, g.size());
                     }
                 }
@@ -328,9 +345,11 @@ public:
                 for (Sequence* s : ref) {
                     BundleAdjusterKeyframes::WindowJob& j = s->pose_job;
                     check(limo_ba_adjust_pose_only(ctx_, j.window, j.has_prior ? &j.prior : nullptr, &j.opts, &j.report), "limo_ba_adjust_pose_only");
+                    fetch_cov(s, 0);
                     ++stats_.pose_only.fallback_calls;
                 }
             }
+            if (want_cov) check(limo_ctx_set_pose_covariance(ctx_, 0), "limo_ctx_set_pose_covariance");  // (the tick's solves do not pay for the pass)
         }
 
         // ---- 4. keyframe selection per sequence, the pushes of all sequences through one limo_landmark_init
@@ -451,6 +470,7 @@ public:
 
     // KITTI odometry rows of sequence i: those of a StreamDriver given the same frames
     void writeKittiTrajectory(size_t i, std::ostream& os) const { seqs_.at(i)->writeKittiTrajectory(os); }
+    void writeCovariances(size_t i, std::ostream& os) const { seqs_.at(i)->writeCovariances(os); }  // (StreamParams::pose_covariance)
 
     BundleAdjusterKeyframes& adjuster(size_t i) { return seqs_.at(i)->ba; }
     const std::vector<EigenPose>& poses(size_t i) const { return seqs_.at(i)->poses; }

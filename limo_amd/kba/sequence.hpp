@@ -71,6 +71,10 @@ struct StreamParams {
     // below) where the library behind the C-ABI has it, else - and always with `false` - the host selector.  The two give the same
     // selection, hence the same pose rows.  The default follows the measurement of BASELINE.md §4.17.
     bool landmark_selection_on_device = false;
+    // Marginal covariance of every refined frame pose (not in the reference; include/limo_hip.h, "Pose covariance"): the frame's
+    // adjustPoseOnly ends with the library's covariance pass and the sequence keeps its 6 x 6 block and status per frame
+    // (Sequence::covariances, writeCovariances).  No pose changes with it.
+    bool pose_covariance = false;
     // landmark selection (keyframe_ba_monolid.launch:36-38; wiring of MonoLidar::reconfigureRequest, mono_lidar.cpp:396-430)
     unsigned max_number_landmarks_near_bin = 200, max_number_landmarks_middle_bin = 200, max_number_landmarks_far_bin = 100;
     double roi_middle = 15., roi_far = 40.;                            // :405-408
@@ -133,6 +137,7 @@ auto timed(double& sec, F&& fn) -> decltype(fn()) {  // ... the time of fn()
 // the node's wiring of keyframe selection and landmark selection (mono_lidar.cpp:396-430) for one sequence's adjuster
 inline void configureSequence(const StreamParams& p, BundleAdjusterKeyframes& ba, KeyframeSelector& selector) {
     ba.set_solver_time(p.solver_time_sec);
+    ba.setPoseCovariance(p.pose_covariance);
     ba.outlier_rejection_options_.depth_thres = p.robust_loss_depth_thres;
     ba.outlier_rejection_options_.reprojection_thres = p.robust_loss_reprojection_thres;
     ba.outlier_rejection_options_.depth_quantile = p.outlier_rejection_quantile;
@@ -397,6 +402,7 @@ struct Sequence {
         if (has_external) prior = *external_prior;
         stamp = tracklets.stamps.front();
         first = is_keyframe = solve_due = false;
+        frame_cov = BundleAdjusterKeyframes::PoseCovariance();
         five_point_query.estimate = false;
     }
 
@@ -474,6 +480,7 @@ struct Sequence {
         if (wantsPoseOnly()) {
             timed(stats.sec_pose_only, [&] { ba.commitPoseOnly(pose_job); });
             stats.sec_abi_pose_only += ba.last_report_.time_sec;
+            if (p.pose_covariance) frame_cov = ba.lastPoseCovariance(stamp);
             trace("pose-only", cur->pose_);
         }
         pose = cur->getEigenPose();
@@ -532,6 +539,7 @@ struct Sequence {
         ++stats.frames;
         stats.keyframes += is_keyframe;
         poses.push_back(pose);
+        if (p.pose_covariance) covariances.push_back(frame_cov);
         cur.reset();
         pose_job.flat.reset(), solve_job.flat.reset(), select.flat.reset();
         return poses.back();
@@ -543,6 +551,20 @@ struct Sequence {
         for (const auto& pose_kf_origin : poses) kitti_io::writePoseRow(os, kitti_io::inCameraFrame(cv, pose_kf_origin.inverse()));
     }
 
+    // StreamParams::pose_covariance: one row per frame so far - the 36 numbers of the covariance of the frame's adjustPoseOnly (tangent
+    // units of limo_hip.h, %.17g) and its status; a frame that was not refined (the first, one with an external prior) has zeros and
+    // LIMO_COV_NOT_COMPUTED
+    void writeCovariances(std::ostream& os) const {
+        char buf[40];
+        for (const auto& c : covariances) {
+            for (double v : c.cov) {
+                std::snprintf(buf, sizeof(buf), "%.17g ", v);
+                os << buf;
+            }
+            os << c.status << "\n";
+        }
+    }
+
     const StreamParams& p;
     Camera::Ptr camera;
     BundleAdjusterKeyframes ba;
@@ -551,6 +573,8 @@ struct Sequence {
     MotionState motion;
     StreamStats stats;
     std::vector<EigenPose> poses;
+    std::vector<BundleAdjusterKeyframes::PoseCovariance> covariances;  // per frame, with StreamParams::pose_covariance
+    BundleAdjusterKeyframes::PoseCovariance frame_cov;                // ... of the frame in flight
     std::string last_summary;
     five_point::Motion last_five_point;  // the last five-point estimate (diagnostics: inliers, samples)
     std::vector<float> uv, depth, point_d;  // staging of the sweep call, its result, the depth of every point of the message

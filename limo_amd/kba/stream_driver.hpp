@@ -144,6 +144,7 @@ public:
 
     // KITTI odometry rows of the frames so far, 12 numbers per line (mono_lidar.cpp:281-294)
     void writeKittiTrajectory(std::ostream& os) const { seq_.writeKittiTrajectory(os); }
+    void writeCovariances(std::ostream& os) const { seq_.writeCovariances(os); }  // (StreamParams::pose_covariance)
 
     BundleAdjusterKeyframes& adjuster() { return seq_.ba; }
     const std::vector<EigenPose>& poses() const { return seq_.poses; }
